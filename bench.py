@@ -16,8 +16,15 @@ region, so inputs are resident in HBM when it starts.
 
 The headline (`value`, `dtype`, `roofline`, `valu`, `lds`) is measured on the f64 kernel -- Float64 is the
 reference's arithmetic (inc/types.jl, inc/eap_chain.jl:12-36) and that kernel reproduces the CPU oracle bit for
-bit.  The f32 kernel (f32 state and transcendentals, f64 running sums; the survey-sanctioned fast path) is timed
-in the same run with the same K/W and reported in the sibling object `fast_path`.
+bit.  A plain run measures the headline and nothing else.  With --full, the f32 kernel (f32 state and
+transcendentals, f64 running sums; the survey-sanctioned fast path) is timed in the same run with the same K/W and
+reported in the sibling object `fast_path`, and the other objects named below are measured too.
+
+--dump-outputs DIR writes what the last timed step computed, as float64 .npy files (rank 0): `reduction` (the
+all-reduced NRED-double vector that reduce_into hands the caller), `avg` / `stderr` / `acceptance` (the pooled summary
+made from it) and `chain_means` [NQ x chains] (the per-chain running means that vector folds; rank 0's chains, a
+fixed seeded sample of them when they would exceed 48 MB, their indices in `chain_index`).  Inputs are seeded, so the
+same arguments give the same inputs from run to run.
 
 Prints ONE JSON line (rank 0).  `roofline.achieved` = algorithmic bytes (32 B per attempted update in f64: one
 (theta, phi) pair read and written; 16 B in f32 -- SURVEY.md 8(d)) x updates per launch / mean launch time
@@ -29,8 +36,10 @@ VALU issue (`valu`); `lds` is the third fraction SURVEY 8(d) asks for.  `traffic
 the PMC passes in profiles/pmc_traffic.json and are used only if that file was collected on the kernel sources being
 benchmarked (sha256 stamp), else null / estimate.
 
-Beside the headline: `configs` (one measured entry per BASELINE configuration) and `phase_scan` (the clustering main on the
-ensemble shape the reference launches its phase scans with: 2 730 single-chain cases; microseconds per step).
+With --full, beside the headline: `fast_path`, `rng_named` (the headline under xoshiro128++), `cpu_baseline` (the CPU
+restatement timed on the host, with the parity of the device path against it), `configs` (one measured entry per BASELINE
+configuration) and `phase_scan` (the clustering main on the ensemble shape the reference launches its phase scans with:
+2 730 single-chain cases; microseconds per step).
 """
 from __future__ import annotations
 
@@ -55,6 +64,7 @@ VALU_F64_OPS_ESTIMATE = {"f64": 128.0}                   # of which f64 ops (DES
 STATE_BYTES = {"f32": 16, "f64": 32, "q16": 8}              # one state cell read + written per attempted update
 DTYPE = {"f32": "f32 state+transcendentals, f64 running sums", "f64": "f64",
          "q16": "u16 lattice angles, f32 transcendentals, f64 running sums"}
+DUMP_MEANS_BYTES = 48 << 20                 # cap of --dump-outputs' chain_means: the whole dump stays under 64 MB
 
 
 def kernel_source_hash() -> str:
@@ -263,6 +273,22 @@ def parity_vs_cpu(ps, prec, n, chains, mc_steps, device, cpu_mean, cpu_se):
     return out
 
 
+def dump_outputs(out_dir, red, means, last):
+    """--dump-outputs: the last timed step's results as float64 .npy files (module docstring)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    nq, m = means.shape
+    idx = np.arange(m)
+    keep = DUMP_MEANS_BYTES // (8 * nq)
+    if m > keep:
+        idx = np.sort(np.random.default_rng(20260501).choice(m, keep, replace=False))
+    arrays = {"reduction": red, "avg": list(last.avg), "stderr": list(last.stderr),
+              "acceptance": [last.acceptance_ratio, last.ar_stderr], "chain_means": means[:, idx], "chain_index": idx}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+    log(f"outputs of the last timed step written to {out_dir}: {', '.join(arrays)}")
+
+
 def spawn_ranks(args) -> int:
     """--gpus N > 1 from a bare shell (WORLD_SIZE unset): start N fresh rank processes, one per GPU, BEFORE this
     process makes any GPU call (it never does: torch is not even imported here), relay rank 0's JSON line, and
@@ -301,7 +327,14 @@ def main():
     ap.add_argument("--force-dist", action="store_true", help="initialise the process group even for one rank")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="collective backend; gloo (via host memory) only to rehearse N>1 on a box with fewer GPUs")
+    ap.add_argument("--full", action="store_true",
+                    help="measure more than the headline: fast_path, rng_named, cpu_baseline (+ parity), configs, phase_scan "
+                         "(each still subject to its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step computed to DIR/<name>.npy (float64, rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
@@ -352,8 +385,9 @@ def main():
     nstep_total = args.steps + args.warmup
     red = torch.zeros(ps.NRED, dtype=torch.float64, device="cuda")
 
-    def measure(precision: str, rng_name: str = None):
-        """W warm-up + K timed bench steps of the sweep kernel in `precision`; returns the timing record."""
+    def measure(precision: str, rng_name: str = None, keep_means: bool = False):
+        """W warm-up + K timed bench steps of the sweep kernel in `precision`; returns the timing record (with the last
+        step's per-chain means if `keep_means`)."""
         prec = PREC[precision]
         rng_name = rng_name or args.rng
         with torch.cuda.stream(stream):
@@ -405,10 +439,12 @@ def main():
         elapsed = float(t.item())
         kernel_ms = [a.elapsed_time(b) for a, b in events]
         ens[-1].sync()           # surfaces a timed-out persistent launch (PSTAT_ERR_HIP) instead of timing garbage
-        last = ps.summary_from_reduction(red.cpu().tolist(), args.mc_steps)
+        red_host = red.cpu().tolist()
+        last = ps.summary_from_reduction(red_host, args.mc_steps)
+        means = ens[-1].chain_means() if keep_means else None
         for e in ens:
             e.close()
-        return dict(precision=precision, elapsed=elapsed, kernel_ms=kernel_ms, last=last, info=info)
+        return dict(precision=precision, elapsed=elapsed, kernel_ms=kernel_ms, last=last, info=info, red=red_host, means=means)
 
     def price(rec, pmc):
         """value / roofline / valu / lds of one timing record."""
@@ -486,11 +522,13 @@ def main():
                       "chains_collapsed": int(last.chains_collapsed)},
         }
 
-    head = measure(args.precision)
+    head = measure(args.precision, keep_means=bool(args.dump_outputs) and rank == 0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, head["red"], head["means"], head["last"])
     fast = named = None
-    if args.precision == "f64" and not args.no_fast_path:
+    if args.full and args.precision == "f64" and not args.no_fast_path:
         fast = measure("f32")
-    if args.precision == "f64" and args.rng == "mwc64x" and not args.no_rng_named:
+    if args.full and args.precision == "f64" and args.rng == "mwc64x" and not args.no_rng_named:
         named = measure("f64", "xoshiro128++")    # the generator the north star names, on the headline kernel
 
     if rank == 0:
@@ -536,13 +574,13 @@ def main():
                                 "note": "same kernel, workload, K and W as the headline, which runs the default MWC64X "
                                         "(one v_mad_u64_u32 + one v_xor per draw against ten 32-bit ops; DESIGN.md section 4)"}
         base = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             base, cpu_mean, cpu_se = cpu_baseline(args.n, args.mc_steps, args.cpu_seconds)
             base["parity"] = parity_vs_cpu(ps, PREC[args.precision], args.n, args.chains, args.mc_steps, local_rank, cpu_mean, cpu_se)
             if fast is not None:
                 base["parity_fast_path"] = parity_vs_cpu(ps, ps.F32, args.n, args.chains, args.mc_steps, local_rank, cpu_mean, cpu_se)
             out["cpu_baseline"] = base
-        if world == 1 and not args.no_configs and args.precision == "f64" and args.n == 100:
+        if world == 1 and args.full and not args.no_configs and args.precision == "f64" and args.n == 100:
             kern_ms = h["roofline"]["kernel_ms"]
             headline = {"rate": args.chains * args.mc_steps / (kern_ms * 1e-3), "kernel_ms": kern_ms, "kernel": h["kernel"],
                         "check": h["check"]}

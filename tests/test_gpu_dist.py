@@ -64,7 +64,7 @@ def test_bench_starts_its_own_ranks(tmp_path):
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1",
-           "--chains", "4096", "--mc-steps", "3000", "--no-cpu-baseline"]
+           "--chains", "4096", "--mc-steps", "3000", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -167,13 +167,14 @@ def test_phase_scan_four_ranks_equal_one_rank(tmp_path):
 
 
 def test_bench_line_carries_one_measured_entry_per_baseline_config(tmp_path):
-    """The default bench line's `configs` array (rank 0 at N = 1): C1..C5 in f64 at BASELINE.json's sizes, each with its
+    """The --full bench line's `configs` array (rank 0 at N = 1): C1..C5 in f64 at BASELINE.json's sizes, each with its
     kernel, rate, roofline fraction and both CPU baselines (oracle faithful and fast) -- the headline keys untouched."""
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--mc-steps", "3000",
-                        "--chains", "4096", "--cpu-seconds", "0.5", "--config-cpu-seconds", "0.2", "--no-fast-path", "--no-rng-named"],
+                        "--chains", "4096", "--cpu-seconds", "0.5", "--config-cpu-seconds", "0.2", "--no-fast-path", "--no-rng-named",
+                        "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads(r.stdout.strip())
@@ -199,3 +200,39 @@ def test_bench_line_carries_one_measured_entry_per_baseline_config(tmp_path):
     scan = d["phase_scan"]            # the clustering main on the reference's own phase-scan ensemble: one chain per wavefront
     assert scan["chains"] == 2730 and scan["workgroups"] == 2730 and "cluster_chain_wave_kernel" in scan["kernel"]
     assert 0 < scan["us_per_step"] < 50 and scan["value"] == pytest.approx(2730 / (scan["us_per_step"] * 1e-6), rel=1e-3)
+
+
+def test_plain_bench_line_is_the_headline_alone_and_dumps_its_last_step(tmp_path):
+    """A plain run (no --full) measures the headline and nothing beside it; --dump-outputs writes the last timed step's
+    results as float64 arrays, identical from run to run, and the line's `check` is the summary of that step's reduction."""
+    import json
+    import subprocess
+    import polymer_stats_amd as ps
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    names = ("reduction", "avg", "stderr", "acceptance", "chain_means", "chain_index")
+    lines, dumps = [], []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--chains", "4096",
+                            "--mc-steps", "3000", "--dump-outputs", str(tmp_path / run)],
+                           env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(out) == 1, r.stdout
+        lines.append(json.loads(out[0]))
+        dumps.append({k: np.load(tmp_path / run / (k + ".npy")) for k in names})
+    d = lines[0]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "check"):
+        assert key in d, key
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert d["value"] == pytest.approx(4096 * 3000 / (d["ms_per_step"] * 1e-3), rel=1e-6)
+    for key in ("fast_path", "rng_named", "cpu_baseline", "configs", "phase_scan"):
+        assert key not in d, key
+    a, b = dumps
+    for k in names:
+        assert a[k].dtype == np.float64, k
+        np.testing.assert_array_equal(a[k], b[k], err_msg=k)
+    assert a["reduction"].shape == (ps.NRED,) and a["reduction"][0] == 4096
+    assert a["chain_means"].shape == (ps.NQ, 4096) and np.array_equal(a["chain_index"], np.arange(4096))
+    assert a["avg"][2] == d["check"]["r3"] and a["stderr"][2] == d["check"]["r3_stderr"] and a["acceptance"][0] == d["check"]["AR"]
+    np.testing.assert_allclose(a["chain_means"][2].mean(), d["check"]["r3"], rtol=1e-9)
+    assert sum(os.path.getsize(tmp_path / "a" / (k + ".npy")) for k in names) < 64 << 20
