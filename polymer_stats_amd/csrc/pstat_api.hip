@@ -44,6 +44,36 @@ struct Buffer {
   size_t bytes = 0;
 };
 
+// Knobs for tests and experiments that force a choice the handle would otherwise make by its own measured rules.  Read once,
+// when the handle is created; unset or out of range, each leaves that rule in charge.
+//   PSTAT_F64_STATE=w...    the chain-per-wavefront kernel, for a configuration it covers (choose_home)
+//   PSTAT_F64_STATE=l|g...  rules that kernel out; the f64 chain-per-lane kernels keep their cells in LDS | in memory
+//   PSTAT_F32_STATE=l|g...  the f32 clustering main keeps its chains in LDS | in memory
+//   PSTAT_PACK=0|1          set at all, rules out the chain-per-wavefront kernel; forces packed cases off | on for a
+//                           chain-per-lane home with ncases > 1, and 1 prices the packed layout as a deep launch (shape)
+//   PSTAT_LANES=k           lanes per workgroup: 1..64 for ClusterMem, 1..the LDS lane cap for the LDS homes (not SweepMem)
+//   PSTAT_F64_LDS_ROWS=k    SweepMem: monomers whose cells stay in LDS, 0..the rows of a quarter of the LDS
+//   PSTAT_SEGMENTS=k        time segments per chain-per-lane launch (below 1: 1), with no f32 bound on a segment's steps
+//   PSTAT_MAX_SPINS=k       bound on the job queue's predecessor wait, if k > 0
+struct Overrides {
+  char f64_state = 0, f32_state = 0;   // first letter of the value (0: unset)
+  int pack = -1;                       // -1: unset
+  int lanes = 0, f64_lds_rows = -1;    // as atoi() reads them (0 / -1: unset)
+  int segments = 0, max_spins = 0;     // 0: unset
+};
+
+Overrides read_overrides() {
+  Overrides o;
+  if (const char *e = getenv("PSTAT_F64_STATE")) o.f64_state = e[0];
+  if (const char *e = getenv("PSTAT_F32_STATE")) o.f32_state = e[0];
+  if (const char *e = getenv("PSTAT_PACK")) o.pack = atoi(e) != 0 ? 1 : 0;
+  if (const char *e = getenv("PSTAT_LANES")) o.lanes = atoi(e);
+  if (const char *e = getenv("PSTAT_F64_LDS_ROWS")) o.f64_lds_rows = atoi(e);
+  if (const char *e = getenv("PSTAT_SEGMENTS")) o.segments = atoi(e) > 1 ? atoi(e) : 1;
+  if (const char *e = getenv("PSTAT_MAX_SPINS")) o.max_spins = atoi(e) > 0 ? atoi(e) : 0;
+  return o;
+}
+
 }  // namespace
 
 struct pstat_handle {
@@ -56,6 +86,7 @@ struct pstat_handle {
   hipStream_t stream = nullptr;
   bool own_stream = false;
   LaunchCfg cfg{};
+  Overrides ov;                     // test knobs, read at creation
   SweepArgs args{};
   DevState S{};
   std::vector<Buffer> bufs;         // every device allocation, in checkpoint order
@@ -73,8 +104,47 @@ namespace {
 
 // energies whose every step needs all n(n-1)/2 pairs: one chain per wavefront
 bool all_pairs(int energy_type) { return energy_type == PSTAT_INTERACTING || energy_type == PSTAT_CUTOFF; }
-// handles whose steps run one chain per wavefront (no chain blocks, no job queue)
-bool chain_per_wave(const pstat_handle *h) { return all_pairs(h->base.energy_type) || h->cfg.chain_wave != 0; }
+// homes that run one chain per lane in chain blocks from the job queue; the others run one chain per wavefront
+bool chain_per_lane(Home home) { return home == SweepLds || home == SweepMem || home == ClusterLds || home == ClusterMem; }
+
+// The kernel family that runs the steps of a handle of `ncases` x `chains_per_case` chains of n monomers.
+Home choose_home(const LaunchCfg &cfg, int64_t n, int64_t chains_per_case, int64_t ncases, const Overrides &ov) {
+  const bool cluster = cfg.move_set == PSTAT_MOVES_CLUSTER;
+  if (all_pairs(cfg.energy_type)) return cluster ? ClusterAllPairs : Interacting;
+  const int64_t total = chains_per_case * ncases;
+  // The chain-per-wavefront kernel covers the f64 / MWC64X clustering main up to n = 256.  It is chosen for (measured at
+  // n = 100 on the (E0, kT) grid of run/K1_E0-kT-phase.jl, tools/time_cluster_cw.py -> profiles/r04/experiments/time_cluster_cw.txt):
+  // one wave per chain costs the chip ~0.85 ns per chain-step whatever the clusters do (2 730 chains: 3.1 us per step, 43 680:
+  // 36 us).  The chain-per-lane kernel steps a whole ensemble in 4.5-5.5 us while its waves fit the chip once and every chain
+  // is disordered, but a wave runs at the pace of its longest cluster (25-33 us per step on an aligned chain) and a launch at
+  // the pace of its slowest wave: the same grids take it 29-45 us per step at 1 to 16 chains per case.  So: every ensemble of
+  // up to 4 096 chains, and sweeps of many small cases (<= 16 chains each) up to 49 152 chains; large ensembles of few cases
+  // keep the chain-per-lane kernels, whose full waves are 10 x cheaper per chain-step there.  (PSTAT_PACK: a test or
+  // experiment about the block layout is about the chain-per-lane kernels.)
+  if (cluster && cfg.precision == PSTAT_F64 && cfg.rng == PSTAT_RNG_MWC64X && n >= 1 && n <= 256) {
+    if (ov.f64_state == 'w') return ClusterChainWave;
+    if (ov.f64_state != 'l' && ov.f64_state != 'g' && ov.pack < 0 &&
+        (total <= 4096 || (ncases >= 8 && chains_per_case <= 16 && total <= (n <= 128 ? 49152 : 24576))))
+      return ClusterChainWave;
+  }
+  bool mem = false;   // the chain-per-lane kernel keeps its state in DevState::work instead of LDS
+  if (cluster && cfg.precision == PSTAT_F32) {
+    // The f32 clustering main has the in-memory kernel too (20-byte cells, pstat_cluster_gm.hip).  Its LDS kernel is the
+    // faster one while the ensemble is resident or nearly so (measured, 65 536 chains: n <= 80 2.2-2.5e10 proposals/s
+    // against 1.8-2.4e10; n = 100 a tie; the 546 x 64-chain n = 200 phase scan 1.88 s against 2.18 s); an ensemble of more
+    // than twice what LDS seats (160 KiB / 8 n chains per CU) runs in memory (n = 200, 65 536 chains: 1.5e10 against 7.7e9).
+    const int64_t seats = (160 * 1024 / (8 * (n > 0 ? n : 1))) * 256;
+    mem = ov.f32_state != 'l' && (ov.f32_state == 'g' || total > 2 * seats);
+  } else if (cfg.precision == PSTAT_F64) {
+    // f64 cells are 16 bytes: LDS seats 160 KiB / (16 n) chains per CU.  Once that is fewer than four full waves (n > 40)
+    // the non-interacting f64 sweep keeps its cells in global memory instead and runs 64 lanes on every SIMD (run_segment,
+    // ST = 2).  The clustering main's kernel in memory carries the trigonometric cache and is faster at every chain length
+    // (measured n = 10 / 20 / 40: 1.5e10 / 1.4e10 / 1.3e10 proposals/s against 1.0e10 with the cells in LDS).
+    mem = ov.f64_state != 'l' && (ov.f64_state == 'g' || cluster || n * 16 * 256 > 160 * 1024);
+  }
+  if (cluster) return mem ? ClusterMem : ClusterLds;
+  return mem ? SweepMem : SweepLds;
+}
 
 int alloc(pstat_handle *h, void **p, size_t bytes) {
   hipError_t e = hipMalloc(p, bytes);
@@ -154,10 +224,161 @@ int validate(const pstat_params *c, int ncases) {
   return PSTAT_OK;
 }
 
-// attributes of the chain-per-lane kernel that runs this handle's steps
+// attributes of the kernel that runs this configuration's steps (the chain-per-wavefront kernels leave *lds alone)
 hipError_t kernel_info(const LaunchCfg &cfg, const SweepArgs &a, int *lds, int *bpc, const char **name) {
-  return cfg.move_set == PSTAT_MOVES_CLUSTER ? cluster_kernel_info(cfg, a, lds, bpc, name)
-                                             : sweep_kernel_info(cfg, a, lds, bpc, name);
+  switch (cfg.home) {
+    case SweepLds: case SweepMem: return sweep_kernel_info(cfg, a, lds, bpc, name);
+    case ClusterLds: return cluster_kernel_info(cfg, a, lds, bpc, name);
+    case ClusterMem: return cluster_gm_kernel_info(cfg, a, lds, bpc, name);
+    case ClusterChainWave: return cluster_cw_kernel_info(cfg, a.n, bpc, name);
+    case ClusterAllPairs: return cluster_wave_kernel_info(cfg, a.n, bpc, name);
+    case Interacting: return interacting_kernel_info(cfg, a.n, bpc, name);
+  }
+  return hipErrorInvalidValue;
+}
+
+// ---- launch shape of the chain-per-lane kernels: active lanes per workgroup (one wave) and what a workgroup holds.
+// `shape` prices the best lane count (at most a.lanes) of one block layout with the makespan model of the home's kernel
+// family; packed blocks (run_job_queue<true>: a block holds `lanes` consecutive global chains, whichever cases they belong
+// to) are taken when they shorten the launch by more than 5 % -- an ensemble of 2 730 cases x 16 chains is 683 full
+// waves instead of 2 730 quarter-filled ones: measured 2.3 x (non-interacting) and 2.5 x (Ising) on the f64 sweep.
+// Otherwise blocks stay inside a case and its scalars in SGPRs.
+// The clustering main packs into waves no larger than a case's own chains would fill (16 lanes for cases of up to 16
+// chains) unless the unpacked launch is at least four rounds of the resident slots deep.  Its step time is not
+// uniform: a wave runs at the pace of its longest cluster, and across a phase grid that is 4.5 us per step for a
+// disordered chain against 25-33 us for an aligned one (n = 100, tools/phase_latency.py).  A sweep that mixes them is
+// paced by the sequential step time of its cold cases, not by throughput, and there a 64-lane wave of four cases is a
+// little slower than four 16-lane waves (run/K1_E0-kT-phase.jl's grid, 2 730 x 16 chains, 3e5 steps: 11.5 s unpacked,
+// 13.0 s packed four to a wave), while filling the idle lanes of a 16-lane wave with further cases is a gain throughout
+// (2 730 x 5 chains: 1 012 -> 865 ms per 2e4 steps on the whole grid, 747 -> 353 on its cold part; 5 760 x 1 chain:
+// 1.6-2.4 x); only when workgroups queue several deep does the throughput of full waves win (all-cold 2 730 x 16:
+// 676 -> 366 ms per 1e4 steps).  profiles/r04/experiments/time_packed*.txt, twin.txt.
+struct Shape { int lanes; int64_t nblocks; double cost; };
+
+Shape shape(LaunchCfg cfg, const SweepArgs &a, const bool packed, const bool deep, const int cus, const int force_lanes) {
+  cfg.packed = packed ? 1 : 0;
+  const int lanes = a.lanes;
+  const int64_t per_case = a.chains_per_case, total = per_case * a.ncases;
+  auto wgs_of = [&](const int cand) -> int64_t {
+    return packed ? (total + cand - 1) / cand : a.ncases * ((per_case + cand - 1) / cand);
+  };
+  Shape best{lanes, wgs_of(lanes), 1e300};
+  if (cfg.home == SweepMem) {   // f64 sweep with its cells in memory: 64 lanes on every SIMD
+    int lds0 = 0, bpc = 0;
+    if (kernel_info(cfg, a, &lds0, &bpc, nullptr) != hipSuccess || bpc < 1) bpc = 4;
+    double cost = (double)best.nblocks / ((double)bpc * cus);
+    best.cost = cost < 1.0 ? 1.0 : cost;
+    return best;
+  }
+  if (cfg.home == ClusterMem) {
+    // Chains in device memory: nothing limits a wave to fewer than 64 lanes, but an ensemble of fewer waves than the
+    // chip has SIMDs (a phase scan: 546 grid points x 64 chains) runs faster as more, emptier waves -- they fill the
+    // idle SIMDs, and a wave's step lasts as long as its LONGEST cluster, which grows like the logarithm of its lanes.
+    int lds0 = 0, bpc = 0;
+    if (kernel_info(cfg, a, &lds0, &bpc, nullptr) != hipSuccess || bpc < 1) bpc = 1;
+    const double slots = (double)bpc * cus;
+    // (packed, and the unpacked launch not many rounds deep: no wave larger than a case's chains rounded up to 16 / 32 / 64
+    // -- the clustering main's packing rule, above)
+    int cmax = 64;
+    if (packed && !deep) cmax = per_case <= 16 ? 16 : (per_case <= 32 ? 32 : 64);
+    for (int cand = cmax; cand >= 16; cand >>= 1) {
+      if (force_lanes >= 1 && force_lanes <= 64 && cand != force_lanes) continue;
+      double cost = (double)wgs_of(cand) / slots;
+      if (cost < 1.0) cost = 1.0;
+      cost *= 1.0 + 0.1 * std::log2(cand / 16.0);
+      if (cost < best.cost) best = Shape{cand, wgs_of(cand), cost};
+    }
+    return best;
+  }
+  // State in LDS: a CU holds at most 160 KiB / (bytes per chain) chains; pick the lane count that minimises the
+  // makespan max(1, workgroups / resident slots) of one launch -- e.g. f32, n = 100: 51 lanes x 4 workgroups per CU
+  // (204 chains, all four SIMDs) instead of 64 x 3 (192 chains, three SIMDs).
+  bool lds_starved = false;     // full waves: fewer than one per SIMD fit a CU's LDS
+  {
+    int lds0 = 0, bpc0 = 0;
+    lds_starved = kernel_info(cfg, a, &lds0, &bpc0, nullptr) == hipSuccess && bpc0 < 4;
+  }
+  for (int cand = lanes; cand >= 8; --cand) {
+    if (force_lanes >= 1 && force_lanes <= lanes && cand != force_lanes) continue;
+    SweepArgs probe = a;
+    probe.lanes = cand;
+    int lds = 0, bpc = 0;
+    if (kernel_info(cfg, probe, &lds, &bpc, nullptr) != hipSuccess || bpc < 1) continue;
+    const double slots = (double)bpc * cus;
+    double cost = (double)wgs_of(cand) / slots;
+    if (cost < 1.0) cost = 1.0;
+    cost *= 1.0 + 1e-4 * (64 - cand);   // ties: prefer fuller waves
+    if (cfg.home == ClusterLds && lds_starved) {
+      // (only when LDS seats fewer than four FULL waves per CU.)  The cluster step runs a wave for as long as its
+      // LONGEST cluster, so a wave of fewer lanes finishes its steps sooner (~ log of the lane count), and more,
+      // emptier waves also put the idle SIMDs to work.  Measured, n = 100, f64 (LDS seats 102 chains per CU): 4 x 25 lanes
+      // 4.08e9 proposals/s against 2 x 51 lanes 3.61e9 (non-interacting; Ising 5.70e9 / 5.57e9).  Sharing a SIMD
+      // between waves costs more than it gains here (f32: 4 x 51 lanes 1.77e10, 8 x 25 lanes 1.52e10).
+      const double waves_per_simd = bpc / 4.0;
+      cost *= 1.0 + 0.1 * std::log2(cand / 16.0);
+      if (waves_per_simd > 1.0) cost *= 1.0 + 0.25 * (waves_per_simd - 1.0);
+    }
+    if (cost < best.cost) best = Shape{cand, wgs_of(cand), cost};
+  }
+  return best;
+}
+
+// Splits a launch of `nsteps` steps into time segments so that blocks*segments fills the resident
+// workgroup slots evenly (see sweep_kernel).  Returns segments per block.
+int choose_segments(int64_t blocks, int64_t slots, int64_t nsteps, int64_t min_seg) {
+  if (blocks <= slots || nsteps < 2 * min_seg) return 1;
+  int best = 1;
+  double best_eff = 0;
+  for (int s = 1; s <= 12; ++s) {
+    if (nsteps / s < min_seg) break;              // keep fill/spill amortised
+    const double jobs = (double)blocks * s;
+    const double eff = jobs / (std::ceil(jobs / slots) * slots);   // busy fraction of the slots
+    if (eff > best_eff + 0.02) { best_eff = eff; best = s; }
+  }
+  return best;
+}
+
+// Launches the handle's step kernel for `nsteps` steps from step `step0` of the current init (nsteps = 0: the all-pairs
+// kernels derive r, p, U from fresh angles).  A chain-per-lane launch is split into time segments of its job queue.
+hipError_t launch_steps(pstat_handle *h, int64_t step0, int64_t nsteps) {
+  SweepArgs &A = h->args;
+  A.nsteps = nsteps;
+  A.step0 = step0;
+  unsigned grid = 0;
+  if (chain_per_lane(h->cfg.home)) {
+    const int64_t blocks = A.nblocks;
+    // (a fill + spill of the f64 cluster kernel's working buffer costs about ten of its steps, the LDS kernels' a few
+    // hundred of theirs)
+    int nseg = h->ov.segments ? h->ov.segments : choose_segments(blocks, h->slots, nsteps, h->cfg.home == ClusterMem ? 400 : 2000);
+    // f32/q16 running totals are re-derived from the angles at every segment start: bound the stretch
+    // over which their rounding errors can random-walk
+    if (h->base.precision != PSTAT_F64 && !h->ov.segments) {
+      const int64_t need = (nsteps + 32767) / 32768;
+      if (need > nseg) nseg = (int)(need < 0x3fffffffLL ? need : 0x3fffffffLL);
+    }
+    if (nseg > nsteps) nseg = nsteps > 1 ? (int)nsteps : 1;
+    if (blocks * nseg > 0x3fffffffLL) nseg = 1;
+    A.nseg = nseg;
+    A.seg_len = (nsteps + nseg - 1) / nseg;
+    // A job waits at most for one segment of its predecessor.  Bound the wait by a generous multiple of the
+    // longest plausible segment (a spin sleeps ~2 us; a step of the cluster kernel on a long, aligned chain
+    // can take tens of us), so that a long launch is never mistaken for a lost predecessor.
+    const int64_t want = (1ll << 22) + A.seg_len * 256;
+    A.max_spins = h->ov.max_spins ? h->ov.max_spins : (int32_t)(want < 0x7fffffffLL ? want : 0x7fffffffLL);
+    // Segments of one block run one after the other, so at most `blocks` jobs are runnable at any time:
+    // more workgroups than that would only sit in the predecessor wait -- and, worse, leave the working
+    // ones unevenly spread over the SIMDs.
+    grid = (unsigned)(blocks < h->slots ? blocks : h->slots);
+  }
+  switch (h->cfg.home) {
+    case SweepLds: case SweepMem: return launch_sweep(h->cfg, A, h->S, h->d_cases, h->d_queue, grid, h->stream);
+    case ClusterLds: return launch_cluster(h->cfg, A, h->S, h->d_cases, h->d_queue, grid, h->stream);
+    case ClusterMem: return launch_cluster_gm(h->cfg, A, h->S, h->d_cases, h->d_queue, grid, h->stream);
+    case ClusterChainWave: return launch_cluster_cw(h->cfg, A, h->S, h->d_cases, h->stream);
+    case ClusterAllPairs: return launch_cluster_wave(h->cfg, A, h->S, h->d_cases, h->stream);
+    case Interacting: return launch_interacting(h->cfg, A, h->S, h->d_cases, 0, h->stream);
+  }
+  return hipErrorInvalidValue;
 }
 
 int set_device(pstat_handle *h) {
@@ -270,14 +491,12 @@ int pstat_create(const pstat_params *cases, int32_t ncases, void *stream, pstat_
   }
   bool any_fx = false;
   for (auto &c : h->cases) any_fx = any_fx || c.Fx != 0.0;
+  h->ov = read_overrides();
   h->cfg = {h->base.precision, h->base.chain_type, h->base.energy_type, h->base.do_flips ? 1 : 0,
-            h->base.umbrella ? 1 : 0, any_fx ? 1 : 0, 0, h->base.rng, h->base.move_set, 0};
-  h->cfg.chain_wave = cluster_chain_wave(h->cfg, h->base.n, h->base.num_chains, ncases) ? 1 : 0;
-  h->cfg.state_global = (!h->cfg.chain_wave && f64_state_global(h->cfg, h->base.n, (int64_t)ncases * h->base.num_chains)) ? 1 : 0;
+            h->base.umbrella ? 1 : 0, any_fx ? 1 : 0, 0, h->base.rng, h->base.move_set};
+  const Home home = h->cfg.home = choose_home(h->cfg, h->base.n, h->base.num_chains, ncases, h->ov);
 
-  // one chain per wavefront: the all-pairs energies, and the clustering main's small f64 ensembles (pstat_cluster_cw.hip)
-  const bool inter = chain_per_wave(h);
-  int lanes = (inter || h->cfg.state_global) ? 64 : choose_lanes(h->base.precision, h->base.n, h->base.energy_type);
+  int lanes = (home == SweepLds || home == ClusterLds) ? choose_lanes(h->base.precision, h->base.n, h->base.energy_type) : 64;
   if (lanes == 0) {
     delete h;
     return fail(PSTAT_ERR_UNSUPPORTED, "num-monomers = %lld does not fit the 160 KiB LDS of a CU",
@@ -296,11 +515,9 @@ int pstat_create(const pstat_params *cases, int32_t ncases, void *stream, pstat_
   A.ncases = ncases; A.seg_len = 0; A.nseg = 1; A.max_spins = 1 << 22;
   A.lds_rows = 0; A.packed = 0; A.pad_ = 0;
   A.wide_eps = (h->base.precision == PSTAT_F64 && h->base.uniform_bits != 23) ? 1 : 0;
-  const bool cluster_gm = h->cfg.state_global && h->cfg.move_set == PSTAT_MOVES_CLUSTER;   // pstat_cluster_gm.hip
-  if (h->cfg.state_global && !cluster_gm) {   // a quarter of a CU's LDS per wave: four resident waves, 64 lanes x 16 B per row
+  if (home == SweepMem) {   // a quarter of a CU's LDS per wave: four resident waves, 64 lanes x 16 B per row
     int rows = 160 * 1024 / 4 / (64 * 16) - 1;   // one row of the quarter is the trash row of run_segment
-    const char *e = getenv("PSTAT_F64_LDS_ROWS");
-    if (e && atoi(e) >= 0 && atoi(e) <= rows) rows = atoi(e);
+    if (h->ov.f64_lds_rows >= 0 && h->ov.f64_lds_rows <= rows) rows = h->ov.f64_lds_rows;
     A.lds_rows = (int32_t)(h->base.n < rows ? h->base.n : rows);
   }
 
@@ -319,109 +536,22 @@ int pstat_create(const pstat_params *cases, int32_t ncases, void *stream, pstat_
   } while (0)
 
   CREATE_HIP(hipSetDevice(h->device));
-  if (!inter) {
-    // ---- launch shape of the chain-per-lane kernels: active lanes per workgroup (one wave) and what a workgroup holds.
-    // `shape(packed)` prices the best lane count of one block layout with the makespan model of its kernel family;
-    // packed blocks (run_job_queue<true>: a block holds `lanes` consecutive global chains, whichever cases they belong
-    // to) are taken when they shorten the launch by more than 5 % -- an ensemble of 2 730 cases x 16 chains is 683 full
-    // waves instead of 2 730 quarter-filled ones: measured 2.3 x (non-interacting) and 2.5 x (Ising) on the f64 sweep.
-    // Otherwise blocks stay inside a case and its scalars in SGPRs.
-    // The clustering main packs into waves no larger than a case's own chains would fill (16 lanes for cases of up to 16
-    // chains) unless the unpacked launch is at least four rounds of the resident slots deep.  Its step time is not
-    // uniform: a wave runs at the pace of its longest cluster, and across a phase grid that is 4.5 us per step for a
-    // disordered chain against 25-33 us for an aligned one (n = 100, tools/phase_latency.py).  A sweep that mixes them is
-    // paced by the sequential step time of its cold cases, not by throughput, and there a 64-lane wave of four cases is a
-    // little slower than four 16-lane waves (run/K1_E0-kT-phase.jl's grid, 2 730 x 16 chains, 3e5 steps: 11.5 s unpacked,
-    // 13.0 s packed four to a wave), while filling the idle lanes of a 16-lane wave with further cases is a gain throughout
-    // (2 730 x 5 chains: 1 012 -> 865 ms per 2e4 steps on the whole grid, 747 -> 353 on its cold part; 5 760 x 1 chain:
-    // 1.6-2.4 x); only when workgroups queue several deep does the throughput of full waves win (all-cold 2 730 x 16:
-    // 676 -> 366 ms per 1e4 steps).  profiles/r04/experiments/time_packed*.txt, twin.txt.
-    hipDeviceProp_t prop;
+  hipDeviceProp_t prop;
+  if (chain_per_lane(home)) {
     CREATE_HIP(hipGetDeviceProperties(&prop, h->device));
-    const int64_t per_case = h->base.num_chains, total = per_case * ncases;
-    const char *le = getenv("PSTAT_LANES");
-    struct Shape { int lanes; int64_t nblocks; double cost; };
-    auto shape = [&](const bool packed, const bool deep) -> Shape {
-      LaunchCfg cfg = h->cfg;
-      cfg.packed = packed ? 1 : 0;
-      auto wgs_of = [&](const int cand) -> int64_t {
-        return packed ? (total + cand - 1) / cand : (int64_t)ncases * ((per_case + cand - 1) / cand);
-      };
-      Shape best{lanes, wgs_of(lanes), 1e300};
-      if (h->cfg.state_global && !cluster_gm) {   // f64 sweep with its cells in memory: 64 lanes on every SIMD
-        int lds0 = 0, bpc = 0;
-        if (kernel_info(cfg, h->args, &lds0, &bpc, nullptr) != hipSuccess || bpc < 1) bpc = 4;
-        double cost = (double)best.nblocks / ((double)bpc * prop.multiProcessorCount);
-        best.cost = cost < 1.0 ? 1.0 : cost;
-        return best;
-      }
-      if (cluster_gm) {
-        // Chains in device memory: nothing limits a wave to fewer than 64 lanes, but an ensemble of fewer waves than the
-        // chip has SIMDs (a phase scan: 546 grid points x 64 chains) runs faster as more, emptier waves -- they fill the
-        // idle SIMDs, and a wave's step lasts as long as its LONGEST cluster, which grows like the logarithm of its lanes.
-        int lds0 = 0, bpc = 0;
-        if (kernel_info(cfg, h->args, &lds0, &bpc, nullptr) != hipSuccess || bpc < 1) bpc = 1;
-        const double slots = (double)bpc * prop.multiProcessorCount;
-        // (packed, and the unpacked launch not many rounds deep: no wave larger than a case's chains rounded up to 16 / 32 / 64
-        // -- the clustering main's packing rule, above)
-        int cmax = 64;
-        if (packed && !deep) cmax = per_case <= 16 ? 16 : (per_case <= 32 ? 32 : 64);
-        for (int cand = cmax; cand >= 16; cand >>= 1) {
-          if (le && atoi(le) >= 1 && atoi(le) <= 64 && cand != atoi(le)) continue;
-          double cost = (double)wgs_of(cand) / slots;
-          if (cost < 1.0) cost = 1.0;
-          cost *= 1.0 + 0.1 * std::log2(cand / 16.0);
-          if (cost < best.cost) best = Shape{cand, wgs_of(cand), cost};
-        }
-        return best;
-      }
-      // State in LDS: a CU holds at most 160 KiB / (bytes per chain) chains; pick the lane count that minimises the
-      // makespan max(1, workgroups / resident slots) of one launch -- e.g. f32, n = 100: 51 lanes x 4 workgroups per CU
-      // (204 chains, all four SIMDs) instead of 64 x 3 (192 chains, three SIMDs).
-      bool lds_starved = false;     // full waves: fewer than one per SIMD fit a CU's LDS
-      {
-        int lds0 = 0, bpc0 = 0;
-        lds_starved = kernel_info(cfg, h->args, &lds0, &bpc0, nullptr) == hipSuccess && bpc0 < 4;
-      }
-      for (int cand = lanes; cand >= 8; --cand) {
-        if (le && atoi(le) >= 1 && atoi(le) <= lanes && cand != atoi(le)) continue;
-        SweepArgs probe = h->args;
-        probe.lanes = cand;
-        int lds = 0, bpc = 0;
-        if (kernel_info(cfg, probe, &lds, &bpc, nullptr) != hipSuccess || bpc < 1) continue;
-        const double slots = (double)bpc * prop.multiProcessorCount;
-        double cost = (double)wgs_of(cand) / slots;
-        if (cost < 1.0) cost = 1.0;
-        cost *= 1.0 + 1e-4 * (64 - cand);   // ties: prefer fuller waves
-        if (h->cfg.move_set == PSTAT_MOVES_CLUSTER && lds_starved) {
-          // (only when LDS seats fewer than four FULL waves per CU.)  The cluster step runs a wave for as long as its
-          // LONGEST cluster, so a wave of fewer lanes finishes its steps sooner (~ log of the lane count), and more,
-          // emptier waves also put the idle SIMDs to work.  Measured, n = 100, f64 (LDS seats 102 chains per CU): 4 x 25 lanes
-          // 4.08e9 proposals/s against 2 x 51 lanes 3.61e9 (non-interacting; Ising 5.70e9 / 5.57e9).  Sharing a SIMD
-          // between waves costs more than it gains here (f32: 4 x 51 lanes 1.77e10, 8 x 25 lanes 1.52e10).
-          const double waves_per_simd = bpc / 4.0;
-          cost *= 1.0 + 0.1 * std::log2(cand / 16.0);
-          if (waves_per_simd > 1.0) cost *= 1.0 + 0.25 * (waves_per_simd - 1.0);
-        }
-        if (cost < best.cost) best = Shape{cand, wgs_of(cand), cost};
-      }
-      return best;
-    };
-    Shape pick = shape(false, false);
-    if (ncases > 1 && supports_packed_cases(h->cfg)) {
-      const char *pe = getenv("PSTAT_PACK");     // 0 | 1: tests and experiments
-      const Shape pk = shape(true, pick.cost >= 4.0 || (pe && atoi(pe) != 0));
-      if (pe ? atoi(pe) != 0 : pk.cost < 0.95 * pick.cost) {
+    Shape pick = shape(h->cfg, A, false, false, prop.multiProcessorCount, h->ov.lanes);
+    if (ncases > 1) {   // (every chain-per-lane kernel has a packed-cases instantiation)
+      const Shape pk = shape(h->cfg, A, true, pick.cost >= 4.0 || h->ov.pack == 1, prop.multiProcessorCount, h->ov.lanes);
+      if (h->ov.pack >= 0 ? h->ov.pack == 1 : pk.cost < 0.95 * pick.cost) {
         pick = pk;
         h->cfg.packed = 1;
         A.packed = 1;
       }
     }
-    lanes = pick.lanes;
-    A.lanes = lanes;
-    A.blocks_per_case = (per_case + lanes - 1) / lanes;
+    A.lanes = pick.lanes;
+    A.blocks_per_case = (h->base.num_chains + pick.lanes - 1) / pick.lanes;
     A.nblocks = pick.nblocks;
-    if (cluster_gm && (uint64_t)lanes * (uint64_t)h->base.n * (h->base.precision == PSTAT_F64 ? PSTAT_CLUSTER_GM_CELL : 20u) >= 0x80000000ull) {
+    if (home == ClusterMem && (uint64_t)pick.lanes * (uint64_t)h->base.n * (h->base.precision == PSTAT_F64 ? PSTAT_CLUSTER_GM_CELL : 20u) >= 0x80000000ull) {
       pstat_destroy(h);
       return fail(PSTAT_ERR_UNSUPPORTED, "num-monomers = %lld: a wave's working buffer must stay below 2 GiB",
                   (long long)cases[0].n);
@@ -456,9 +586,9 @@ int pstat_create(const pstat_params *cases, int32_t ncases, void *stream, pstat_
   CREATE_TRY(alloc(h, (void **)&S.nanrej, Cz * sizeof(int64_t)));
   const size_t nstate = h->bufs.size();
   CREATE_TRY(alloc(h, &S.ang_tmp, 2 * n * Cz * h->elem));
-  if (cluster_gm)            // working copy of the chains, [chain block][lane][n] cells of 40 (f64) / 20 (f32) bytes (pstat_cluster_gm.hip)
+  if (home == ClusterMem)    // working copy of the chains, [chain block][lane][n] cells of 40 (f64) / 20 (f32) bytes (pstat_cluster_gm.hip)
     CREATE_TRY(alloc(h, &S.work, cluster_gm_work_bytes(h->cfg, A)));
-  else if (h->cfg.state_global)   // working copy of the cells, [chain block][n][64] double2 (run_segment, ST = 2)
+  else if (home == SweepMem)   // working copy of the cells, [chain block][n][64] double2 (run_segment, ST = 2)
     CREATE_TRY(alloc(h, &S.work, (size_t)A.nblocks * n * 64 * 16));
   CREATE_TRY(alloc(h, (void **)&h->d_cases, sizeof(CaseConst) * (size_t)ncases));
   CREATE_TRY(alloc(h, (void **)&h->d_queue, sizeof(int) * sweep_queue_ints(h->args)));
@@ -470,19 +600,12 @@ int pstat_create(const pstat_params *cases, int32_t ncases, void *stream, pstat_
                             hipMemcpyHostToDevice, h->stream));
   const InitOpts io{h->base.use_x0, h->base.x0_phi, h->base.x0_theta, h->base.dx0_phi, h->base.dx0_theta, nullptr};
   CREATE_HIP(launch_init(h->cfg, h->args, h->S, h->d_cases, h->base.phi_step, h->base.theta_step, io, h->stream));
-  if (all_pairs(h->base.energy_type)) {  // a zero-step launch derives r, p, U (with the pair energy) from the fresh angles
-    h->args.nsteps = 0; h->args.step0 = 0;
-    if (h->cfg.move_set == PSTAT_MOVES_CLUSTER)
-      CREATE_HIP(launch_cluster_wave(h->cfg, h->args, h->S, h->d_cases, h->stream));
-    else
-      CREATE_HIP(launch_interacting(h->cfg, h->args, h->S, h->d_cases, 0, h->stream));
-  }
+  if (all_pairs(h->base.energy_type))  // a zero-step launch derives r, p, U (with the pair energy) from the fresh angles
+    CREATE_HIP(launch_steps(h, 0, 0));
   CREATE_HIP(hipStreamSynchronize(h->stream));  // h->cases must outlive the copy; also surfaces faults here
-  if (!inter) {
+  if (chain_per_lane(home)) {
     int lds = 0, bpc = 0;
-    hipDeviceProp_t prop;
     CREATE_HIP(kernel_info(h->cfg, h->args, &lds, &bpc, nullptr));
-    CREATE_HIP(hipGetDeviceProperties(&prop, h->device));
     h->slots = (bpc > 0 ? bpc : 1) * prop.multiProcessorCount;
   }
 #undef CREATE_TRY
@@ -504,21 +627,6 @@ void pstat_destroy(pstat_handle *h) {
   delete h;
 }
 
-// Splits a launch of `nsteps` steps into time segments so that blocks*segments fills the resident
-// workgroup slots evenly (see sweep_kernel).  Returns segments per block.
-static int choose_segments(int64_t blocks, int64_t slots, int64_t nsteps, int64_t min_seg) {
-  if (blocks <= slots || nsteps < 2 * min_seg) return 1;
-  int best = 1;
-  double best_eff = 0;
-  for (int s = 1; s <= 12; ++s) {
-    if (nsteps / s < min_seg) break;              // keep fill/spill amortised
-    const double jobs = (double)blocks * s;
-    const double eff = jobs / (std::ceil(jobs / slots) * slots);   // busy fraction of the slots
-    if (eff > best_eff + 0.02) { best_eff = eff; best = s; }
-  }
-  return best;
-}
-
 int pstat_advance(pstat_handle *h, int64_t nsteps) {
   if (!h) return fail(PSTAT_ERR_INVALID_ARG, "null handle");
   if (nsteps < 0) return fail(PSTAT_ERR_INVALID_ARG, "nsteps must be >= 0");
@@ -527,61 +635,9 @@ int pstat_advance(pstat_handle *h, int64_t nsteps) {
   if (rc) return rc;
   if (h->failed_job) return report_failed_job(h);
   const int64_t max_launch = 1ll << 30;  // per-launch step counters are 32-bit
-  if (chain_per_wave(h)) {
-    while (nsteps > 0) {
-      const int64_t len = nsteps < max_launch ? nsteps : max_launch;
-      h->args.nsteps = len;
-      h->args.step0 = h->step_in_init;
-      if (h->cfg.chain_wave)
-        HIP_TRY(launch_cluster_cw(h->cfg, h->args, h->S, h->d_cases, h->stream));
-      else if (h->cfg.move_set == PSTAT_MOVES_CLUSTER)
-        HIP_TRY(launch_cluster_wave(h->cfg, h->args, h->S, h->d_cases, h->stream));
-      else
-        HIP_TRY(launch_interacting(h->cfg, h->args, h->S, h->d_cases, 0, h->stream));
-      h->step_in_init += len;
-      h->steps_recorded += len;
-      nsteps -= len;
-    }
-    return PSTAT_OK;
-  }
-  const int64_t blocks = h->args.nblocks;
-  const char *env = getenv("PSTAT_SEGMENTS");
-  const char *ms = getenv("PSTAT_MAX_SPINS");
   while (nsteps > 0) {
     const int64_t len = nsteps < max_launch ? nsteps : max_launch;
-    // (a fill + spill of the f64 cluster kernel's working buffer costs about ten of its steps, the LDS kernels' a few
-    // hundred of theirs)
-    const bool cluster_gm = h->cfg.state_global && h->cfg.move_set == PSTAT_MOVES_CLUSTER;
-    int nseg = env ? atoi(env) : choose_segments(blocks, h->slots, len, cluster_gm ? 400 : 2000);
-    if (nseg < 1) nseg = 1;
-    // f32/q16 running totals are re-derived from the angles at every segment start: bound the stretch
-    // over which their rounding errors can random-walk
-    if (h->base.precision != PSTAT_F64 && !env) {
-      const int64_t need = (len + 32767) / 32768;
-      if (need > nseg) nseg = (int)(need < 0x3fffffffLL ? need : 0x3fffffffLL);
-    }
-    if (nseg > len) nseg = (int)len;
-    if (blocks * nseg > 0x3fffffffLL) nseg = 1;
-    h->args.nsteps = len;
-    h->args.step0 = h->step_in_init;
-    h->args.nseg = nseg;
-    h->args.seg_len = (len + nseg - 1) / nseg;
-    // A job waits at most for one segment of its predecessor.  Bound the wait by a generous multiple of the
-    // longest plausible segment (a spin sleeps ~2 us; a step of the cluster kernel on a long, aligned chain
-    // can take tens of us), so that a long launch is never mistaken for a lost predecessor.
-    {
-      const int64_t want = (1ll << 22) + h->args.seg_len * 256;
-      h->args.max_spins = (int32_t)(want < 0x7fffffffLL ? want : 0x7fffffffLL);
-      if (ms && atoi(ms) > 0) h->args.max_spins = atoi(ms);
-    }
-    // Segments of one block run one after the other, so at most `blocks` jobs are runnable at any time:
-    // more workgroups than that would only sit in the predecessor wait -- and, worse, leave the working
-    // ones unevenly spread over the SIMDs.
-    const unsigned grid = (unsigned)(blocks < h->slots ? blocks : h->slots);
-    if (h->cfg.move_set == PSTAT_MOVES_CLUSTER)
-      HIP_TRY(launch_cluster(h->cfg, h->args, h->S, h->d_cases, h->d_queue, grid, h->stream));
-    else
-      HIP_TRY(launch_sweep(h->cfg, h->args, h->S, h->d_cases, h->d_queue, grid, h->stream));
+    HIP_TRY(launch_steps(h, h->step_in_init, len));
     h->step_in_init += len;
     h->steps_recorded += len;
     nsteps -= len;
@@ -602,7 +658,7 @@ int pstat_reinit(pstat_handle *h, int32_t force_init) {
     return fail(PSTAT_ERR_UNSUPPORTED, "mcmc_clustering_eap_chain.jl has no --num-inits: nothing to re-initialise");
   int rc = set_device(h);
   if (rc) return rc;
-  if (h->base.energy_type == PSTAT_INTERACTING) {   // done inside the one-chain-per-wave kernel
+  if (h->cfg.home == Interacting) {   // done inside the one-chain-per-wave kernel
     h->args.nsteps = 0; h->args.step0 = 0;
     HIP_TRY(launch_interacting(h->cfg, h->args, h->S, h->d_cases, force_init ? 2 : 1, h->stream));
     h->step_in_init = 0;
@@ -671,11 +727,7 @@ int pstat_restart_from_x0(pstat_handle *h, const double *x0, int64_t len, double
     io.x0_vec = d_x0;
   }
   hipError_t e = launch_init(h->cfg, h->args, h->S, h->d_cases, h->base.phi_step, h->base.theta_step, io, h->stream);
-  if (e == hipSuccess && all_pairs(h->base.energy_type)) {
-    h->args.nsteps = 0; h->args.step0 = 0;
-    e = h->cfg.move_set == PSTAT_MOVES_CLUSTER ? launch_cluster_wave(h->cfg, h->args, h->S, h->d_cases, h->stream)
-                                               : launch_interacting(h->cfg, h->args, h->S, h->d_cases, 0, h->stream);
-  }
+  if (e == hipSuccess && all_pairs(h->base.energy_type)) e = launch_steps(h, 0, 0);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
   if (d_x0) (void)hipFree(d_x0);
   if (e != hipSuccess) return fail(PSTAT_ERR_HIP, "re-initialisation from x0 failed: %s", hipGetErrorString(e));
@@ -1019,16 +1071,12 @@ int pstat_launch_info_get(pstat_handle *h, pstat_launch_info *out) {
   std::memset(out, 0, sizeof *out);
   int lds = 0, bpc = 0;
   const char *name = "";
-  if (chain_per_wave(h)) {
-    if (h->cfg.chain_wave) HIP_TRY(cluster_cw_kernel_info(h->cfg, h->base.n, &bpc, &name));
-    else if (h->cfg.move_set == PSTAT_MOVES_CLUSTER) HIP_TRY(cluster_wave_kernel_info(h->cfg, h->base.n, &bpc, &name));
-    else HIP_TRY(interacting_kernel_info(h->cfg, h->base.n, &bpc, &name));
-  } else HIP_TRY(kernel_info(h->cfg, h->args, &lds, &bpc, &name));
+  HIP_TRY(kernel_info(h->cfg, h->args, &lds, &bpc, &name));
   std::snprintf(out->kernel, sizeof out->kernel, "%s", name);
   out->lds_bytes = lds;
   out->threads_per_block = 64;
   out->lanes_per_block = h->args.lanes;
-  out->blocks = chain_per_wave(h) ? h->S.C : h->args.nblocks;
+  out->blocks = chain_per_lane(h->cfg.home) ? h->args.nblocks : h->S.C;
   out->packed_cases = h->args.packed;
   out->blocks_per_cu = bpc;
   hipDeviceProp_t prop;

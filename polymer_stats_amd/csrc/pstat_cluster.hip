@@ -573,7 +573,6 @@ static int cluster_lds_bytes(const LaunchCfg &cfg, const SweepArgs &a) {
 
 hipError_t cluster_kernel_info(const LaunchCfg &cfg, const SweepArgs &a, int *lds_bytes, int *blocks_per_cu,
                                const char **name) {
-  if (cfg.state_global) return cluster_gm_kernel_info(cfg, a, lds_bytes, blocks_per_cu, name);   // pstat_cluster_gm.hip
   ClusterFn fn = pick_cluster(cfg);
   const int lds = cluster_lds_bytes(cfg, a);
   hipError_t e = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -591,7 +590,6 @@ hipError_t cluster_kernel_info(const LaunchCfg &cfg, const SweepArgs &a, int *ld
 
 hipError_t launch_cluster(const LaunchCfg &cfg, const SweepArgs &a, const DevState &s, const CaseConst *cases,
                           int *queue, unsigned grid, hipStream_t stream) {
-  if (cfg.state_global) return launch_cluster_gm(cfg, a, s, cases, queue, grid, stream);
   ClusterFn fn = pick_cluster(cfg);
   const int lds = cluster_lds_bytes(cfg, a);
   hipError_t e = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);

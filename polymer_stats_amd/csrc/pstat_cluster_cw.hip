@@ -36,11 +36,10 @@
 //     the first version, before any of this, 45; tools/ab_cw_waves.sh -> profiles/r04/experiments/ab_cw_waves.txt).
 // Results: the same trajectories as the oracle and the chain-per-lane kernels bit for bit (angles, generator state, acceptance
 // counts, step sizes; tests/fuzz_cluster_wave.py); running sums differ in their last bits (order of the member sums), like
-// every kernel pair here.  Chosen by cluster_chain_wave() below (PSTAT_F64_STATE=wave|lds|global overrides, for tests and
-// experiments); xoshiro128++ has no cheap skip-ahead and keeps the chain-per-lane kernels.
+// every kernel pair here.  Home ClusterChainWave, chosen by choose_home() (pstat_api.hip; PSTAT_F64_STATE=wave|lds|global overrides,
+// for tests and experiments); xoshiro128++ has no cheap skip-ahead and keeps the chain-per-lane kernels.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
 #include <type_traits>
 
 #define PSTAT_THETA_GENERIC_TAIL 1   // (one sincos form for all three angles of the step: they share an instruction stream)
@@ -724,27 +723,6 @@ CwFn pick(const LaunchCfg &cfg, const int64_t n) {
 }
 
 }  // namespace
-
-// The configurations this kernel covers, and the ensembles it is chosen for (measured at n = 100 on the (E0, kT) grid of
-// run/K1_E0-kT-phase.jl, tools/time_cluster_cw.py -> profiles/r04/experiments/time_cluster_cw.txt).  One wave per chain costs the
-// chip ~0.85 ns per chain-step whatever the clusters do (2 730 chains: 3.1 us per step, 43 680: 36 us).  The chain-per-lane
-// kernel steps a whole ensemble in 4.5-5.5 us while its waves fit the chip once and every chain is disordered, but a wave runs at
-// the pace of its longest cluster (25-33 us per step on an aligned chain) and a launch at the pace of its slowest wave: the
-// same grids take it 29-45 us per step at 1 to 16 chains per case.  So: every ensemble of up to 4 096 chains, and sweeps of
-// many small cases (<= 16 chains each) up to 49 152 chains; large ensembles of few cases keep the chain-per-lane kernels,
-// whose full waves are 10 x cheaper per chain-step there.
-bool cluster_chain_wave(const LaunchCfg &cfg, const int64_t n, const int64_t chains_per_case, const int64_t ncases) {
-  if (cfg.move_set != PSTAT_MOVES_CLUSTER || cfg.precision != PSTAT_F64 || cfg.rng != PSTAT_RNG_MWC64X) return false;
-  if (cfg.energy_type != PSTAT_NONINTERACTING && cfg.energy_type != PSTAT_ISING) return false;
-  if (n < 1 || n > 256) return false;
-  const char *e = getenv("PSTAT_F64_STATE");
-  if (e && e[0] == 'w') return true;
-  if (e && (e[0] == 'l' || e[0] == 'g')) return false;
-  if (getenv("PSTAT_PACK")) return false;     // (a test or experiment about the block layout is about the chain-per-lane kernels)
-  const int64_t total = chains_per_case * ncases;
-  if (total <= 4096) return true;
-  return ncases >= 8 && chains_per_case <= 16 && total <= (n <= 128 ? 49152 : 24576);
-}
 
 hipError_t cluster_cw_kernel_info(const LaunchCfg &cfg, const int64_t n, int *blocks_per_cu, const char **name) {
   int nb = 0;

@@ -1,5 +1,5 @@
 // pstat_cluster_gm.hip -- the step of mcmc_clustering_eap_chain.jl:268-311 with the chain state in DEVICE MEMORY: the f64 kernel
-// of that main (every chain length), and its f32 sibling for ensembles LDS cannot seat (f64_state_global(), pstat_kernels.hip).
+// of that main (every chain length), and its f32 sibling for ensembles LDS cannot seat (home ClusterMem, choose_home() in pstat_api.hip).
 //
 // Same step, stream contract and results as cluster_kernel<R> of pstat_cluster.hip (one chain per lane, the
 // persistent (block, segment) job queue); what differs is where a chain lives while a segment runs and what a cell holds.

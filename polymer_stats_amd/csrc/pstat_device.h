@@ -37,7 +37,7 @@ struct DevState {
   double *uref;         // f64[C]         sum(u) of the chain's first configuration: the umbrella weights
                         //                are taken relative to it (a per-chain constant factor cancels
                         //                in value/normalizer, inc/average.jl:38,63-67)
-  void *work;           // f64 "state in memory" kernels only: the waves' working copy of their chains while a segment
+  void *work;           // homes SweepMem and ClusterMem only: the waves' working copy of their chains while a segment
                         //                runs (filled from / spilled to `ang` like LDS is); not checkpointed.  Sweep:
                         //                [chain block][n][64] double2 (theta, phi), chain-contiguous for the Ising energy.
                         //                Clustering main: [chain block][lane][n] 40-byte (f32: 20-byte) cells (pstat_cluster_gm.hip)
@@ -267,18 +267,27 @@ __device__ __forceinline__ void run_job_queue(const SweepArgs &A, int *__restric
 }
 #endif  // __HIPCC__
 
+// The kernel family that runs a handle's steps, chosen once by choose_home() (pstat_api.hip).  The first four run one chain
+// per lane in chain blocks from the job queue (run_job_queue), the others one chain per wavefront.
+enum Home {
+  SweepLds,          // fixed-force main, cells in LDS (pstat_kernels.hip)
+  SweepMem,          // fixed-force main, f64, cells in the global working buffer DevState::work (run_segment, ST = 2)
+  ClusterLds,        // clustering main, cells in LDS (pstat_cluster.hip)
+  ClusterMem,        // clustering main, chains in DevState::work (pstat_cluster_gm.hip: f64, and f32 for large ensembles)
+  ClusterChainWave,  // clustering main, small f64 ensembles: one chain per wavefront (pstat_cluster_cw.hip)
+  ClusterAllPairs,   // clustering main with the all-pairs energies (pstat_cluster_wave.hip)
+  Interacting,       // fixed-force main with the all-pairs energy (pstat_interacting.hip)
+};
+
 // host-callable launchers implemented in pstat_kernels.hip; all asynchronous on `stream`
 struct LaunchCfg {
   int precision, chain_type, energy_type, do_flips, umbrella, has_fx;
   int lag;  // a re-init has happened on this handle
   int rng;  // PSTAT_RNG_MWC64X | PSTAT_RNG_XOSHIRO128PP
   int move_set;  // PSTAT_MOVES_SINGLE (mcmc_eap_chain.jl) | PSTAT_MOVES_CLUSTER (mcmc_clustering_eap_chain.jl)
-  int state_global;  // f64 chain-per-lane kernels: state cells in the global working buffer (DevState::work) instead of LDS
-  int packed;        // chain blocks straddle cases (SweepArgs::packed): the kernel instantiation with per-lane case scalars
-  int chain_wave;    // clustering main, small f64 ensembles: one chain per wavefront (pstat_cluster_cw.hip, cluster_chain_wave())
+  Home home;     // the kernel family
+  int packed;    // chain blocks straddle cases (SweepArgs::packed): the kernel instantiation with per-lane case scalars
 };
-// the kernel of this configuration has a packed-cases instantiation (every chain-per-lane kernel; not the all-pairs ones)
-bool supports_packed_cases(const LaunchCfg &cfg);
 hipError_t launch_init(const LaunchCfg &cfg, const SweepArgs &a, const DevState &s,
                        const CaseConst *cases, double phi_step, double theta_step,
                        const InitOpts &io, hipStream_t stream);
@@ -288,7 +297,7 @@ hipError_t launch_cluster(const LaunchCfg &cfg, const SweepArgs &a, const DevSta
                           const CaseConst *cases, int *queue, unsigned grid, hipStream_t stream);
 hipError_t cluster_kernel_info(const LaunchCfg &cfg, const SweepArgs &a, int *lds_bytes,
                                int *blocks_per_cu, const char **name);
-// the cluster kernel with its chains in DevState::work (pstat_cluster_gm.hip: f64, and f32 for large ensembles); chosen by f64_state_global()
+// the cluster kernel with its chains in DevState::work (home ClusterMem)
 hipError_t launch_cluster_gm(const LaunchCfg &cfg, const SweepArgs &a, const DevState &s,
                              const CaseConst *cases, int *queue, unsigned grid, hipStream_t stream);
 hipError_t cluster_gm_kernel_info(const LaunchCfg &cfg, const SweepArgs &a, int *lds_bytes,
@@ -310,7 +319,6 @@ size_t reduce_scratch_doubles();
 hipError_t sweep_kernel_info(const LaunchCfg &cfg, const SweepArgs &a, int *lds_bytes,
                              int *blocks_per_cu, const char **name);
 int choose_lanes(int precision, int64_t n, int energy_type);
-bool f64_state_global(const LaunchCfg &cfg, int64_t n, int64_t total_chains);   // the f64 chain-per-lane kernel of this configuration keeps its state in DevState::work
 // --energy-type interacting: one chain per wavefront (pstat_interacting.hip), n <= 512
 hipError_t launch_interacting(const LaunchCfg &cfg, const SweepArgs &a, const DevState &s,
                               const CaseConst *cases, int reinit_mode, hipStream_t stream);
@@ -319,7 +327,6 @@ hipError_t launch_cluster_wave(const LaunchCfg &cfg, const SweepArgs &a, const D
                                hipStream_t stream);
 hipError_t cluster_wave_kernel_info(const LaunchCfg &cfg, int64_t n, int *blocks_per_cu, const char **name);
 // clustering main, non-interacting / Ising, f64, small ensembles: one chain per wavefront (pstat_cluster_cw.hip)
-bool cluster_chain_wave(const LaunchCfg &cfg, int64_t n, int64_t chains_per_case, int64_t ncases);
 hipError_t launch_cluster_cw(const LaunchCfg &cfg, const SweepArgs &a, const DevState &s, const CaseConst *cases,
                              hipStream_t stream);
 hipError_t cluster_cw_kernel_info(const LaunchCfg &cfg, int64_t n, int *blocks_per_cu, const char **name);

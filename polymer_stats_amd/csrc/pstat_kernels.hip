@@ -1110,40 +1110,7 @@ SweepFn pick_sweep_q16(const LaunchCfg &cfg);
 SweepFn pick_sweep_f64(const LaunchCfg &cfg);
 SweepFn pick_sweep_f64g(const LaunchCfg &cfg);
 
-// f64 cells are 16 bytes: LDS seats 160 KiB / (16 n) chains per CU.  Once that is fewer than four full waves
-// (n > 40) the non-interacting f64 sweep keeps its cells in global memory instead and runs 64 lanes on every
-// SIMD (run_segment, ST = 2).  PSTAT_F64_STATE=lds|global overrides the choice (experiments, tests).
-// The clustering main's chain-per-lane kernel always keeps its chains in memory (pstat_cluster_gm.hip).
-bool f64_state_global(const LaunchCfg &cfg, int64_t n, int64_t total_chains) {
-  if (cfg.energy_type != PSTAT_NONINTERACTING && cfg.energy_type != PSTAT_ISING) return false;
-  if (cfg.precision == PSTAT_F32 && cfg.move_set == PSTAT_MOVES_CLUSTER) {
-    // The f32 clustering main has the in-memory kernel too (20-byte cells, pstat_cluster_gm.hip).  Its LDS kernel is the
-    // faster one while the ensemble is resident or nearly so (measured, 65 536 chains: n <= 80 2.2-2.5e10 proposals/s
-    // against 1.8-2.4e10; n = 100 a tie; the 546 x 64-chain n = 200 phase scan 1.88 s against 2.18 s); an ensemble of more
-    // than twice what LDS seats (160 KiB / 8 n chains per CU) runs in memory (n = 200, 65 536 chains: 1.5e10 against 7.7e9).
-    // PSTAT_F32_STATE=lds|global overrides (tests).
-    const char *e = getenv("PSTAT_F32_STATE");
-    if (e && e[0] == 'l') return false;
-    if (e && e[0] == 'g') return true;
-    const int64_t seats = (160 * 1024 / (8 * (n > 0 ? n : 1))) * 256;
-    return total_chains > 2 * seats;
-  }
-  if (cfg.precision != PSTAT_F64) return false;
-  const char *e = getenv("PSTAT_F64_STATE");
-  if (e && e[0] == 'l') return false;
-  if (e && e[0] == 'g') return true;
-  // the clustering main's kernel in memory carries the trigonometric cache and is faster at every chain length
-  // (measured n = 10 / 20 / 40: 1.5e10 / 1.4e10 / 1.3e10 proposals/s against 1.0e10 with the cells in LDS)
-  if (cfg.move_set == PSTAT_MOVES_CLUSTER) return true;
-  return n * 16 * 256 > 160 * 1024;
-}
-
 static int cell_bytes(int precision) { return precision == PSTAT_F64 ? 16 : (precision == PSTAT_Q16 ? 4 : 8); }
-
-bool supports_packed_cases(const LaunchCfg &cfg) {
-  // every chain-per-lane kernel has a packed instantiation; the all-pairs energies run a chain per wavefront: nothing to pack
-  return cfg.energy_type == PSTAT_NONINTERACTING || cfg.energy_type == PSTAT_ISING;
-}
 
 int choose_lanes(int precision, int64_t n, int energy_type) {
   (void)energy_type;
@@ -1155,13 +1122,13 @@ int choose_lanes(int precision, int64_t n, int energy_type) {
 }
 
 static SweepFn pick_sweep(const LaunchCfg &cfg) {
-  if (cfg.precision == PSTAT_F64 && cfg.state_global) return pick_sweep_f64g(cfg);
+  if (cfg.home == SweepMem) return pick_sweep_f64g(cfg);
   return cfg.precision == PSTAT_F64 ? pick_sweep_f64(cfg)
        : (cfg.precision == PSTAT_Q16 ? pick_sweep_q16(cfg) : pick_sweep_f32(cfg));
 }
 
 static int sweep_lds_bytes(const LaunchCfg &cfg, const SweepArgs &a) {
-  if (cfg.state_global) return (a.lds_rows + 1) * 64 * 16;   // + the trash row
+  if (cfg.home == SweepMem) return (a.lds_rows + 1) * 64 * 16;   // + the trash row
   return (int)(a.n * a.lanes * cell_bytes(cfg.precision));
 }
 
@@ -1176,7 +1143,7 @@ hipError_t sweep_kernel_info(const LaunchCfg &cfg, const SweepArgs &a, int *lds_
   if (e != hipSuccess) return e;
   if (lds_bytes) *lds_bytes = lds;
   if (blocks_per_cu) *blocks_per_cu = nb;
-  if (name) *name = cfg.precision == PSTAT_F64 ? (cfg.state_global ? (cfg.packed ? "sweep_kernel<double, state in L2> [packed cases]" : "sweep_kernel<double, state in L2>")
+  if (name) *name = cfg.precision == PSTAT_F64 ? (cfg.home == SweepMem ? (cfg.packed ? "sweep_kernel<double, state in L2> [packed cases]" : "sweep_kernel<double, state in L2>")
                                                                    : (cfg.packed ? "sweep_kernel<double> [packed cases]" : "sweep_kernel<double>"))
                  : (cfg.precision == PSTAT_Q16 ? (cfg.packed ? "sweep_kernel<float, q16 state> [packed cases]" : "sweep_kernel<float, q16 state>")
                                                : (cfg.packed ? "sweep_kernel<float> [packed cases]" : "sweep_kernel<float>"));
