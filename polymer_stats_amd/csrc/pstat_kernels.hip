@@ -132,6 +132,30 @@ struct Draw {  // raw words of one step's proposal, mcmc_eap_chain.jl:277-280,28
   uint32_t w0;                                  // the index draw's raw word (its low bits feed the 53-bit eps, pstat_math.h)
 };
 
+// The generator as a step loop holds it in registers: G itself, except MWC64X under WIDE.  Its draw is one
+// v_mad_u64_u32, x * A + {c, 0}; held as two words, every draw re-forms that 64-bit addend with two moves.  The wide form
+// keeps the last product-sum t = {x, c} whole and takes the addend as t >> 32 -- one v_lshrrev_b64 -- with the 32 in a
+// register the compiler cannot see through (it would turn a literal shift back into the two moves; a vector register,
+// because one more scalar makes the polar instantiation spill its scalars: DESIGN 9.2).  Same words.
+template <typename G, bool WIDE> struct StepGen : G {};
+template <> struct StepGen<Mwc64x, true> {
+  uint64_t t;
+  uint32_t sh;
+  __device__ inline void load(const uint32_t *p, int64_t stride) {
+    t = (uint64_t)p[0] | ((uint64_t)p[stride] << 32);
+    sh = 32;
+    asm volatile("" : "+v"(sh));
+  }
+  __device__ inline uint32_t next() {
+    const uint32_t x = (uint32_t)t, r = x ^ (uint32_t)(t >> 32);
+    t = (uint64_t)x * Mwc64x::A + (t >> sh);
+    return r;
+  }
+  __device__ inline void store(uint32_t *p, int64_t stride) const {
+    p[0] = (uint32_t)t; p[stride] = (uint32_t)(t >> 32); p[2 * stride] = 0u; p[3 * stride] = 0u;
+  }
+};
+
 template <bool RARE, typename G>
 __device__ __forceinline__ Draw draw_step(G &g, uint32_t n, bool flips, uint32_t row_bytes, uint32_t lane_bytes) {
   Draw d;
@@ -223,7 +247,7 @@ __device__ __forceinline__ void run_segment(const SweepArgs &A, const DevState &
   // step sizes in the unit the proposal is added in: radians (f64), turns (f32), lattice cells (q16)
   constexpr double th_unit = Q ? 3.14159265358979323846 / 65536.0 : AG::unit;
   constexpr double ph_unit = Q ? 6.28318530717958647692 / 65536.0 : AG::unit;
-  G g;
+  StepGen<G, GM> g;
   g.load(S.rng + c, C);
   double phistep_d = S.stepsz[0 * C + c], thstep_d = S.stepsz[1 * C + c];
   R phistep = (R)(phistep_d / ph_unit), thstep = (R)(thstep_d / th_unit);
@@ -280,15 +304,32 @@ __device__ __forceinline__ void run_segment(const SweepArgs &A, const DevState &
   struct RowG { Cell l; v4i g; };
   struct RowG3 { RowG c, lo, hi; };     // Ising: the monomer, its lower and its upper neighbour
   using Row = typename std::conditional<GI, RowG3, typename std::conditional<GM, RowG, Cell>::type>::type;
+  // In the [n][64] layout (AS: every step but the chain-contiguous Ising one, which keeps a compare on idx and selects) the
+  // byte offset `cell` = idx * row_bytes + lane_bytes that the draw computed already orders the homes -- cell < trash
+  // exactly when idx < nL -- so the steering is arithmetic on it, one v_min_u32 and one v_sub per access:
+  //   LDS address    min(cell, trash)   rows [0, nL) are themselves, every memory row lands on the trash row;
+  //   buffer offset  cell - gbase       the resource spans the memory rows [nL, n) only (base cells + gbase, (n - nL) rows):
+  //                                     an LDS row wraps to >= 2^32 - gbase and is dropped by the bounds check.
+  // A step that stores nothing puts NOWHERE (~0) in place of `cell`: min() sends it to the trash row, ~0 - gbase is out
+  // of bounds as well (gbase < 2^24), and as a forwarding tag it equals no cell.  The fill and the spill address `cells`
+  // itself, not the resource: the bytes of row i stay at cells + i * row_bytes.
+  constexpr bool AS = GM && !CC;
+  constexpr uint32_t NOWHERE = 0xFFFFFFFFu;
   const uint32_t nL = GM ? (uint32_t)A.lds_rows : 0u;
   const uint32_t trash = nL * row_bytes + lane_bytes;        // LDS row nL: never read for its contents
-  __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(GM ? (void *)cells : (void *)nullptr, 0,
-                                                                  GM ? (int)((uint32_t)n * row_bytes) : 0, 0x00020000);
+  const uint32_t gbase = AS ? nL * row_bytes : 0u;           // the LDS rows' share of `cells` (lds_rows <= n)
+  __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(GM ? (void *)(cells + gbase) : (void *)nullptr, 0,
+                                                                  GM ? (int)((uint32_t)n * row_bytes - gbase) : 0, 0x00020000);
   auto rdcell = [&](const uint32_t idx, const uint32_t cell) __attribute__((always_inline)) -> RowG {
-    const bool inL = idx < nL;
     RowG r;
-    r.l = *reinterpret_cast<Cell *>(smem + (inL ? cell : trash));
-    r.g = __builtin_amdgcn_raw_buffer_load_b128(rsrc, inL ? 0xFFFFFFFFu : gofs(idx), 0, 0);
+    if constexpr (AS) {
+      r.l = *reinterpret_cast<Cell *>(smem + (cell < trash ? cell : trash));
+      r.g = __builtin_amdgcn_raw_buffer_load_b128(rsrc, cell - gbase, 0, 0);
+    } else {
+      const bool inL = idx < nL;
+      r.l = *reinterpret_cast<Cell *>(smem + (inL ? cell : trash));
+      r.g = __builtin_amdgcn_raw_buffer_load_b128(rsrc, inL ? 0xFFFFFFFFu : gofs(idx), 0, 0);
+    }
     return r;
   };
   // a fetched cell at its first use: its home, then the commits made after its load was issued (fw2 older, fw1 newer)
@@ -331,7 +372,13 @@ __device__ __forceinline__ void run_segment(const SweepArgs &A, const DevState &
     }
   };
   auto wr = [&](const Draw &d, const Cell v, const bool ok) __attribute__((always_inline)) {
-    if constexpr (GM) {
+    if constexpr (AS) {
+      const uint32_t at = ok ? d.cell : NOWHERE;
+      *reinterpret_cast<Cell *>(smem + (at < trash ? at : trash)) = v;
+      typedef double v2dd __attribute__((ext_vector_type(2)));
+      const v2dd vv = {v.x, v.y};
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i, vv), rsrc, at - gbase, 0, 0);
+    } else if constexpr (GM) {
       const bool inL = d.idx < nL;
       *reinterpret_cast<Cell *>(smem + ((ok && inL) ? d.cell : trash)) = v;
       typedef double v2dd __attribute__((ext_vector_type(2)));
