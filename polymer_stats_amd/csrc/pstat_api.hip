@@ -37,7 +37,16 @@ int fail(int code, const char *fmt, ...) {
       return fail(PSTAT_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e));          \
   } while (0)
 
+// an int-returning step of an entry point: PSTAT_OK or the status to hand back
+#define PSTAT_TRY(expr)             \
+  do {                              \
+    int _rc = (expr);               \
+    if (_rc) return _rc;            \
+  } while (0)
+
 constexpr uint64_t CKPT_MAGIC = 0x5053544154434b34ull;  // "PSTATCK4" (v4: the header identifies the handle it was taken from)
+constexpr size_t kStateBuffers = 11;   // a checkpoint image holds the handle's first kStateBuffers allocations (pstat_create)
+constexpr int kLdsBudget = 160 * 1024;   // LDS of a CU: the most a workgroup's dynamic LDS can be
 
 struct Buffer {
   void *ptr = nullptr;
@@ -86,6 +95,7 @@ struct pstat_handle {
   hipStream_t stream = nullptr;
   bool own_stream = false;
   LaunchCfg cfg{};
+  StepKernel kernel{};              // the step kernel of cfg, resolved whenever cfg changes (resolve_kernel)
   Overrides ov;                     // test knobs, read at creation
   SweepArgs args{};
   DevState S{};
@@ -224,17 +234,48 @@ int validate(const pstat_params *c, int ncases) {
   return PSTAT_OK;
 }
 
-// attributes of the kernel that runs this configuration's steps (the chain-per-wavefront kernels leave *lds alone)
-hipError_t kernel_info(const LaunchCfg &cfg, const SweepArgs &a, int *lds, int *bpc, const char **name) {
-  switch (cfg.home) {
-    case SweepLds: case SweepMem: return sweep_kernel_info(cfg, a, lds, bpc, name);
-    case ClusterLds: return cluster_kernel_info(cfg, a, lds, bpc, name);
-    case ClusterMem: return cluster_gm_kernel_info(cfg, a, lds, bpc, name);
-    case ClusterChainWave: return cluster_cw_kernel_info(cfg, a.n, bpc, name);
-    case ClusterAllPairs: return cluster_wave_kernel_info(cfg, a.n, bpc, name);
-    case Interacting: return interacting_kernel_info(cfg, a.n, bpc, name);
-  }
-  return hipErrorInvalidValue;
+// ---- the handle's step kernel: resolved once, probed and launched here
+// bytes of one monomer's cell (theta, phi) in LDS
+int cell_bytes(int precision) { return precision == PSTAT_F64 ? 16 : (precision == PSTAT_Q16 ? 4 : 8); }
+
+// the most lanes (64, 32, 16, 8) whose chains of n cells fit a CU's LDS; 0: not even 8
+int choose_lanes(int precision, int64_t n) {
+  for (int lanes = 64; lanes >= 8; lanes >>= 1)
+    if (n * cell_bytes(precision) * lanes <= kLdsBudget) return lanes;
+  return 0;
+}
+
+// dynamic LDS of a workgroup of a.lanes chains
+int lds_bytes(Home home, int precision, const SweepArgs &a) {
+  if (home == SweepMem) return (a.lds_rows + 1) * 64 * 16;   // + the trash row
+  if (home == SweepLds || home == ClusterLds) return (int)(a.n * a.lanes * cell_bytes(precision));
+  return 0;
+}
+
+// queue layout: [0] error flag (sticky: never cleared by a launch), [1] job counter, [2 ..] per-block "segments done"
+size_t queue_ints(const SweepArgs &a) { return 2 + (size_t)a.nblocks; }
+
+// The kernel that runs cfg's steps, ready to launch with any LDS size the handle can ask for.
+int resolve_kernel(const LaunchCfg &cfg, int64_t n, StepKernel *out) {
+  static StepKernel (*const of_home[])(const LaunchCfg &, int64_t) = {   // indexed by Home
+      sweep_step_kernel, sweep_step_kernel, cluster_step_kernel, cluster_gm_step_kernel,
+      cluster_cw_step_kernel, cluster_wave_step_kernel, interacting_step_kernel};
+  static_assert(sizeof of_home / sizeof *of_home == Interacting + 1, "one resolver per Home");
+  *out = of_home[cfg.home](cfg, n);
+  if (cfg.home == SweepLds || cfg.home == SweepMem || cfg.home == ClusterLds)
+    HIP_TRY(hipFuncSetAttribute(out->fn, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget));
+  return PSTAT_OK;
+}
+
+// The sweep's instantiation depends on cfg.lag: whoever changes a handle's lag does it here.
+int set_lag(pstat_handle *h, int lag) {
+  h->cfg.lag = lag;
+  return resolve_kernel(h->cfg, h->base.n, &h->kernel);
+}
+
+// resident workgroups per CU of kernel k with `lds` bytes of dynamic LDS
+hipError_t occupancy(const StepKernel &k, int lds, int *blocks_per_cu) {
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k.fn, 64, lds);
 }
 
 // ---- launch shape of the chain-per-lane kernels: active lanes per workgroup (one wave) and what a workgroup holds.
@@ -255,8 +296,9 @@ hipError_t kernel_info(const LaunchCfg &cfg, const SweepArgs &a, int *lds, int *
 // 676 -> 366 ms per 1e4 steps).  profiles/r04/experiments/time_packed*.txt, twin.txt.
 struct Shape { int lanes; int64_t nblocks; double cost; };
 
-Shape shape(LaunchCfg cfg, const SweepArgs &a, const bool packed, const bool deep, const int cus, const int force_lanes) {
-  cfg.packed = packed ? 1 : 0;
+// (k: the kernel of cfg, whose `packed` names the layout)
+Shape shape(const StepKernel &k, const LaunchCfg &cfg, const SweepArgs &a, const bool deep, const int cus, const int force_lanes) {
+  const bool packed = cfg.packed != 0;
   const int lanes = a.lanes;
   const int64_t per_case = a.chains_per_case, total = per_case * a.ncases;
   auto wgs_of = [&](const int cand) -> int64_t {
@@ -264,8 +306,8 @@ Shape shape(LaunchCfg cfg, const SweepArgs &a, const bool packed, const bool dee
   };
   Shape best{lanes, wgs_of(lanes), 1e300};
   if (cfg.home == SweepMem) {   // f64 sweep with its cells in memory: 64 lanes on every SIMD
-    int lds0 = 0, bpc = 0;
-    if (kernel_info(cfg, a, &lds0, &bpc, nullptr) != hipSuccess || bpc < 1) bpc = 4;
+    int bpc = 0;
+    if (occupancy(k, lds_bytes(cfg.home, cfg.precision, a), &bpc) != hipSuccess || bpc < 1) bpc = 4;
     double cost = (double)best.nblocks / ((double)bpc * cus);
     best.cost = cost < 1.0 ? 1.0 : cost;
     return best;
@@ -274,8 +316,8 @@ Shape shape(LaunchCfg cfg, const SweepArgs &a, const bool packed, const bool dee
     // Chains in device memory: nothing limits a wave to fewer than 64 lanes, but an ensemble of fewer waves than the
     // chip has SIMDs (a phase scan: 546 grid points x 64 chains) runs faster as more, emptier waves -- they fill the
     // idle SIMDs, and a wave's step lasts as long as its LONGEST cluster, which grows like the logarithm of its lanes.
-    int lds0 = 0, bpc = 0;
-    if (kernel_info(cfg, a, &lds0, &bpc, nullptr) != hipSuccess || bpc < 1) bpc = 1;
+    int bpc = 0;
+    if (occupancy(k, 0, &bpc) != hipSuccess || bpc < 1) bpc = 1;
     const double slots = (double)bpc * cus;
     // (packed, and the unpacked launch not many rounds deep: no wave larger than a case's chains rounded up to 16 / 32 / 64
     // -- the clustering main's packing rule, above)
@@ -293,17 +335,15 @@ Shape shape(LaunchCfg cfg, const SweepArgs &a, const bool packed, const bool dee
   // State in LDS: a CU holds at most 160 KiB / (bytes per chain) chains; pick the lane count that minimises the
   // makespan max(1, workgroups / resident slots) of one launch -- e.g. f32, n = 100: 51 lanes x 4 workgroups per CU
   // (204 chains, all four SIMDs) instead of 64 x 3 (192 chains, three SIMDs).
-  bool lds_starved = false;     // full waves: fewer than one per SIMD fit a CU's LDS
-  {
-    int lds0 = 0, bpc0 = 0;
-    lds_starved = kernel_info(cfg, a, &lds0, &bpc0, nullptr) == hipSuccess && bpc0 < 4;
-  }
+  int bpc0 = 0;
+  const bool lds_starved =      // full waves: fewer than one per SIMD fit a CU's LDS
+      occupancy(k, lds_bytes(cfg.home, cfg.precision, a), &bpc0) == hipSuccess && bpc0 < 4;
   for (int cand = lanes; cand >= 8; --cand) {
     if (force_lanes >= 1 && force_lanes <= lanes && cand != force_lanes) continue;
     SweepArgs probe = a;
     probe.lanes = cand;
-    int lds = 0, bpc = 0;
-    if (kernel_info(cfg, probe, &lds, &bpc, nullptr) != hipSuccess || bpc < 1) continue;
+    int bpc = 0;
+    if (occupancy(k, lds_bytes(cfg.home, cfg.precision, probe), &bpc) != hipSuccess || bpc < 1) continue;
     const double slots = (double)bpc * cus;
     double cost = (double)wgs_of(cand) / slots;
     if (cost < 1.0) cost = 1.0;
@@ -339,8 +379,9 @@ int choose_segments(int64_t blocks, int64_t slots, int64_t nsteps, int64_t min_s
 }
 
 // Launches the handle's step kernel for `nsteps` steps from step `step0` of the current init (nsteps = 0: the all-pairs
-// kernels derive r, p, U from fresh angles).  A chain-per-lane launch is split into time segments of its job queue.
-hipError_t launch_steps(pstat_handle *h, int64_t step0, int64_t nsteps) {
+// kernels derive r, p, U from fresh angles; reinit_mode 1 | 2: home Interacting re-initialises, 2 = forced).  A chain-per-lane
+// launch is split into time segments of its job queue.
+hipError_t launch_steps(pstat_handle *h, int64_t step0, int64_t nsteps, int reinit_mode = 0) {
   SweepArgs &A = h->args;
   A.nsteps = nsteps;
   A.step0 = step0;
@@ -369,16 +410,25 @@ hipError_t launch_steps(pstat_handle *h, int64_t step0, int64_t nsteps) {
     // more workgroups than that would only sit in the predecessor wait -- and, worse, leave the working
     // ones unevenly spread over the SIMDs.
     grid = (unsigned)(blocks < h->slots ? blocks : h->slots);
+    hipError_t e = hipMemsetAsync(h->d_queue + 1, 0, sizeof(int) * (queue_ints(A) - 1), h->stream);   // [0]: the sticky error word
+    if (e != hipSuccess) return e;
+  } else {
+    grid = (unsigned)h->S.C;
   }
-  switch (h->cfg.home) {
-    case SweepLds: case SweepMem: return launch_sweep(h->cfg, A, h->S, h->d_cases, h->d_queue, grid, h->stream);
-    case ClusterLds: return launch_cluster(h->cfg, A, h->S, h->d_cases, h->d_queue, grid, h->stream);
-    case ClusterMem: return launch_cluster_gm(h->cfg, A, h->S, h->d_cases, h->d_queue, grid, h->stream);
-    case ClusterChainWave: return launch_cluster_cw(h->cfg, A, h->S, h->d_cases, h->stream);
-    case ClusterAllPairs: return launch_cluster_wave(h->cfg, A, h->S, h->d_cases, h->stream);
-    case Interacting: return launch_interacting(h->cfg, A, h->S, h->d_cases, 0, h->stream);
+  // the kernel's arguments: (SweepArgs, DevState, cases) and the family's scalars (StepKernel, pstat_device.h)
+  const LaunchCfg &cfg = h->cfg;
+  SweepRare rare{cfg.do_flips, cfg.lag, cfg.umbrella};
+  int umbrella = cfg.umbrella, cutoff = cfg.energy_type == PSTAT_CUTOFF ? 1 : 0;
+  int do_flips = cfg.do_flips, lag = (cfg.lag || reinit_mode) ? 1 : 0;
+  void *argv[6] = {&A, &h->S, &h->d_cases};
+  switch (cfg.home) {
+    case SweepLds: case SweepMem: argv[3] = &rare; argv[4] = &h->d_queue; break;
+    case ClusterLds: case ClusterMem: argv[3] = &umbrella; argv[4] = &h->d_queue; break;
+    case ClusterChainWave: argv[3] = &umbrella; break;
+    case ClusterAllPairs: argv[3] = &umbrella; argv[4] = &cutoff; break;
+    case Interacting: argv[3] = &do_flips; argv[4] = &lag; argv[5] = &reinit_mode; break;
   }
-  return hipErrorInvalidValue;
+  return hipLaunchKernel(h->kernel.fn, dim3(grid), dim3(64), argv, lds_bytes(cfg.home, cfg.precision, A), h->stream);
 }
 
 int set_device(pstat_handle *h) {
@@ -476,7 +526,9 @@ int pstat_create(const pstat_params *cases, int32_t ncases, void *stream, pstat_
   if (cases[0].device < 0 || cases[0].device >= ndev)
     return fail(PSTAT_ERR_NO_DEVICE, "device %d out of range (have %d)", cases[0].device, ndev);
 
-  pstat_handle *h = new (std::nothrow) pstat_handle;
+  struct Destroy { void operator()(pstat_handle *p) const { pstat_destroy(p); } };
+  std::unique_ptr<pstat_handle, Destroy> owner(new (std::nothrow) pstat_handle);   // every early return below destroys it
+  pstat_handle *const h = owner.get();
   if (!h) return fail(PSTAT_ERR_NOMEM, "host allocation failed");
   try {   // std::vector growth may throw: nothing propagates through the C ABI
   h->base = cases[0];
@@ -496,12 +548,10 @@ int pstat_create(const pstat_params *cases, int32_t ncases, void *stream, pstat_
             h->base.umbrella ? 1 : 0, any_fx ? 1 : 0, 0, h->base.rng, h->base.move_set};
   const Home home = h->cfg.home = choose_home(h->cfg, h->base.n, h->base.num_chains, ncases, h->ov);
 
-  int lanes = (home == SweepLds || home == ClusterLds) ? choose_lanes(h->base.precision, h->base.n, h->base.energy_type) : 64;
-  if (lanes == 0) {
-    delete h;
+  const int lanes = (home == SweepLds || home == ClusterLds) ? choose_lanes(h->base.precision, h->base.n) : 64;
+  if (lanes == 0)
     return fail(PSTAT_ERR_UNSUPPORTED, "num-monomers = %lld does not fit the 160 KiB LDS of a CU",
                 (long long)cases[0].n);
-  }
   SweepArgs &A = h->args;
   A.n = h->base.n;
   A.chains_per_case = h->base.num_chains;
@@ -521,100 +571,87 @@ int pstat_create(const pstat_params *cases, int32_t ncases, void *stream, pstat_
     A.lds_rows = (int32_t)(h->base.n < rows ? h->base.n : rows);
   }
 
-#define CREATE_TRY(expr)            \
-  do {                              \
-    int _rc = (expr);               \
-    if (_rc) { pstat_destroy(h); return _rc; } \
-  } while (0)
-#define CREATE_HIP(expr)                                                                   \
-  do {                                                                                     \
-    hipError_t _e = (expr);                                                                \
-    if (_e != hipSuccess) {                                                                \
-      pstat_destroy(h);                                                                    \
-      return fail(PSTAT_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e));           \
-    }                                                                                      \
-  } while (0)
-
-  CREATE_HIP(hipSetDevice(h->device));
+  HIP_TRY(hipSetDevice(h->device));
+  PSTAT_TRY(resolve_kernel(h->cfg, A.n, &h->kernel));
   hipDeviceProp_t prop;
   if (chain_per_lane(home)) {
-    CREATE_HIP(hipGetDeviceProperties(&prop, h->device));
-    Shape pick = shape(h->cfg, A, false, false, prop.multiProcessorCount, h->ov.lanes);
+    HIP_TRY(hipGetDeviceProperties(&prop, h->device));
+    Shape pick = shape(h->kernel, h->cfg, A, false, prop.multiProcessorCount, h->ov.lanes);
     if (ncases > 1) {   // (every chain-per-lane kernel has a packed-cases instantiation)
-      const Shape pk = shape(h->cfg, A, true, pick.cost >= 4.0 || h->ov.pack == 1, prop.multiProcessorCount, h->ov.lanes);
+      LaunchCfg packed = h->cfg;
+      packed.packed = 1;
+      StepKernel kp;
+      PSTAT_TRY(resolve_kernel(packed, A.n, &kp));
+      const Shape pk = shape(kp, packed, A, pick.cost >= 4.0 || h->ov.pack == 1, prop.multiProcessorCount, h->ov.lanes);
       if (h->ov.pack >= 0 ? h->ov.pack == 1 : pk.cost < 0.95 * pick.cost) {
         pick = pk;
-        h->cfg.packed = 1;
+        h->cfg = packed;
+        h->kernel = kp;
         A.packed = 1;
       }
     }
     A.lanes = pick.lanes;
     A.blocks_per_case = (h->base.num_chains + pick.lanes - 1) / pick.lanes;
     A.nblocks = pick.nblocks;
-    if (home == ClusterMem && (uint64_t)pick.lanes * (uint64_t)h->base.n * (h->base.precision == PSTAT_F64 ? PSTAT_CLUSTER_GM_CELL : 20u) >= 0x80000000ull) {
-      pstat_destroy(h);
+    if (home == ClusterMem && (uint64_t)pick.lanes * (uint64_t)h->base.n * (h->base.precision == PSTAT_F64 ? PSTAT_CLUSTER_GM_CELL : 20u) >= 0x80000000ull)
       return fail(PSTAT_ERR_UNSUPPORTED, "num-monomers = %lld: a wave's working buffer must stay below 2 GiB",
                   (long long)cases[0].n);
-    }
   }
   // (checked on the FINAL lane count: the job queue counts blocks and (block, segment) jobs in 32 bits)
-  if (A.nblocks > 0x3fffffffLL) {
-    pstat_destroy(h);
+  if (A.nblocks > 0x3fffffffLL)
     return fail(PSTAT_ERR_INVALID_ARG, "too many chains for one handle: %lld chain blocks", (long long)A.nblocks);
-  }
   if (stream) {
     h->stream = (hipStream_t)stream;
   } else {
-    CREATE_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     h->own_stream = true;
   }
   DevState &S = h->S;
   const int64_t C = (int64_t)ncases * h->base.num_chains;
   S.C = C;
   const size_t n = (size_t)h->base.n, Cz = (size_t)C;
-  // checkpoint order = allocation order
-  CREATE_TRY(alloc(h, &S.ang, 2 * n * Cz * h->elem));
-  CREATE_TRY(alloc(h, (void **)&S.rng, 4 * Cz * sizeof(uint32_t)));
-  CREATE_TRY(alloc(h, (void **)&S.stepsz, 2 * Cz * sizeof(double)));
-  CREATE_TRY(alloc(h, (void **)&S.win, 2 * Cz * sizeof(int64_t)));
-  CREATE_TRY(alloc(h, (void **)&S.nacc_total, Cz * sizeof(int64_t)));
-  CREATE_TRY(alloc(h, (void **)&S.obs, NOBS_STATE * Cz * sizeof(double)));
-  CREATE_TRY(alloc(h, (void **)&S.sums, NSUMS * Cz * sizeof(double)));
-  CREATE_TRY(alloc(h, (void **)&S.wnorm, Cz * sizeof(double)));
-  CREATE_TRY(alloc(h, (void **)&S.lag, Cz * sizeof(double)));
-  CREATE_TRY(alloc(h, (void **)&S.uref, Cz * sizeof(double)));
-  CREATE_TRY(alloc(h, (void **)&S.nanrej, Cz * sizeof(int64_t)));
-  const size_t nstate = h->bufs.size();
-  CREATE_TRY(alloc(h, &S.ang_tmp, 2 * n * Cz * h->elem));
+  // checkpoint order = allocation order: the image is these buffers
+  const struct { void **p; size_t bytes; } state[] = {
+      {&S.ang, 2 * n * Cz * h->elem},
+      {(void **)&S.rng, 4 * Cz * sizeof(uint32_t)},
+      {(void **)&S.stepsz, 2 * Cz * sizeof(double)},
+      {(void **)&S.win, 2 * Cz * sizeof(int64_t)},
+      {(void **)&S.nacc_total, Cz * sizeof(int64_t)},
+      {(void **)&S.obs, NOBS_STATE * Cz * sizeof(double)},
+      {(void **)&S.sums, NSUMS * Cz * sizeof(double)},
+      {(void **)&S.wnorm, Cz * sizeof(double)},
+      {(void **)&S.lag, Cz * sizeof(double)},
+      {(void **)&S.uref, Cz * sizeof(double)},
+      {(void **)&S.nanrej, Cz * sizeof(int64_t)},
+  };
+  static_assert(sizeof state / sizeof *state == kStateBuffers, "the checkpoint image is the first kStateBuffers allocations");
+  for (const auto &b : state) PSTAT_TRY(alloc(h, b.p, b.bytes));
+  PSTAT_TRY(alloc(h, &S.ang_tmp, 2 * n * Cz * h->elem));
   if (home == ClusterMem)    // working copy of the chains, [chain block][lane][n] cells of 40 (f64) / 20 (f32) bytes (pstat_cluster_gm.hip)
-    CREATE_TRY(alloc(h, &S.work, cluster_gm_work_bytes(h->cfg, A)));
+    PSTAT_TRY(alloc(h, &S.work, cluster_gm_work_bytes(h->cfg, A)));
   else if (home == SweepMem)   // working copy of the cells, [chain block][n][64] double2 (run_segment, ST = 2)
-    CREATE_TRY(alloc(h, &S.work, (size_t)A.nblocks * n * 64 * 16));
-  CREATE_TRY(alloc(h, (void **)&h->d_cases, sizeof(CaseConst) * (size_t)ncases));
-  CREATE_TRY(alloc(h, (void **)&h->d_queue, sizeof(int) * sweep_queue_ints(h->args)));
-  CREATE_TRY(alloc(h, (void **)&h->d_partial, sizeof(double) * reduce_scratch_doubles()));
-  CREATE_TRY(alloc(h, (void **)&h->d_red, sizeof(double) * PSTAT_NRED));
-  (void)nstate;
-  CREATE_HIP(hipMemsetAsync(h->d_queue, 0, sizeof(int) * sweep_queue_ints(h->args), h->stream));
-  CREATE_HIP(hipMemcpyAsync(h->d_cases, h->cases.data(), sizeof(CaseConst) * (size_t)ncases,
-                            hipMemcpyHostToDevice, h->stream));
+    PSTAT_TRY(alloc(h, &S.work, (size_t)A.nblocks * n * 64 * 16));
+  PSTAT_TRY(alloc(h, (void **)&h->d_cases, sizeof(CaseConst) * (size_t)ncases));
+  PSTAT_TRY(alloc(h, (void **)&h->d_queue, sizeof(int) * queue_ints(h->args)));
+  PSTAT_TRY(alloc(h, (void **)&h->d_partial, sizeof(double) * reduce_scratch_doubles()));
+  PSTAT_TRY(alloc(h, (void **)&h->d_red, sizeof(double) * PSTAT_NRED));
+  HIP_TRY(hipMemsetAsync(h->d_queue, 0, sizeof(int) * queue_ints(h->args), h->stream));
+  HIP_TRY(hipMemcpyAsync(h->d_cases, h->cases.data(), sizeof(CaseConst) * (size_t)ncases,
+                         hipMemcpyHostToDevice, h->stream));
   const InitOpts io{h->base.use_x0, h->base.x0_phi, h->base.x0_theta, h->base.dx0_phi, h->base.dx0_theta, nullptr};
-  CREATE_HIP(launch_init(h->cfg, h->args, h->S, h->d_cases, h->base.phi_step, h->base.theta_step, io, h->stream));
+  HIP_TRY(launch_init(h->cfg, h->args, h->S, h->d_cases, h->base.phi_step, h->base.theta_step, io, h->stream));
   if (all_pairs(h->base.energy_type))  // a zero-step launch derives r, p, U (with the pair energy) from the fresh angles
-    CREATE_HIP(launch_steps(h, 0, 0));
-  CREATE_HIP(hipStreamSynchronize(h->stream));  // h->cases must outlive the copy; also surfaces faults here
+    HIP_TRY(launch_steps(h, 0, 0));
+  HIP_TRY(hipStreamSynchronize(h->stream));  // h->cases must outlive the copy; also surfaces faults here
   if (chain_per_lane(home)) {
-    int lds = 0, bpc = 0;
-    CREATE_HIP(kernel_info(h->cfg, h->args, &lds, &bpc, nullptr));
+    int bpc = 0;
+    HIP_TRY(occupancy(h->kernel, lds_bytes(home, h->cfg.precision, h->args), &bpc));
     h->slots = (bpc > 0 ? bpc : 1) * prop.multiProcessorCount;
   }
-#undef CREATE_TRY
-#undef CREATE_HIP
   } catch (const std::bad_alloc &) {
-    pstat_destroy(h);
     return fail(PSTAT_ERR_NOMEM, "host allocation failed");
   }
-  *out = h;
+  *out = owner.release();
   return PSTAT_OK;
 }
 
@@ -658,17 +695,12 @@ int pstat_reinit(pstat_handle *h, int32_t force_init) {
     return fail(PSTAT_ERR_UNSUPPORTED, "mcmc_clustering_eap_chain.jl has no --num-inits: nothing to re-initialise");
   int rc = set_device(h);
   if (rc) return rc;
-  if (h->cfg.home == Interacting) {   // done inside the one-chain-per-wave kernel
-    h->args.nsteps = 0; h->args.step0 = 0;
-    HIP_TRY(launch_interacting(h->cfg, h->args, h->S, h->d_cases, force_init ? 2 : 1, h->stream));
-    h->step_in_init = 0;
-    h->cfg.lag = 1;
-    return PSTAT_OK;
-  }
-  HIP_TRY(launch_reinit(h->cfg, h->args, h->S, h->d_cases, force_init, h->stream));
+  if (h->cfg.home == Interacting)   // done inside the one-chain-per-wave kernel
+    HIP_TRY(launch_steps(h, 0, 0, force_init ? 2 : 1));
+  else
+    HIP_TRY(launch_reinit(h->cfg, h->args, h->S, h->d_cases, force_init, h->stream));
   h->step_in_init = 0;
-  h->cfg.lag = 1;  // from now on the sweep tracks the acceptor's stale-cache offset
-  return PSTAT_OK;
+  return set_lag(h, 1);  // from now on the sweep tracks the acceptor's stale-cache offset
 }
 
 int pstat_reset_averages(pstat_handle *h) {
@@ -733,8 +765,7 @@ int pstat_restart_from_x0(pstat_handle *h, const double *x0, int64_t len, double
   if (e != hipSuccess) return fail(PSTAT_ERR_HIP, "re-initialisation from x0 failed: %s", hipGetErrorString(e));
   h->steps_recorded = 0;
   h->step_in_init = 0;
-  h->cfg.lag = 0;
-  return PSTAT_OK;
+  return set_lag(h, 0);
 }
 
 int pstat_scale_kT(pstat_handle *h, double mult) {
@@ -943,7 +974,6 @@ struct CkptHeader {
   uint64_t seed, chain_id0;     // case 0's
   uint64_t params_fnv;          // fingerprint of everything else a chain's continuation depends on (params_fingerprint)
 };
-static const int kStateBuffers = 11;
 
 // FNV-1a over the options that are not spelled out in the header: every case's physics scalars except its current kT
 // (which the image carries and restore re-instates), its seed and first chain id, the kT it was created with, and the
@@ -971,7 +1001,7 @@ static uint64_t params_fingerprint(const pstat_handle *h) {
 
 static size_t checkpoint_bytes(const pstat_handle *h) {
   size_t need = sizeof(CkptHeader) + sizeof(double) * (size_t)h->ncases;
-  for (int i = 0; i < kStateBuffers; ++i) need += h->bufs[i].bytes;
+  for (size_t i = 0; i < kStateBuffers; ++i) need += h->bufs[i].bytes;
   return need;
 }
 
@@ -997,7 +1027,7 @@ int pstat_checkpoint(pstat_handle *h, void *buf, size_t *bytes) {
   std::memcpy(q, &hd, sizeof hd);
   q += sizeof hd;
   for (int i = 0; i < h->ncases; ++i, q += sizeof(double)) std::memcpy(q, &h->cases[(size_t)i].kT, sizeof(double));
-  for (int i = 0; i < kStateBuffers; ++i) {
+  for (size_t i = 0; i < kStateBuffers; ++i) {
     HIP_TRY(hipMemcpy(q, h->bufs[i].ptr, h->bufs[i].bytes, hipMemcpyDeviceToHost));
     q += h->bufs[i].bytes;
   }
@@ -1054,14 +1084,13 @@ int pstat_restore(pstat_handle *h, const void *buf, size_t bytes) {
   // the temperature of every case as it was when the image was taken (a rung of the burn-in ladder: pstat_scale_kT / pstat_set_kT)
   for (int i = 0; i < h->ncases; ++i) h->cases[(size_t)i].kT = kT[(size_t)i];
   HIP_TRY(hipMemcpy(h->d_cases, h->cases.data(), sizeof(CaseConst) * (size_t)h->ncases, hipMemcpyHostToDevice));
-  for (int i = 0; i < kStateBuffers; ++i) {
+  for (size_t i = 0; i < kStateBuffers; ++i) {
     HIP_TRY(hipMemcpy(h->bufs[i].ptr, q, h->bufs[i].bytes, hipMemcpyHostToDevice));
     q += h->bufs[i].bytes;
   }
   h->steps_recorded = hd.steps_recorded;
   h->step_in_init = hd.step_in_init;
-  h->cfg.lag = hd.lag;
-  return PSTAT_OK;
+  return set_lag(h, hd.lag);
 }
 
 int pstat_launch_info_get(pstat_handle *h, pstat_launch_info *out) {
@@ -1069,10 +1098,10 @@ int pstat_launch_info_get(pstat_handle *h, pstat_launch_info *out) {
   int rc = set_device(h);
   if (rc) return rc;
   std::memset(out, 0, sizeof *out);
-  int lds = 0, bpc = 0;
-  const char *name = "";
-  HIP_TRY(kernel_info(h->cfg, h->args, &lds, &bpc, &name));
-  std::snprintf(out->kernel, sizeof out->kernel, "%s", name);
+  const int lds = lds_bytes(h->cfg.home, h->cfg.precision, h->args);
+  int bpc = 0;
+  HIP_TRY(occupancy(h->kernel, lds, &bpc));
+  std::snprintf(out->kernel, sizeof out->kernel, "%s", h->kernel.name);
   out->lds_bytes = lds;
   out->threads_per_block = 64;
   out->lanes_per_block = h->args.lanes;

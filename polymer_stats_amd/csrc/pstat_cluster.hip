@@ -563,41 +563,10 @@ ClusterFn pick_cluster_f64(const LaunchCfg &cfg) {
   return cfg.rng == PSTAT_RNG_XOSHIRO128PP ? pick_ct_en<double, Xoshiro128pp, 0>(cfg) : pick_ct_en<double, Mwc64x, 0>(cfg);
 }
 
-static ClusterFn pick_cluster(const LaunchCfg &cfg) {
-  return cfg.precision == PSTAT_F64 ? pick_cluster_f64(cfg) : pick_cluster_f32(cfg);
-}
-
-static int cluster_lds_bytes(const LaunchCfg &cfg, const SweepArgs &a) {
-  return (int)(a.n * a.lanes * (cfg.precision == PSTAT_F64 ? 16 : (cfg.precision == PSTAT_Q16 ? 4 : 8)));
-}
-
-hipError_t cluster_kernel_info(const LaunchCfg &cfg, const SweepArgs &a, int *lds_bytes, int *blocks_per_cu,
-                               const char **name) {
-  ClusterFn fn = pick_cluster(cfg);
-  const int lds = cluster_lds_bytes(cfg, a);
-  hipError_t e = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  if (e != hipSuccess) return e;
-  int nb = 0;
-  e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)fn, 64, lds);
-  if (e != hipSuccess) return e;
-  if (lds_bytes) *lds_bytes = lds;
-  if (blocks_per_cu) *blocks_per_cu = nb;
-  if (name) *name = cfg.precision == PSTAT_F64 ? (cfg.packed ? "cluster_kernel<double> [packed cases]" : "cluster_kernel<double>")
-                 : (cfg.precision == PSTAT_Q16 ? (cfg.packed ? "cluster_kernel<float, q16 state> [packed cases]" : "cluster_kernel<float, q16 state>")
-                                               : (cfg.packed ? "cluster_kernel<float> [packed cases]" : "cluster_kernel<float>"));
-  return hipSuccess;
-}
-
-hipError_t launch_cluster(const LaunchCfg &cfg, const SweepArgs &a, const DevState &s, const CaseConst *cases,
-                          int *queue, unsigned grid, hipStream_t stream) {
-  ClusterFn fn = pick_cluster(cfg);
-  const int lds = cluster_lds_bytes(cfg, a);
-  hipError_t e = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  if (e != hipSuccess) return e;
-  e = hipMemsetAsync(queue + 1, 0, sizeof(int) * (sweep_queue_ints(a) - 1), stream);   // queue[0]: sticky error word
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(fn, dim3(grid), dim3(64), lds, stream, a, s, cases, cfg.umbrella, queue);
-  return hipGetLastError();
+StepKernel cluster_step_kernel(const LaunchCfg &cfg, int64_t) {
+  if (cfg.precision == PSTAT_F64) return {(const void *)pick_cluster_f64(cfg), PSTAT_KERNEL_NAME(cfg, "cluster_kernel<double>")};
+  return {(const void *)pick_cluster_f32(cfg), cfg.precision == PSTAT_Q16 ? PSTAT_KERNEL_NAME(cfg, "cluster_kernel<float, q16 state>")
+                                                                            : PSTAT_KERNEL_NAME(cfg, "cluster_kernel<float>")};
 }
 #endif
 

@@ -724,19 +724,8 @@ CwFn pick(const LaunchCfg &cfg, const int64_t n) {
 
 }  // namespace
 
-hipError_t cluster_cw_kernel_info(const LaunchCfg &cfg, const int64_t n, int *blocks_per_cu, const char **name) {
-  int nb = 0;
-  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)pick(cfg, n), 64, 0);
-  if (e != hipSuccess) return e;
-  if (blocks_per_cu) *blocks_per_cu = nb;
-  if (name) *name = "cluster_chain_wave_kernel<double>";
-  return hipSuccess;
-}
-
-hipError_t launch_cluster_cw(const LaunchCfg &cfg, const SweepArgs &a, const DevState &s, const CaseConst *cases,
-                             hipStream_t stream) {
-  hipLaunchKernelGGL(pick(cfg, a.n), dim3((unsigned)s.C), dim3(64), 0, stream, a, s, cases, cfg.umbrella);
-  return hipGetLastError();
+StepKernel cluster_cw_step_kernel(const LaunchCfg &cfg, const int64_t n) {
+  return {(const void *)pick(cfg, n), "cluster_chain_wave_kernel<double>"};
 }
 
 }  // namespace pstat

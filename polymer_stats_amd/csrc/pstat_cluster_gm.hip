@@ -747,25 +747,9 @@ size_t cluster_gm_work_bytes(const LaunchCfg &cfg, const SweepArgs &a) {
          (cfg.precision == PSTAT_F64 ? cell_bytes<double>() : cell_bytes<float>());
 }
 
-hipError_t cluster_gm_kernel_info(const LaunchCfg &cfg, const SweepArgs &a, int *lds_bytes, int *blocks_per_cu,
-                                  const char **name) {
-  (void)a;
-  int nb = 0;
-  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)pick(cfg), 64, 0);
-  if (e != hipSuccess) return e;
-  if (lds_bytes) *lds_bytes = 0;
-  if (blocks_per_cu) *blocks_per_cu = nb;
-  if (name) *name = cfg.precision == PSTAT_F64 ? (cfg.packed ? "cluster_kernel<double, state in memory> [packed cases]" : "cluster_kernel<double, state in memory>")
-                                                : (cfg.packed ? "cluster_kernel<float, state in memory> [packed cases]" : "cluster_kernel<float, state in memory>");
-  return hipSuccess;
-}
-
-hipError_t launch_cluster_gm(const LaunchCfg &cfg, const SweepArgs &a, const DevState &s, const CaseConst *cases,
-                             int *queue, unsigned grid, hipStream_t stream) {
-  hipError_t e = hipMemsetAsync(queue + 1, 0, sizeof(int) * (sweep_queue_ints(a) - 1), stream);   // queue[0]: sticky error word
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(pick(cfg), dim3(grid), dim3(64), 0, stream, a, s, cases, cfg.umbrella, queue);
-  return hipGetLastError();
+StepKernel cluster_gm_step_kernel(const LaunchCfg &cfg, int64_t) {
+  return {(const void *)pick(cfg), cfg.precision == PSTAT_F64 ? PSTAT_KERNEL_NAME(cfg, "cluster_kernel<double, state in memory>")
+                                                                : PSTAT_KERNEL_NAME(cfg, "cluster_kernel<float, state in memory>")};
 }
 
 }  // namespace pstat

@@ -406,27 +406,10 @@ WaveFn pick_wave_f32(const LaunchCfg &cfg, int64_t n) {
 #if !defined(PSTAT_WPART) || PSTAT_WPART == 2
 WaveFn pick_wave_f32(const LaunchCfg &cfg, int64_t n);
 
-static WaveFn pick_wave(const LaunchCfg &cfg, int64_t n) {
-  if (cfg.precision != PSTAT_F64) return pick_wave_f32(cfg, n);
-  return cfg.rng == PSTAT_RNG_XOSHIRO128PP ? pick_m<double, Xoshiro128pp>(cfg, n) : pick_m<double, Mwc64x>(cfg, n);
-}
-
-hipError_t launch_cluster_wave(const LaunchCfg &cfg, const SweepArgs &a, const DevState &s, const CaseConst *cases,
-                               hipStream_t stream) {
-  WaveFn fn = pick_wave(cfg, a.n);
-  hipLaunchKernelGGL(fn, dim3((unsigned)s.C), dim3(64), 0, stream, a, s, cases, cfg.umbrella,
-                     cfg.energy_type == PSTAT_CUTOFF ? 1 : 0);
-  return hipGetLastError();
-}
-
-hipError_t cluster_wave_kernel_info(const LaunchCfg &cfg, int64_t n, int *blocks_per_cu, const char **name) {
-  WaveFn fn = pick_wave(cfg, n);
-  int nb = 0;
-  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)fn, 64, 0);
-  if (e != hipSuccess) return e;
-  if (blocks_per_cu) *blocks_per_cu = nb;
-  if (name) *name = cfg.precision == PSTAT_F64 ? "cluster_wave_kernel<double>" : "cluster_wave_kernel<float>";
-  return hipSuccess;
+StepKernel cluster_wave_step_kernel(const LaunchCfg &cfg, int64_t n) {
+  if (cfg.precision != PSTAT_F64) return {(const void *)pick_wave_f32(cfg, n), "cluster_wave_kernel<float>"};
+  return {(const void *)(cfg.rng == PSTAT_RNG_XOSHIRO128PP ? pick_m<double, Xoshiro128pp>(cfg, n) : pick_m<double, Mwc64x>(cfg, n)),
+          "cluster_wave_kernel<double>"};
 }
 #endif
 

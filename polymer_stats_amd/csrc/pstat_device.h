@@ -279,7 +279,7 @@ enum Home {
   Interacting,       // fixed-force main with the all-pairs energy (pstat_interacting.hip)
 };
 
-// host-callable launchers implemented in pstat_kernels.hip; all asynchronous on `stream`
+// What pstat_api.hip chooses and reads once per handle; the host entry points below are asynchronous on `stream`.
 struct LaunchCfg {
   int precision, chain_type, energy_type, do_flips, umbrella, has_fx;
   int lag;  // a re-init has happened on this handle
@@ -288,24 +288,37 @@ struct LaunchCfg {
   Home home;     // the kernel family
   int packed;    // chain blocks straddle cases (SweepArgs::packed): the kernel instantiation with per-lane case scalars
 };
+
+struct SweepRare {  // wave-uniform switches of the sweep's rarely used options (RARE instantiations only)
+  int flips;        // --do-flips
+  int lag;          // a re-init happened: the acceptor's cached log-pi may be offset (see reinit_kernel)
+  int umb;          // --umbrella-sampling: AntiDipoleWeightFunction + UmbrellaAverager
+};
+
+// The instantiation that runs a handle's steps.  Each family file exports one function that resolves it for (cfg, n): the
+// only place its template tree is walked and its display name (pstat_launch_info.kernel) stated.  The handle keeps the
+// result; pstat_api.hip probes its occupancy and launches it.  Every step kernel takes (SweepArgs, DevState,
+// const CaseConst *) and then its family's scalars, listed with each function (launch_steps passes them).
+struct StepKernel {
+  const void *fn;
+  const char *name;
+};
+// the chain-per-lane kernels' name: the packed-cases instantiation says so
+#define PSTAT_KERNEL_NAME(cfg, s) ((cfg).packed ? s " [packed cases]" : s)
+StepKernel sweep_step_kernel(const LaunchCfg &cfg, int64_t n);         // homes SweepLds, SweepMem: SweepRare, int *queue
+StepKernel cluster_step_kernel(const LaunchCfg &cfg, int64_t n);       // ClusterLds: int umbrella, int *queue
+StepKernel cluster_gm_step_kernel(const LaunchCfg &cfg, int64_t n);    // ClusterMem: int umbrella, int *queue
+StepKernel cluster_cw_step_kernel(const LaunchCfg &cfg, int64_t n);    // ClusterChainWave (n <= 256): int umbrella
+StepKernel cluster_wave_step_kernel(const LaunchCfg &cfg, int64_t n);  // ClusterAllPairs (n <= 512): int umbrella, int cutoff
+StepKernel interacting_step_kernel(const LaunchCfg &cfg, int64_t n);   // Interacting (n <= 512): int do_flips, int lag, int reinit_mode
+// bytes of DevState::work for home ClusterMem
+size_t cluster_gm_work_bytes(const LaunchCfg &cfg, const SweepArgs &a);
+
+// initialisation, re-initialisation and reduction (pstat_kernels.hip)
 hipError_t launch_init(const LaunchCfg &cfg, const SweepArgs &a, const DevState &s,
                        const CaseConst *cases, double phi_step, double theta_step,
                        const InitOpts &io, hipStream_t stream);
 hipError_t launch_reset_sampler(const DevState &s, double phi_step, double theta_step, hipStream_t stream);
-// clustering main (pstat_cluster.hip): single-monomer move + cluster_flip! per step
-hipError_t launch_cluster(const LaunchCfg &cfg, const SweepArgs &a, const DevState &s,
-                          const CaseConst *cases, int *queue, unsigned grid, hipStream_t stream);
-hipError_t cluster_kernel_info(const LaunchCfg &cfg, const SweepArgs &a, int *lds_bytes,
-                               int *blocks_per_cu, const char **name);
-// the cluster kernel with its chains in DevState::work (home ClusterMem)
-hipError_t launch_cluster_gm(const LaunchCfg &cfg, const SweepArgs &a, const DevState &s,
-                             const CaseConst *cases, int *queue, unsigned grid, hipStream_t stream);
-hipError_t cluster_gm_kernel_info(const LaunchCfg &cfg, const SweepArgs &a, int *lds_bytes,
-                                  int *blocks_per_cu, const char **name);
-size_t cluster_gm_work_bytes(const LaunchCfg &cfg, const SweepArgs &a);
-hipError_t launch_sweep(const LaunchCfg &cfg, const SweepArgs &a, const DevState &s,
-                        const CaseConst *cases, int *queue, unsigned grid, hipStream_t stream);
-size_t sweep_queue_ints(const SweepArgs &a);
 hipError_t launch_reinit(const LaunchCfg &cfg, const SweepArgs &a, const DevState &s,
                          const CaseConst *cases, int force_init, hipStream_t stream);
 // true iff x is NaN or +-Inf (one v_cmp_class)
@@ -315,21 +328,5 @@ hipError_t launch_reduce(const DevState &s, int64_t c0, int64_t c1, int64_t step
                          int umbrella, const CaseConst *cases, int64_t chains_per_case, int64_t n,
                          double *partial, double *out, hipStream_t stream);
 size_t reduce_scratch_doubles();
-// LDS bytes and kernel attributes of the sweep kernel chosen for cfg
-hipError_t sweep_kernel_info(const LaunchCfg &cfg, const SweepArgs &a, int *lds_bytes,
-                             int *blocks_per_cu, const char **name);
-int choose_lanes(int precision, int64_t n, int energy_type);
-// --energy-type interacting: one chain per wavefront (pstat_interacting.hip), n <= 512
-hipError_t launch_interacting(const LaunchCfg &cfg, const SweepArgs &a, const DevState &s,
-                              const CaseConst *cases, int reinit_mode, hipStream_t stream);
-// clustering main with the all-pairs energies (interacting, cutoff): pstat_cluster_wave.hip
-hipError_t launch_cluster_wave(const LaunchCfg &cfg, const SweepArgs &a, const DevState &s, const CaseConst *cases,
-                               hipStream_t stream);
-hipError_t cluster_wave_kernel_info(const LaunchCfg &cfg, int64_t n, int *blocks_per_cu, const char **name);
-// clustering main, non-interacting / Ising, f64, small ensembles: one chain per wavefront (pstat_cluster_cw.hip)
-hipError_t launch_cluster_cw(const LaunchCfg &cfg, const SweepArgs &a, const DevState &s, const CaseConst *cases,
-                             hipStream_t stream);
-hipError_t cluster_cw_kernel_info(const LaunchCfg &cfg, int64_t n, int *blocks_per_cu, const char **name);
-hipError_t interacting_kernel_info(const LaunchCfg &cfg, int64_t n, int *blocks_per_cu, const char **name);
 
 }  // namespace pstat

@@ -430,27 +430,11 @@ InterFn pick_interacting_f32(const LaunchCfg &cfg, int64_t n);
 InterFn pick_interacting_f32_umb(const LaunchCfg &cfg, int64_t n);
 InterFn pick_interacting_f64_umb(const LaunchCfg &cfg, int64_t n);
 
-static InterFn pick_interacting(const LaunchCfg &cfg, int64_t n) {
-  if (cfg.precision != PSTAT_F64) return cfg.umbrella ? pick_interacting_f32_umb(cfg, n) : pick_interacting_f32(cfg, n);
-  return cfg.umbrella ? pick_interacting_f64_umb(cfg, n) : pick_interacting_ru<double, false>(cfg, n);
-}
-
-hipError_t launch_interacting(const LaunchCfg &cfg, const SweepArgs &a, const DevState &s,
-                              const CaseConst *cases, int reinit_mode, hipStream_t stream) {
-  InterFn fn = pick_interacting(cfg, a.n);
-  hipLaunchKernelGGL(fn, dim3((unsigned)s.C), dim3(64), 0, stream, a, s, cases, cfg.do_flips,
-                     (cfg.lag || reinit_mode) ? 1 : 0, reinit_mode);
-  return hipGetLastError();
-}
-
-hipError_t interacting_kernel_info(const LaunchCfg &cfg, int64_t n, int *blocks_per_cu, const char **name) {
-  InterFn fn = pick_interacting(cfg, n);
-  int nb = 0;
-  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)fn, 64, 0);
-  if (e != hipSuccess) return e;
-  if (blocks_per_cu) *blocks_per_cu = nb;
-  if (name) *name = cfg.precision == PSTAT_F64 ? "interacting_kernel<double>" : "interacting_kernel<float>";
-  return hipSuccess;
+StepKernel interacting_step_kernel(const LaunchCfg &cfg, int64_t n) {
+  if (cfg.precision != PSTAT_F64)
+    return {(const void *)(cfg.umbrella ? pick_interacting_f32_umb(cfg, n) : pick_interacting_f32(cfg, n)), "interacting_kernel<float>"};
+  return {(const void *)(cfg.umbrella ? pick_interacting_f64_umb(cfg, n) : pick_interacting_ru<double, false>(cfg, n)),
+          "interacting_kernel<double>"};
 }
 #endif
 

@@ -172,12 +172,6 @@ __device__ __forceinline__ Draw draw_step(G &g, uint32_t n, bool flips, uint32_t
   return d;
 }
 
-struct SweepRare {  // wave-uniform switches of the rarely used options (RARE instantiations only)
-  int flips;        // --do-flips
-  int lag;          // a re-init happened: the acceptor's cached log-pi may be offset (see reinit_kernel)
-  int umb;          // --umbrella-sampling: AntiDipoleWeightFunction + UmbrellaAverager
-};
-
 // One time-segment of one chain block: fill LDS/registers from HBM, run `nsteps` steps, spill.
 template <typename R, typename G, int CT, int EN, bool FX, bool RARE, int ST>
 __device__ __forceinline__ void run_segment(const SweepArgs &A, const DevState &S, const CaseConst &cc,
@@ -1157,60 +1151,12 @@ SweepFn pick_sweep_q16(const LaunchCfg &cfg);
 SweepFn pick_sweep_f64(const LaunchCfg &cfg);
 SweepFn pick_sweep_f64g(const LaunchCfg &cfg);
 
-static int cell_bytes(int precision) { return precision == PSTAT_F64 ? 16 : (precision == PSTAT_Q16 ? 4 : 8); }
-
-int choose_lanes(int precision, int64_t n, int energy_type) {
-  (void)energy_type;
-  const int64_t per_lane = n * cell_bytes(precision);
-  const int64_t budget = 160 * 1024;
-  for (int lanes = 64; lanes >= 8; lanes >>= 1)
-    if (per_lane * lanes <= budget) return lanes;
-  return 0;
-}
-
-static SweepFn pick_sweep(const LaunchCfg &cfg) {
-  if (cfg.home == SweepMem) return pick_sweep_f64g(cfg);
-  return cfg.precision == PSTAT_F64 ? pick_sweep_f64(cfg)
-       : (cfg.precision == PSTAT_Q16 ? pick_sweep_q16(cfg) : pick_sweep_f32(cfg));
-}
-
-static int sweep_lds_bytes(const LaunchCfg &cfg, const SweepArgs &a) {
-  if (cfg.home == SweepMem) return (a.lds_rows + 1) * 64 * 16;   // + the trash row
-  return (int)(a.n * a.lanes * cell_bytes(cfg.precision));
-}
-
-hipError_t sweep_kernel_info(const LaunchCfg &cfg, const SweepArgs &a, int *lds_bytes,
-                             int *blocks_per_cu, const char **name) {
-  SweepFn fn = pick_sweep(cfg);
-  const int lds = sweep_lds_bytes(cfg, a);
-  hipError_t e = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  if (e != hipSuccess) return e;
-  int nb = 0;
-  e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)fn, 64, lds);
-  if (e != hipSuccess) return e;
-  if (lds_bytes) *lds_bytes = lds;
-  if (blocks_per_cu) *blocks_per_cu = nb;
-  if (name) *name = cfg.precision == PSTAT_F64 ? (cfg.home == SweepMem ? (cfg.packed ? "sweep_kernel<double, state in L2> [packed cases]" : "sweep_kernel<double, state in L2>")
-                                                                   : (cfg.packed ? "sweep_kernel<double> [packed cases]" : "sweep_kernel<double>"))
-                 : (cfg.precision == PSTAT_Q16 ? (cfg.packed ? "sweep_kernel<float, q16 state> [packed cases]" : "sweep_kernel<float, q16 state>")
-                                               : (cfg.packed ? "sweep_kernel<float> [packed cases]" : "sweep_kernel<float>"));
-  return hipSuccess;
-}
-
-// queue layout: [0] error flag (sticky: never cleared by a launch), [1] job counter, [2 ..] per-block "segments done"
-size_t sweep_queue_ints(const SweepArgs &a) { return 2 + (size_t)a.nblocks; }
-
-hipError_t launch_sweep(const LaunchCfg &cfg, const SweepArgs &a, const DevState &s,
-                        const CaseConst *cases, int *queue, unsigned grid, hipStream_t stream) {
-  SweepFn fn = pick_sweep(cfg);
-  const int lds = sweep_lds_bytes(cfg, a);
-  hipError_t e = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  if (e != hipSuccess) return e;
-  e = hipMemsetAsync(queue + 1, 0, sizeof(int) * (sweep_queue_ints(a) - 1), stream);
-  if (e != hipSuccess) return e;
-  SweepRare rare{cfg.do_flips, cfg.lag, cfg.umbrella};
-  hipLaunchKernelGGL(fn, dim3(grid), dim3(64), lds, stream, a, s, cases, rare, queue);
-  return hipGetLastError();
+// cfg.lag, do_flips and umbrella select the RARE instantiation: a handle re-resolves when its lag changes (pstat_api.hip)
+StepKernel sweep_step_kernel(const LaunchCfg &cfg, int64_t) {
+  if (cfg.home == SweepMem) return {(const void *)pick_sweep_f64g(cfg), PSTAT_KERNEL_NAME(cfg, "sweep_kernel<double, state in L2>")};
+  if (cfg.precision == PSTAT_F64) return {(const void *)pick_sweep_f64(cfg), PSTAT_KERNEL_NAME(cfg, "sweep_kernel<double>")};
+  if (cfg.precision == PSTAT_Q16) return {(const void *)pick_sweep_q16(cfg), PSTAT_KERNEL_NAME(cfg, "sweep_kernel<float, q16 state>")};
+  return {(const void *)pick_sweep_f32(cfg), PSTAT_KERNEL_NAME(cfg, "sweep_kernel<float>")};
 }
 
 template <typename G>

@@ -83,6 +83,32 @@ def test_round_trip_and_every_mismatch_is_refused(ps):
             _refused(ps, batch2, bblob, "physics scalar")
 
 
+def test_an_image_taken_after_a_reinit_resumes_on_a_fresh_handle(ps):
+    """After pstat_reinit the acceptor's cached log-density is offset (the `lag` of reinit_kernel), the image says so, and
+    the f64 sweep then runs the instantiation that tracks it.  A fresh handle has never re-initialised: restoring such an
+    image must switch it over too, or its chains part from the original's at the first comparison that the offset decides.
+    Angles, generator words, counters and sums agree bit for bit -- the f64 sweep with its cells in LDS (n = 24) and in
+    memory (n = 100), and the all-pairs kernel."""
+    for name, kw in (("f64 sweep, cells in LDS", dict(BASE)),
+                     ("f64 sweep, cells in memory", dict(BASE, n=100)),
+                     ("interacting", dict(BASE, n=40, energy_type=1, K1=0.5))):
+        with ps.Ensemble(ps.default_params(**kw)) as a, ps.Ensemble(ps.default_params(**kw)) as b:
+            a.advance(300)
+            a.reinit(True)                   # forced: every chain adopts the draw, so every chain's cache is offset ...
+            a.advance(5)                     # ... and after five steps many still are
+            blob = a.checkpoint()
+            a.advance(400)
+            b.restore(blob)                  # b: created, never stepped, never re-initialised
+            b.advance(400)
+            for c in (0, 9, 63):
+                x, y = a.chain_state(c), b.chain_state(c)
+                for k in ("theta", "phi", "rng", "sums"):
+                    assert np.array_equal(x[k], y[k]), (name, c, k)
+                for k in ("nacc_total", "steps_recorded", "nacc_window", "natt_window", "phi_step", "theta_step", "normalizer"):
+                    assert x[k] == y[k], (name, c, k)
+            assert y["steps_recorded"] == 705, name
+
+
 def test_checkpoint_buffer_too_small_reports_the_size(ps):
     lib = ps._lib.load()
     with ps.Ensemble(ps.default_params(**BASE)) as e:

@@ -3,6 +3,9 @@ GLOBAL chains, whichever cases they belong to (run_job_queue<true>, csrc/pstat_d
 drivers need: one chain per case, 5-25 repeats (run/K1_E0-kT-phase.jl:19-45, run/interacting_dielectric_study.jl:37-47).
 The case's physics scalars then travel per lane (VGPRs) instead of per wave (SGPRs); nothing else may change: a chain's
 trajectory depends on its (seed, chain id) and its case's options, never on which lanes share its wave."""
+import json
+import os
+
 import numpy as np
 import pytest
 
@@ -141,6 +144,35 @@ def test_pstat_create_packs_when_it_shortens_the_launch_and_only_then(ps, monkey
         assert e.launch_info().packed_cases == 0
     with ps.Ensemble(grid(3000, 16, energy_type=ps.INTERACTING)[:40]) as e:    # all-pairs: a chain per wavefront, nothing to pack
         assert e.launch_info().packed_cases == 0
+
+
+def test_launch_shapes_are_those_of_the_recorded_library(ps, monkeypatch):
+    """tests/golden/launch_shapes.json: what pstat_launch_info_get answered for a table of configurations that reaches
+    every kernel family (both generators, the three precisions, batches that pack and that do not, n on both sides of 40, 64,
+    128 and 256, ensembles on both sides of the chain-per-wavefront bounds, handles after a re-init), recorded on an MI355X
+    by the library of the commit BEFORE the one that made a handle resolve its kernel once.  The expected values are that
+    library's, never this one's: kernel name, lanes, blocks, packing, LDS bytes and resident workgroups per CU all equal."""
+    for knob in ("F64_STATE", "F32_STATE", "PACK", "LANES", "F64_LDS_ROWS", "SEGMENTS", "MAX_SPINS"):
+        monkeypatch.delenv("PSTAT_" + knob, raising=False)
+    golden = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "launch_shapes.json")))
+    assert len(golden["shapes"]) >= 25
+    wrong = []
+    for rec in golden["shapes"]:
+        kw = rec["params"]
+        cases = [ps.default_params(**dict(kw, kT=1.0 + 0.01 * i, chain_id0=i * kw["num_chains"])) for i in range(rec["ncases"])]
+        with ps.Ensemble(cases) as e:
+            if rec["reinit"]:
+                e.advance(10)
+                e.reinit(False)
+                e.advance(10)
+                e.sync()
+            li = e.launch_info()
+            got = dict(kernel=li.kernel.decode(), lanes_per_block=li.lanes_per_block, blocks=li.blocks,
+                       packed_cases=li.packed_cases, lds_bytes=li.lds_bytes, blocks_per_cu=li.blocks_per_cu)
+        if got != rec["expect"]:
+            wrong.append((rec["name"], got, rec["expect"]))
+    assert not wrong, wrong
+    assert len({rec["expect"]["kernel"] for rec in golden["shapes"]}) >= 14     # the table's reach: families x packing
 
 
 def test_packed_f32_sweep_statistics_and_unpacked_agreement(ps, monkeypatch):
