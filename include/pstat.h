@@ -254,7 +254,7 @@ int pstat_microstate(pstat_handle *h, int64_t chain, double out[7]);
 
 /* The quantities printed at mcmc_eap_chain.jl:365,386-395.  Synchronises.  Like every accessor that
  * synchronises (pstat_sync, pstat_reduce_host, pstat_rolling, pstat_microstate, pstat_chain_state,
- * pstat_chain_extras, pstat_checkpoint) it fails with PSTAT_ERR_HIP if a launch since the last successful
+ * pstat_chain_extras, pstat_checkpoint, pstat_series_read) it fails with PSTAT_ERR_HIP if a launch since the last successful
  * call did not run to completion (a job of the persistent kernels timed out waiting for its predecessor):
  * the handle's averages are then not the averages of the steps it was asked for. */
 int pstat_summary_get(pstat_handle *h, int32_t icase, pstat_summary *out);
@@ -263,6 +263,35 @@ int pstat_summary_get(pstat_handle *h, int32_t icase, pstat_summary *out);
  * all-reduce over GPUs) into a summary.  Pure host arithmetic. */
 int pstat_summary_from_reduction(const double red[PSTAT_NRED], int64_t steps_per_chain,
                                  pstat_summary *out);
+
+/* The stepout time series (the rows of <prefix>_trajectory.csv and <prefix>_rolling.csv, mcmc_eap_chain.jl:329-348,
+ * mcmc_clustering_eap_chain.jl:312-335), recorded on the device for every case of the handle at once and read back in
+ * bulk.  A series belongs to the handle it was opened on; it is not part of a checkpoint, and pstat_destroy closes the
+ * ones still open.
+ *   pstat_series_open     device memory for `capacity_rows` rows of ncases * (PSTAT_NRED + 7 [+ 2n]) doubles.
+ *                         PSTAT_SERIES_ANGLES: rows also hold the angles of every case's first chain.  PSTAT_ERR_NOMEM if
+ *                         the device allocation fails.
+ *   pstat_advance_series  pstat_advance(h, nsteps) that appends a row after every `stepout`-th step counted from the start
+ *                         of the call (one small launch per row for all cases; a remainder nsteps % stepout is advanced
+ *                         and not recorded).  Asynchronous on the handle's stream.  The chains, generators, counters and
+ *                         running sums end up exactly as after pstat_advance.  If the rows would not fit it fails with
+ *                         PSTAT_ERR_TOO_SMALL before anything is enqueued.
+ *   pstat_series_read     the first `nrows` rows recorded (at most those recorded so far), host memory; synchronises, and
+ *                         fails like every accessor that does if a launch did not complete.  For row r and case k:
+ *                         steps_recorded[r] the steps every chain had recorded; red[r][k] the vector pstat_reduce_host(h, k)
+ *                         would have returned at that step; micro[r][k] what pstat_microstate(h, k * num_chains) would
+ *                         have; angles[r][k] the theta[n] then phi[n] of pstat_chain_state for that chain -- equal as
+ *                         doubles, each of them.  Any output pointer may be NULL (angles must be, without PSTAT_SERIES_ANGLES).
+ *   pstat_series_clear    forgets the rows, keeps the memory. */
+typedef struct pstat_series pstat_series;
+enum { PSTAT_SERIES_ANGLES = 1 };
+int pstat_series_open(pstat_handle *h, int64_t capacity_rows, int32_t flags, pstat_series **out);
+int pstat_advance_series(pstat_handle *h, pstat_series *s, int64_t nsteps, int64_t stepout);
+int pstat_series_read(pstat_handle *h, pstat_series *s, int64_t nrows, int64_t *steps_recorded /* [nrows] */,
+                      double *red /* [nrows][ncases][PSTAT_NRED] */, double *micro /* [nrows][ncases][7] */,
+                      double *angles /* [nrows][ncases][2n] */);
+int pstat_series_clear(pstat_handle *h, pstat_series *s);
+void pstat_series_close(pstat_handle *h, pstat_series *s);
 
 /* Per-chain accessors for tests and tooling (host buffers).  angles: theta[n] then phi[n] as
  * doubles, radians; sums: the 16 per-chain running sums in rolling.csv order;

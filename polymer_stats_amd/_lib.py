@@ -19,6 +19,7 @@ NX = 2
 NRED = 1 + 2 * NQ + NX
 MWC64X_MAX_CHAINS = 1 << 22
 MOVES_SINGLE, MOVES_CLUSTER = 0, 1
+SERIES_ANGLES = 1
 OBS_NAMES = ["r1", "r2", "r3", "r1sq", "r2sq", "r3sq", "rsq",
              "p1", "p2", "p3", "p1sq", "p2sq", "p3sq", "psq", "U", "Usq"]
 
@@ -29,6 +30,7 @@ SYMBOLS = [
     "pstat_reinit", "pstat_reset_averages", "pstat_set_kT", "pstat_scale_kT", "pstat_reset_sampler", "pstat_reduce_device", "pstat_reduce_host", "pstat_rolling", "pstat_microstate",
     "pstat_summary_get", "pstat_summary_from_reduction", "pstat_chain_state", "pstat_chain_extras", "pstat_restart_from_x0",
     "pstat_checkpoint", "pstat_restore", "pstat_launch_info_get", "pstat_chain_means",
+    "pstat_series_open", "pstat_advance_series", "pstat_series_read", "pstat_series_clear", "pstat_series_close",
 ]
 ABI_VERSION = 6
 
@@ -110,6 +112,12 @@ def load():
     L.pstat_restore.argtypes = [vp, vp, C.c_size_t]
     L.pstat_launch_info_get.argtypes = [vp, C.POINTER(LaunchInfo)]
     L.pstat_chain_means.argtypes = [vp, i32, dp]
+    L.pstat_series_open.argtypes = [vp, i64, i32, C.POINTER(vp)]
+    L.pstat_advance_series.argtypes = [vp, vp, i64, i64]
+    L.pstat_series_read.argtypes = [vp, vp, i64, C.POINTER(C.c_int64), dp, dp, dp]
+    L.pstat_series_clear.argtypes = [vp, vp]
+    L.pstat_series_close.argtypes = [vp, vp]
+    L.pstat_series_close.restype = None
     if L.pstat_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI version {L.pstat_abi_version()}, this binding needs {ABI_VERSION}: "
                           "rebuild it with `make -C polymer_stats_amd/csrc`")

@@ -108,6 +108,16 @@ struct pstat_handle {
   int64_t step_in_init = 0;         // the reference's loop variable `step` (mcmc_eap_chain.jl:276)
   size_t elem = 4;                  // sizeof(R)
   int failed_job = 0;               // sticky: 1 + the job of a persistent launch that timed out (0 = none)
+  std::vector<pstat_series *> series;   // series still open (pstat_destroy closes them)
+};
+
+// The stepout time series of one handle: rows recorded on the device by launch_record, read back in bulk.
+struct pstat_series {
+  int64_t capacity = 0, rows = 0;
+  double *d_red = nullptr;          // [capacity][ncases][PSTAT_NRED]
+  double *d_micro = nullptr;        // [capacity][ncases][7]
+  double *d_angles = nullptr;       // [capacity][ncases][2n], PSTAT_SERIES_ANGLES only
+  std::vector<int64_t> steps;       // [capacity]: the handle's steps_recorded at each row (known when the row is enqueued)
 };
 
 namespace {
@@ -459,6 +469,33 @@ int sync_checked(pstat_handle *h) {
   return PSTAT_OK;
 }
 
+// `nsteps` steps of every chain, in launches of at most 2^30 (per-launch step counters are 32-bit)
+int enqueue_steps(pstat_handle *h, int64_t nsteps) {
+  const int64_t max_launch = 1ll << 30;
+  while (nsteps > 0) {
+    const int64_t len = nsteps < max_launch ? nsteps : max_launch;
+    HIP_TRY(launch_steps(h, h->step_in_init, len));
+    h->step_in_init += len;
+    h->steps_recorded += len;
+    nsteps -= len;
+  }
+  return PSTAT_OK;
+}
+
+// the series if it is one of the handle's open ones
+pstat_series *own_series(pstat_handle *h, pstat_series *s) {
+  for (pstat_series *mine : h->series)
+    if (mine == s) return s;
+  return nullptr;
+}
+
+void free_series(pstat_series *s) {
+  (void)hipFree(s->d_red);
+  (void)hipFree(s->d_micro);
+  (void)hipFree(s->d_angles);
+  delete s;
+}
+
 int reduce_to_host(pstat_handle *h, int icase, double red[PSTAT_NRED]) {
   int rc = pstat_reduce_device(h, icase, h->d_red);
   if (rc) return rc;
@@ -660,6 +697,7 @@ void pstat_destroy(pstat_handle *h) {
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   for (auto &b : h->bufs) (void)hipFree(b.ptr);
+  for (pstat_series *s : h->series) free_series(s);
   if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }
@@ -671,15 +709,102 @@ int pstat_advance(pstat_handle *h, int64_t nsteps) {
   int rc = set_device(h);
   if (rc) return rc;
   if (h->failed_job) return report_failed_job(h);
-  const int64_t max_launch = 1ll << 30;  // per-launch step counters are 32-bit
-  while (nsteps > 0) {
-    const int64_t len = nsteps < max_launch ? nsteps : max_launch;
-    HIP_TRY(launch_steps(h, h->step_in_init, len));
-    h->step_in_init += len;
-    h->steps_recorded += len;
-    nsteps -= len;
+  return enqueue_steps(h, nsteps);
+}
+
+int pstat_series_open(pstat_handle *h, int64_t capacity_rows, int32_t flags, pstat_series **out) {
+  if (!h || !out) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
+  *out = nullptr;
+  if (capacity_rows < 1) return fail(PSTAT_ERR_INVALID_ARG, "capacity_rows must be >= 1");
+  if (flags & ~PSTAT_SERIES_ANGLES) return fail(PSTAT_ERR_INVALID_ARG, "unknown series flags %d", flags);
+  const size_t cases = (size_t)h->ncases, n2 = 2 * (size_t)h->base.n;
+  const size_t row_doubles = cases * (PSTAT_NRED + 7 + ((flags & PSTAT_SERIES_ANGLES) ? n2 : 0));
+  if ((uint64_t)capacity_rows > (SIZE_MAX / sizeof(double)) / row_doubles)
+    return fail(PSTAT_ERR_NOMEM, "a series of %lld rows does not fit the address space", (long long)capacity_rows);
+  PSTAT_TRY(set_device(h));
+  pstat_series *s = new (std::nothrow) pstat_series;
+  if (!s) return fail(PSTAT_ERR_NOMEM, "host allocation failed");
+  const size_t rows = (size_t)capacity_rows;
+  const struct { double **p; size_t doubles; } parts[] = {
+      {&s->d_red, rows * cases * PSTAT_NRED},
+      {&s->d_micro, rows * cases * 7},
+      {&s->d_angles, (flags & PSTAT_SERIES_ANGLES) ? rows * cases * n2 : 0},
+  };
+  for (const auto &b : parts) {
+    if (!b.doubles) continue;
+    hipError_t e = hipMalloc((void **)b.p, b.doubles * sizeof(double));
+    if (e != hipSuccess) {
+      free_series(s);
+      return fail(PSTAT_ERR_NOMEM, "hipMalloc(%zu) failed: %s", b.doubles * sizeof(double), hipGetErrorString(e));
+    }
   }
+  try {
+    s->steps.resize(rows);
+    h->series.push_back(s);
+  } catch (const std::bad_alloc &) {
+    free_series(s);
+    return fail(PSTAT_ERR_NOMEM, "host allocation failed");
+  }
+  s->capacity = capacity_rows;
+  *out = s;
   return PSTAT_OK;
+}
+
+int pstat_advance_series(pstat_handle *h, pstat_series *s, int64_t nsteps, int64_t stepout) {
+  if (!h || !s) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
+  if (!own_series(h, s)) return fail(PSTAT_ERR_INVALID_ARG, "the series is not an open series of this handle");
+  if (nsteps < 0) return fail(PSTAT_ERR_INVALID_ARG, "nsteps must be >= 0");
+  if (stepout < 1) return fail(PSTAT_ERR_INVALID_ARG, "stepout must be >= 1");
+  const int64_t nrows = nsteps / stepout;
+  if (nrows > s->capacity - s->rows)
+    return fail(PSTAT_ERR_TOO_SMALL, "the series has %lld of %lld rows free, this call would record %lld",
+                (long long)(s->capacity - s->rows), (long long)s->capacity, (long long)nrows);
+  PSTAT_TRY(set_device(h));
+  if (h->failed_job) return report_failed_job(h);
+  const size_t cases = (size_t)h->ncases, n2 = 2 * (size_t)h->base.n;
+  for (int64_t i = 0; i < nrows; ++i) {
+    PSTAT_TRY(enqueue_steps(h, stepout));
+    const size_t row = (size_t)s->rows;
+    HIP_TRY(launch_record(h->cfg, h->args, h->S, h->d_cases, h->steps_recorded, s->d_red + row * cases * PSTAT_NRED,
+                          s->d_micro + row * cases * 7, s->d_angles ? s->d_angles + row * cases * n2 : nullptr, h->stream));
+    s->steps[row] = h->steps_recorded;
+    s->rows += 1;
+  }
+  return enqueue_steps(h, nsteps - nrows * stepout);
+}
+
+int pstat_series_read(pstat_handle *h, pstat_series *s, int64_t nrows, int64_t *steps_recorded, double *red, double *micro,
+                      double *angles) {
+  if (!h || !s) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
+  if (!own_series(h, s)) return fail(PSTAT_ERR_INVALID_ARG, "the series is not an open series of this handle");
+  if (nrows < 0 || nrows > s->rows)
+    return fail(PSTAT_ERR_INVALID_ARG, "%lld rows asked for, %lld recorded", (long long)nrows, (long long)s->rows);
+  if (angles && !s->d_angles) return fail(PSTAT_ERR_INVALID_ARG, "the series was opened without PSTAT_SERIES_ANGLES");
+  PSTAT_TRY(set_device(h));
+  PSTAT_TRY(sync_checked(h));
+  const size_t rows = (size_t)nrows, cases = (size_t)h->ncases, n2 = 2 * (size_t)h->base.n;
+  if (!rows) return PSTAT_OK;
+  if (steps_recorded) std::memcpy(steps_recorded, s->steps.data(), rows * sizeof(int64_t));
+  if (red) HIP_TRY(hipMemcpy(red, s->d_red, rows * cases * PSTAT_NRED * sizeof(double), hipMemcpyDeviceToHost));
+  if (micro) HIP_TRY(hipMemcpy(micro, s->d_micro, rows * cases * 7 * sizeof(double), hipMemcpyDeviceToHost));
+  if (angles) HIP_TRY(hipMemcpy(angles, s->d_angles, rows * cases * n2 * sizeof(double), hipMemcpyDeviceToHost));
+  return PSTAT_OK;
+}
+
+int pstat_series_clear(pstat_handle *h, pstat_series *s) {
+  if (!h || !s) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
+  if (!own_series(h, s)) return fail(PSTAT_ERR_INVALID_ARG, "the series is not an open series of this handle");
+  s->rows = 0;   // later rows are enqueued behind whatever still writes the old ones
+  return PSTAT_OK;
+}
+
+void pstat_series_close(pstat_handle *h, pstat_series *s) {
+  if (!h || !s || !own_series(h, s)) return;
+  (void)hipSetDevice(h->device);
+  (void)hipStreamSynchronize(h->stream);   // rows may still be in flight
+  for (size_t i = 0; i < h->series.size(); ++i)
+    if (h->series[i] == s) { h->series.erase(h->series.begin() + (long)i); break; }
+  free_series(s);
 }
 
 int pstat_sync(pstat_handle *h) {

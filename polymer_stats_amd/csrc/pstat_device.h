@@ -328,5 +328,10 @@ hipError_t launch_reduce(const DevState &s, int64_t c0, int64_t c1, int64_t step
                          int umbrella, const CaseConst *cases, int64_t chains_per_case, int64_t n,
                          double *partial, double *out, hipStream_t stream);
 size_t reduce_scratch_doubles();
+// one row of a series (pstat_series.hip): for every case k of the handle, red[k][PSTAT_NRED] = what launch_reduce gives for
+// the case's chains, micro[k][7] = obs of the case's first chain, and, unless angles is null, angles[k][2n] = that chain's
+// theta then phi in radians
+hipError_t launch_record(const LaunchCfg &cfg, const SweepArgs &a, const DevState &s, const CaseConst *cases,
+                         int64_t steps_recorded, double *red, double *micro, double *angles, hipStream_t stream);
 
 }  // namespace pstat

@@ -76,6 +76,18 @@ class Ensemble:
         """kT of every case <- its creation-time kT * mult (one rung of the burn-in ladder for a grid)."""
         check(self._L.pstat_scale_kT(self._h, float(mult)))
 
+    # --- the stepout time series, recorded on the device
+    def open_series(self, capacity_rows: int, angles: bool = False) -> "Series":
+        """Device memory for `capacity_rows` rows; `angles`: rows also hold every case's first chain's angles."""
+        s = C.c_void_p()
+        check(self._L.pstat_series_open(self._h, int(capacity_rows), _lib.SERIES_ANGLES if angles else 0, C.byref(s)))
+        return Series(self, s, bool(angles))
+
+    def advance_series(self, series: "Series", nsteps: int, stepout: int):
+        """advance(nsteps) that appends a row to `series` after every `stepout`-th step (asynchronous)."""
+        check(self._L.pstat_advance_series(self._h, series._s, int(nsteps), int(stepout)))
+        series.rows += int(nsteps) // int(stepout)
+
     # --- read-outs
     def reduce_into(self, dev_ptr: int, icase: int = -1):
         """Device-side reduction into a caller-owned device buffer of NRED doubles (async)."""
@@ -147,6 +159,36 @@ class Ensemble:
         info = LaunchInfo()
         check(self._L.pstat_launch_info_get(self._h, C.byref(info)))
         return info
+
+
+class Series:
+    """Rows recorded by Ensemble.advance_series (pstat_series_*); `rows` counts them."""
+
+    def __init__(self, ensemble: Ensemble, s, angles: bool):
+        self._e, self._s, self.angles, self.rows = ensemble, s, angles, 0
+
+    def read(self, nrows: int | None = None):
+        """(steps[rows], red[rows, ncases, NRED], micro[rows, ncases, 7], angles[rows, ncases, 2n] or None) of the first
+        `nrows` rows (default: all recorded).  Synchronises."""
+        e = self._e
+        r = self.rows if nrows is None else int(nrows)
+        steps = np.zeros(r, dtype=np.int64)
+        red = np.zeros((r, e.ncases, NRED))
+        micro = np.zeros((r, e.ncases, 7))
+        ang = np.zeros((r, e.ncases, 2 * e.n)) if self.angles else None
+        dp = C.POINTER(C.c_double)
+        check(e._L.pstat_series_read(e._h, self._s, r, steps.ctypes.data_as(C.POINTER(C.c_int64)), red.ctypes.data_as(dp),
+                                     micro.ctypes.data_as(dp), ang.ctypes.data_as(dp) if self.angles else None))
+        return steps, red, micro, ang
+
+    def clear(self):
+        check(self._e._L.pstat_series_clear(self._e._h, self._s))
+        self.rows = 0
+
+    def close(self):
+        if self._s and self._e._h:      # (closing the ensemble closes its series)
+            self._e._L.pstat_series_close(self._e._h, self._s)
+        self._s = None
 
 
 def summary_from_reduction(red: Iterable[float], steps_per_chain: int) -> Summary:

@@ -194,26 +194,22 @@ def _stage(pool, nsteps, mult, write: bool):
     try:
         if write:
             files = CsvFiles([p["prefix"] for p in plist], [traj_header(p["num-monomers"]) for p in plist], ROLL_HEADER)
-        start = last_update = time.time()
-        step = 0
-        while step < nsteps:
-            seg = nsteps - step
-            if stepout > 0:
-                seg = min(seg, stepout - step % stepout)
-            pool.advance(seg)
-            step += seg
-            if time.time() - last_update > pargs["update-freq"]:        # :280-284
+        start = time.time()
+        last_update = [start]
+
+        def tick(step):                                                 # :280-284 (per chunk of rows)
+            if time.time() - last_update[0] > pargs["update-freq"]:
                 _log(pargs, 3, "Info", f"elapsed: {time.time() - start}")
                 _log(pargs, 3, "Info", f"step:    {step} / {nsteps}")
-                last_update = time.time()
-            if stepout > 0 and step % stepout == 0:                     # :312-335
-                for k in range(len(files) if files else 0):
-                    micro = pool.microstate(k)
-                    st = pool.chain0(k)
-                    mus = _dipoles(plist[k], st["phi"], st["theta"])
-                    angles = np.stack([st["phi"], st["theta"]], axis=1).reshape(-1)
-                    s = pool.summary(k)
-                    files.rows(k, jl_row([step, *micro, *angles, *mus.reshape(-1)]), jl_row([step, *s.avg, *s.extra_avg]))
+                last_update[0] = time.time()
+        for step, micro, ang, sums in pool.recorded(nsteps, stepout, angles=True, tick=tick):   # rows :312-335
+            for k in range(len(files)):
+                n = plist[k]["num-monomers"]
+                theta, phi = ang[k][:n], ang[k][n:]
+                mus = _dipoles(plist[k], phi, theta)
+                angles = np.stack([phi, theta], axis=1).reshape(-1)
+                files.rows(k, jl_row([step, *micro[k], *angles, *mus.reshape(-1)]),
+                           jl_row([step, *sums[k].avg, *sums[k].extra_avg]))
         out = [pool.summary(k) for k in range(len(plist))]
         _log(pargs, 3, "Info", f"total time elapsed: {time.time() - start}")
         for k, s in enumerate(out):

@@ -29,6 +29,10 @@ from . import _lib
 from .ensemble import Ensemble, summary_from_reduction
 from .julia_fmt import jl_float, jl_row, jl_vector
 
+# Device memory one handle's series may take: the rows of a recorded run are read back and written out in chunks of
+# as many rows as fit (a row is ncases x (NRED + 7 [+ 2n]) doubles; at least one row per chunk).
+SERIES_BUDGET_BYTES = 256 << 20
+
 TRAJ_HEADER = "step,r1,r2,r3,p1,p2,p3,U"
 ROLL_HEADER = "step,r1,r2,r3,r1sq,r2sq,r3sq,rsq,p1,p2,p3,p1sq,p2sq,p3sq,psq,U,Usq"
 
@@ -238,6 +242,57 @@ class _Pool:
             e.reset_averages()
         self.steps = 0
 
+    def recorded(self, nsteps, stepout, angles=False, tick=None):
+        """advance(nsteps), yielding after every `stepout`-th step (step, micro, ang, summaries): per case the microstate
+        [7] of its first chain, with `angles` that chain's theta[n] then phi[n], and its pooled summary.  The rows are
+        recorded on the device for all cases at once (Ensemble.advance_series) and come back a chunk at a time: shard
+        vectors are added as in summary(), the microstate is shard 0's.  `tick(step)` is called once per chunk.
+        --numeric-type other than float64 needs every chain's means at every row (summary()): it takes the per-row calls."""
+        ncases = len(self.plist)
+        nrows = nsteps // stepout if stepout > 0 else 0
+        if self.numeric_type != "float64":
+            for r in range(1, nrows + 1):
+                self.advance(stepout)
+                if tick:
+                    tick(r * stepout)
+                st = [self.chain0(k) for k in range(ncases)] if angles else None
+                yield (r * stepout, [self.microstate(k) for k in range(ncases)],
+                       [np.concatenate([c["theta"], c["phi"]]) for c in st] if angles else None,
+                       [self.summary(k) for k in range(ncases)])
+        elif nrows:
+            n = self.parts[0].n
+            row_bytes = 8 * ncases * (_lib.NRED + 7 + (2 * n if angles else 0))
+            chunk = min(nrows, max(1, SERIES_BUDGET_BYTES // row_bytes))
+            series = [e.open_series(chunk, angles=angles and i == 0) for i, e in enumerate(self.parts)]
+            try:
+                done = 0
+                while done < nrows:
+                    m = min(chunk, nrows - done)
+                    for e, s in zip(self.parts, series):
+                        e.advance_series(s, m * stepout, stepout)      # asynchronous: the devices run concurrently
+                    self.steps += m * stepout
+                    reads = [s.read() for s in series]
+                    for s in series:
+                        s.clear()
+                    steps, _, micro, ang = reads[0]
+                    red = np.zeros((m, ncases, _lib.NRED))
+                    for rd in reads:
+                        red += rd[1]
+                    if tick:
+                        tick((done + m) * stepout)
+                    for r in range(m):
+                        yield ((done + r + 1) * stepout, micro[r], ang[r] if angles else None,
+                               [summary_from_reduction(red[r, k], int(steps[r])) for k in range(ncases)])
+                    done += m
+            finally:
+                for s in series:
+                    s.close()
+        rest = nsteps - nrows * stepout      # not recorded
+        if rest > 0:
+            self.advance(rest)
+            if tick:
+                tick(nsteps)
+
     def chain0(self, k=0):
         return self.parts[0].chain_state(k * self.counts[0])      # the first chain of case k
 
@@ -344,7 +399,8 @@ def mcmc(nsteps: int, pargs: dict):
 def mcmc_cases(nsteps: int, plist: list, write_csv: bool = True, info: dict | None = None) -> list:
     """mcmc(nsteps, pargs) for every case of `plist` at once -- parsed options that differ only in their physics scalars,
     prefix and seed (one case: the command line; many: a sweep, polymer_stats_amd/sweep.py) -- as ONE ensemble: one launch
-    per segment for all of them.  `write_csv=False` skips the two CSV files of every case (then one launch per init)."""
+    per init for all of them, or, with the two CSV files of every case (`write_csv`), one per --stepout steps followed by the
+    launch that records the row of every case on the device (_Pool.recorded)."""
     pargs = plist[0]
     if pargs["acc"] != "metropolis":
         raise ReferenceError_(f"'{pargs['acc']}' acceptance criteria has not yet been implemented.")  # :184
@@ -362,25 +418,18 @@ def mcmc_cases(nsteps: int, plist: list, write_csv: bool = True, info: dict | No
             pool.burn_in(int(pargs["burn-in"]), ladder or [1.0])
         if write_csv:                                # :256-259
             files = CsvFiles([p["prefix"] for p in plist], [TRAJ_HEADER] * len(plist), ROLL_HEADER)
-        start = last_update = time.time()
+        start = time.time()
+        last_update = [start]
         for init in range(1, pargs["num-inits"] + 1):           # :266
-            step = 0
-            while step < nsteps:                                # :276 (in segments)
-                seg = nsteps - step
-                if stepout > 0:
-                    seg = min(seg, stepout - step % stepout)
-                pool.advance(seg)
-                step += seg
-                if time.time() - last_update > pargs["update-freq"]:   # :294-299
+            def tick(step):                                     # :294-299 (per chunk of rows)
+                if time.time() - last_update[0] > pargs["update-freq"]:
                     _log(pargs, 3, "Info", f"elapsed: {time.time() - start}")
                     _log(pargs, 3, "Info", f"init:    {init} / {pargs['num-inits']}")
                     _log(pargs, 3, "Info", f"step:    {step} / {nsteps}")
-                    last_update = time.time()
-                if stepout > 0 and step % stepout == 0:          # :329-348
-                    for k in range(len(files) if files else 0):
-                        micro = pool.microstate(k)
-                        s = pool.summary(k)
-                        files.rows(k, jl_row([step, *micro]), jl_row([step, *s.avg]))
+                    last_update[0] = time.time()
+            for step, micro, _, sums in pool.recorded(nsteps, stepout, tick=tick):   # :276, rows :329-348
+                for k in range(len(files)):
+                    files.rows(k, jl_row([step, *micro[k]]), jl_row([step, *sums[k].avg]))
             if init < pargs["num-inits"]:                        # :352-361
                 pool.reinit(bool(pargs["force-init"]))
         out = [pool.summary(k) for k in range(len(plist))]

@@ -216,7 +216,8 @@ def run_sweep(main_name: str, fixed_argv: list[str], cases: list[dict], workdir:
               seed: int | None = None, precision: str | None = None, rng: str | None = None, rank: int = 0, world: int = 1,
               device: int = 0, overwrite: bool = False, write_csv: bool = False, max_chains: int = 262144, log=None) -> dict:
     """Runs the cases whose `.out` does not exist yet (run/interacting_dielectric_study.jl:39) and that fall to this rank
-    (position in the full case list modulo `world`).  Returns {"ran": [...], "skipped": [...], "launches": k}."""
+    (position in the full case list modulo `world`).  `write_csv` also writes every case's two time-series files (rows
+    recorded on the device for the whole ensemble, _Pool.recorded).  Returns {"ran": [...], "skipped": [...], "launches": k}."""
     main = MAINS[main_name]
     os.makedirs(workdir, exist_ok=True)
     todo_all = plan(main_name, fixed_argv, cases, workdir, name=name, num_chains=num_chains, seed=seed, precision=precision,

@@ -47,7 +47,8 @@ def main():
     ap.add_argument("--gpus", type=int, default=1, help="ranks; > 1 from a bare shell starts them (one per GPU)")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal: ranks beyond the visible GPUs share them")
     ap.add_argument("--overwrite", action="store_true")
-    ap.add_argument("--csv", action="store_true", help="also write every case's _trajectory.csv and _rolling.csv (launches split at --stepout)")
+    ap.add_argument("--csv", action="store_true", help="also write every case's _trajectory.csv and _rolling.csv, one row per --stepout steps: the rows of all cases are "
+                         "recorded on the device by one launch each and read back in chunks (formatting their text is then the larger part of a big run)")
     ap.add_argument("--max-chains", type=int, default=262144, help="chains per launch (cases per ensemble = this / num-chains)")
     ap.add_argument("--dry-run", action="store_true", help="print the plan (cases, file names, ensembles) and stop: no GPU needed")
     ap.add_argument("--aggregate", default="", help="afterwards write scripts/aggregate_mcmc.jl's CSV of the whole directory here")
