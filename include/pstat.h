@@ -204,6 +204,43 @@ void pstat_default_params(pstat_params *p);
 int pstat_create(const pstat_params *cases, int32_t ncases, void *stream, pstat_handle **out);
 void pstat_destroy(pstat_handle *h);
 
+/* The planar main, 2D/mcmc_clustering_eap_chain.jl: same pstat_params, same handle type.
+ * A planar chain has ONE angle per monomer, n_i = (cos phi_i, sin phi_i); the field and Fz act on the second component,
+ * Fx on the first (2D/inc/energy.jl:8, 2D/inc/eap_chain.jl:64); the target density has no sin(theta) Jacobian
+ * (2D/inc/acceptance.jl:18-22).  One step = the single-monomer move phi_idx += dphi followed, on the trial chain, by
+ * cluster_flip! (2D/inc/eap_chain.jl:194-257): with probability cluster_prob the cluster grown from the moved monomer is
+ * inverted (phi_i += pi for every member), accepted by Metropolis-Hastings with the ratio alpha of its boundary links.
+ * Replaces `chain = EAPChain(pargs)` (2D/mcmc_clustering_eap_chain.jl:151; phi ~ U(0, 2 pi)) and, through pstat_advance,
+ * the step loop :238-278.  The reference's burn-in ladder (:323-336) has no effect on any of its outputs -- mcmc(nsteps,
+ * pargs, chain) overwrites the chain it is handed on its first line -- so one run of that main is: pstat_create_planar,
+ * pstat_advance(num-steps).  (A host that WANTS the ladder carries the chains through it with pstat_scale_kT,
+ * pstat_reset_sampler and pstat_reset_averages, as the 3D clustering main does.)
+ *
+ * The planar observables are the 3D 16-vectors with component 1 in the x slots and component 2 in the z slots -- what the
+ * reference's CSV headers call r1, r3 -- and every y entry (r2, r2sq, p2, p2sq) exactly 0; extra_avg (sum cos^2 theta,
+ * <psi>) stays 0: the planar main has no such averagers.
+ *
+ * How pstat_params is read for a planar handle:
+ *   read     E0, K1, K2, mu, kT, Fz, Fx, b, phi_step, adj_lb, adj_ub, adj_scale, steps_per_adjust, n, num_chains, seed,
+ *            chain_id0, chain_type, energy_type, umbrella, precision, device, rng, uniform_bits, and cluster_prob -- here
+ *            the probability OF flipping the cluster (2D/mcmc_clustering_eap_chain.jl:71-74), where the 3D clustering main
+ *            reads it as the probability of not trying.  Under uniform_bits = 53 the low 21 bits of eps are the low 9 bits
+ *            of the step's dphi word, the low 9 of its flip word and the low 3 of its index word.
+ *   must be at their pstat_default_params values, else PSTAT_ERR_INVALID_ARG naming the field: do_flips, bend_mod,
+ *            bend_angle, use_x0 (the planar main has no such options).
+ *   ignored  theta_step, x0_*, dx0_*, cutoff_radius, move_set (a planar handle always runs the combined move).
+ *   NB pstat_default_params keeps the 3D defaults: the planar main's --step-adjust-ub is 0.40, not 0.55; setting it is
+ *   the caller's business.
+ * PSTAT_ERR_UNSUPPORTED: precision other than PSTAT_F64; energy_type PSTAT_INTERACTING (planar all-pairs); n > 2 560 (8-byte
+ * cells of eight chains must fit a CU's LDS).  PSTAT_CUTOFF is PSTAT_ERR_INVALID_ARG: the planar main has no such energy.
+ * Every accessor works on a planar handle.  pstat_microstate: [r1, 0, r3, p1, 0, p3, U]; pstat_chain_state and series rows:
+ * angles = n zeros, then phi[n]; steps = {phi_step, 0, normalizer}; pstat_chain_extras: zeros.  pstat_reinit and
+ * pstat_restart_from_x0 return PSTAT_ERR_UNSUPPORTED (the planar main has neither --num-inits nor --x0).  A checkpoint
+ * of a planar handle is refused by a handle of pstat_create and the reverse (PSTAT_ERR_BAD_CHECKPOINT).
+ * Umbrella sampling uses the rising gauge of pstat_chain_state's normalizer: value / normalizer is what the reference's
+ * a-priori gauge (2D/inc/average.jl:110-118) gives wherever that is finite. */
+int pstat_create_planar(const pstat_params *cases, int32_t ncases, void *stream, pstat_handle **out);
+
 /* Replaces `nsteps` iterations of the step loop, mcmc_eap_chain.jl:276-328, for every chain:
  * proposal draw (:277-280), move! (inc/eap_chain.jl:230-257), energy (inc/energy.jl:7-23),
  * Metropolis (inc/acceptance.jl:29-39), step-size adaptation (:301-322), record! x 8 (:327-328).

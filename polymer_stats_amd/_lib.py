@@ -22,6 +22,10 @@ MOVES_SINGLE, MOVES_CLUSTER = 0, 1
 SERIES_ANGLES = 1
 OBS_NAMES = ["r1", "r2", "r3", "r1sq", "r2sq", "r3sq", "rsq",
              "p1", "p2", "p3", "p1sq", "p2sq", "p3sq", "psq", "U", "Usq"]
+# the planar main's rolling.csv columns after "step" (2D/mcmc_clustering_eap_chain.jl:230) and where each sits in the
+# 16-vector: component 1 in the x slots, component 2 in the z slots, the y slots exactly 0
+PLANAR_OBS_NAMES = ["r1", "r3", "r1sq", "r3sq", "rsq", "p1", "p3", "p1sq", "p3sq", "psq", "U", "Usq"]
+PLANAR_OBS_INDEX = [OBS_NAMES.index(k) for k in PLANAR_OBS_NAMES]
 
 # every symbol include/pstat.h declares (tests check the built library exports all of them)
 SYMBOLS = [
@@ -31,6 +35,7 @@ SYMBOLS = [
     "pstat_summary_get", "pstat_summary_from_reduction", "pstat_chain_state", "pstat_chain_extras", "pstat_restart_from_x0",
     "pstat_checkpoint", "pstat_restore", "pstat_launch_info_get", "pstat_chain_means",
     "pstat_series_open", "pstat_advance_series", "pstat_series_read", "pstat_series_clear", "pstat_series_close",
+    "pstat_create_planar",
 ]
 ABI_VERSION = 6
 
@@ -90,6 +95,7 @@ def load():
     L.pstat_default_params.argtypes = [C.POINTER(Params)]
     L.pstat_default_params.restype = None
     L.pstat_create.argtypes = [C.POINTER(Params), i32, vp, C.POINTER(vp)]
+    L.pstat_create_planar.argtypes = [C.POINTER(Params), i32, vp, C.POINTER(vp)]
     L.pstat_destroy.argtypes = [vp]
     L.pstat_destroy.restype = None
     L.pstat_advance.argtypes = [vp, i64]
@@ -139,3 +145,9 @@ def default_params(**kw) -> Params:
             raise KeyError(k)
         setattr(p, k, v)
     return p
+
+
+def default_planar_params(**kw) -> Params:
+    """Option defaults of the planar main (2D/mcmc_clustering_eap_chain.jl:15-129) for Ensemble(..., planar=True): those of
+    default_params except --step-adjust-ub 0.40."""
+    return default_params(**{"adj_ub": 0.40, **kw})

@@ -7,8 +7,10 @@ read out of the file NAME (`E0-0001000_K1-...`: the text after the first `-` of 
 scripts/aggregate_mcmc.jl:69; with runflag the last token is dropped, :63-65) followed by the values right of the `=` of
 every line, vectors flattened (:71).  Numbers are written the way Julia's writedlm prints Float64 (shortest round-trip).
 The header names the 22 output columns of the clustering main's twelve lines; a file of the fixed-force main's ten lines
-gives 20 values and the header drops Ealign and psi (scripts/aggregate_mcmc_legacy.jl).  The planar (2D) variant of the
-reference is outside this implementation."""
+gives 20 values and the header drops Ealign and psi (scripts/aggregate_mcmc_legacy.jl).  A file of the planar main's ten
+lines (2-element vectors: 15 values, polymer_stats_amd.mcmc_clustering_eap_chain_2d) is recognised by that count and gets
+the reference's planar header (scripts/aggregate_mcmc.jl:56); the explicit `2D` argument of the reference's script, which
+there also switches how it globs, is not taken."""
 from __future__ import annotations
 
 import fnmatch
@@ -19,6 +21,7 @@ from .julia_fmt import jl_row
 
 OUT_3D = ["r1", "r2", "r3", "lambda1", "lambda2", "lambda3", "r1sq", "r2sq", "r3sq", "rsquared", "p1", "p2", "p3", "p1sq",
           "p2sq", "p3sq", "psquared", "U", "Usquared", "Ealign", "psi", "AR"]
+OUT_2D = ["r1", "r2", "lambda1", "lambda2", "r1sq", "r2sq", "rsquared", "p1", "p2", "p1sq", "p2sq", "psquared", "U", "Usquared", "AR"]
 USAGE = "usage: julia aggregate.jl <outfile> <indir> <pattern> <dielectric|polar> [<3D|2D>] [<kappaflag>] [<runflag>]"
 
 
@@ -71,6 +74,8 @@ def aggregate(outfile: str, indir: str, pattern: str, chain: str, kappaflag: boo
                   "misaligned", file=sys.stderr)
             return 1
     cols = OUT_3D if not rows or len(rows[0][2]) == len(OUT_3D) else [c for c in OUT_3D if c not in ("Ealign", "psi")]
+    if rows and len(rows[0][2]) == len(OUT_2D):       # the planar main's ten lines
+        cols = OUT_2D
     with open(outfile, "w") as out:
         out.write(",".join(heads + cols) + "\n")
         for f, fields, vals in rows:
@@ -85,7 +90,7 @@ def main(argv=None) -> int:
         print(USAGE)
         return 1
     if len(a) >= 5 and a[4] != "3D":
-        print("the planar (2D) variant is outside this implementation" if a[4] == "2D" else USAGE)
+        print("the `2D` argument is not taken: files of the planar main are recognised by their 15 values" if a[4] == "2D" else USAGE)
         return 1
     flag = lambda i: len(a) > i and a[i] == "true"     # parse(Bool, ARGS[i])
     return aggregate(a[0], a[1], a[2], a[3], kappaflag=flag(5), runflag=flag(6))

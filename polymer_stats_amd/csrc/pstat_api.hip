@@ -125,10 +125,13 @@ namespace {
 // energies whose every step needs all n(n-1)/2 pairs: one chain per wavefront
 bool all_pairs(int energy_type) { return energy_type == PSTAT_INTERACTING || energy_type == PSTAT_CUTOFF; }
 // homes that run one chain per lane in chain blocks from the job queue; the others run one chain per wavefront
-bool chain_per_lane(Home home) { return home == SweepLds || home == SweepMem || home == ClusterLds || home == ClusterMem; }
+bool chain_per_lane(Home home) {
+  return home == SweepLds || home == SweepMem || home == ClusterLds || home == ClusterMem || home == Planar;
+}
 
 // The kernel family that runs the steps of a handle of `ncases` x `chains_per_case` chains of n monomers.
 Home choose_home(const LaunchCfg &cfg, int64_t n, int64_t chains_per_case, int64_t ncases, const Overrides &ov) {
+  if (cfg.planar) return Planar;   // the planar main has one kernel family (pstat_planar.hip)
   const bool cluster = cfg.move_set == PSTAT_MOVES_CLUSTER;
   if (all_pairs(cfg.energy_type)) return cluster ? ClusterAllPairs : Interacting;
   const int64_t total = chains_per_case * ncases;
@@ -245,21 +248,85 @@ int validate(const pstat_params *c, int ncases) {
 }
 
 // ---- the handle's step kernel: resolved once, probed and launched here
-// bytes of one monomer's cell (theta, phi) in LDS
-int cell_bytes(int precision) { return precision == PSTAT_F64 ? 16 : (precision == PSTAT_Q16 ? 4 : 8); }
+// bytes of one monomer's cell in LDS: (theta, phi), or phi alone for the planar main (f64 only)
+int cell_bytes(Home home, int precision) {
+  if (home == Planar) return 8;
+  return precision == PSTAT_F64 ? 16 : (precision == PSTAT_Q16 ? 4 : 8);
+}
 
 // the most lanes (64, 32, 16, 8) whose chains of n cells fit a CU's LDS; 0: not even 8
-int choose_lanes(int precision, int64_t n) {
+int choose_lanes(Home home, int precision, int64_t n) {
   for (int lanes = 64; lanes >= 8; lanes >>= 1)
-    if (n * cell_bytes(precision) * lanes <= kLdsBudget) return lanes;
+    if (n * cell_bytes(home, precision) * lanes <= kLdsBudget) return lanes;
   return 0;
 }
 
 // dynamic LDS of a workgroup of a.lanes chains
 int lds_bytes(Home home, int precision, const SweepArgs &a) {
   if (home == SweepMem) return (a.lds_rows + 1) * 64 * 16;   // + the trash row
-  if (home == SweepLds || home == ClusterLds) return (int)(a.n * a.lanes * cell_bytes(precision));
+  if (home == SweepLds || home == ClusterLds || home == Planar) return (int)(a.n * a.lanes * cell_bytes(home, precision));
   return 0;
+}
+
+// pstat_create_planar's reading of pstat_params (include/pstat.h, next to its declaration)
+int validate_planar(const pstat_params *c, int ncases) {
+  if (ncases < 1) return fail(PSTAT_ERR_INVALID_ARG, "ncases must be >= 1");
+  const pstat_params &b = c[0];
+  pstat_params d;
+  pstat_default_params(&d);
+  if (b.n < 1) return fail(PSTAT_ERR_INVALID_ARG, "num-monomers must be >= 1");
+  if (b.n > 0x7fffffff / 64) return fail(PSTAT_ERR_INVALID_ARG, "num-monomers too large");
+  if (b.num_chains < 1) return fail(PSTAT_ERR_INVALID_ARG, "num-chains must be >= 1");
+  if (b.chain_type != PSTAT_DIELECTRIC && b.chain_type != PSTAT_POLAR)
+    return fail(PSTAT_ERR_INVALID_ARG, "chain-type is not understood.");       // 2D/inc/eap_chain.jl:74
+  if (b.energy_type == PSTAT_CUTOFF)
+    return fail(PSTAT_ERR_INVALID_ARG, "energy_type: the planar main has no energy-type 'cutoff' (2D/inc/eap_chain.jl:81-89)");
+  if (b.energy_type < PSTAT_NONINTERACTING || b.energy_type > PSTAT_CUTOFF)
+    return fail(PSTAT_ERR_INVALID_ARG, "energy-type is not understood.");      // 2D/inc/eap_chain.jl:88
+  if (b.precision != PSTAT_F32 && b.precision != PSTAT_F64 && b.precision != PSTAT_Q16)
+    return fail(PSTAT_ERR_INVALID_ARG, "precision must be PSTAT_F32, PSTAT_F64 or PSTAT_Q16");
+  // options the planar main does not have: anything but the default is a mistake of the caller's
+  if (b.do_flips != d.do_flips) return fail(PSTAT_ERR_INVALID_ARG, "do_flips: 2D/mcmc_clustering_eap_chain.jl has no --do-flips");
+  if (b.bend_mod != d.bend_mod) return fail(PSTAT_ERR_INVALID_ARG, "bend_mod: 2D/mcmc_clustering_eap_chain.jl has no --bend-mod");
+  if (b.bend_angle != d.bend_angle)
+    return fail(PSTAT_ERR_INVALID_ARG, "bend_angle: 2D/mcmc_clustering_eap_chain.jl has no --bend-angle");
+  if (b.use_x0 != d.use_x0) return fail(PSTAT_ERR_INVALID_ARG, "use_x0: 2D/mcmc_clustering_eap_chain.jl has no --x0");
+  if (b.rng != PSTAT_RNG_MWC64X && b.rng != PSTAT_RNG_XOSHIRO128PP)
+    return fail(PSTAT_ERR_INVALID_ARG, "rng must be PSTAT_RNG_MWC64X or PSTAT_RNG_XOSHIRO128PP");
+  if (b.uniform_bits != 0 && b.uniform_bits != 23 && b.uniform_bits != 53)
+    return fail(PSTAT_ERR_INVALID_ARG, "uniform_bits must be 0 (the precision's default), 23 or 53");
+  if (b.rng == PSTAT_RNG_MWC64X)
+    for (int i = 0; i < ncases; ++i)
+      if (c[i].chain_id0 > PSTAT_MWC64X_MAX_CHAINS || (uint64_t)b.num_chains > PSTAT_MWC64X_MAX_CHAINS - c[i].chain_id0)
+        return fail(PSTAT_ERR_INVALID_ARG, "MWC64X streams are disjoint only for global chain ids < 2^22: chain_id0 + "
+                    "num_chains = %llu + %lld exceeds that (case %d); use PSTAT_RNG_XOSHIRO128PP for larger ids",
+                    (unsigned long long)c[i].chain_id0, (long long)b.num_chains, i);
+  if (!(b.phi_step > 0)) return fail(PSTAT_ERR_INVALID_ARG, "phi-step must be > 0");
+  if (!(b.adj_scale > 0)) return fail(PSTAT_ERR_INVALID_ARG, "step-adjust-scale must be > 0");
+  for (int i = 0; i < ncases; ++i) {
+    const pstat_params &p = c[i];
+    if (!(p.kT > 0)) return fail(PSTAT_ERR_INVALID_ARG, "kT must be > 0 (case %d)", i);
+    if (!std::isfinite(p.E0) || !std::isfinite(p.K1) || !std::isfinite(p.K2) || !std::isfinite(p.mu) ||
+        !std::isfinite(p.Fz) || !std::isfinite(p.Fx) || !std::isfinite(p.b))
+      return fail(PSTAT_ERR_INVALID_ARG, "non-finite physics parameter (case %d)", i);
+    if (!(p.cluster_prob >= 0.0 && p.cluster_prob <= 1.0))
+      return fail(PSTAT_ERR_INVALID_ARG, "cluster-prob must be in [0, 1] (case %d)", i);
+    if (p.n != b.n || p.num_chains != b.num_chains || p.chain_type != b.chain_type || p.energy_type != b.energy_type ||
+        p.do_flips != b.do_flips || p.umbrella != b.umbrella || p.precision != b.precision || p.device != b.device ||
+        p.rng != b.rng || p.phi_step != b.phi_step || p.adj_lb != b.adj_lb || p.adj_ub != b.adj_ub ||
+        p.adj_scale != b.adj_scale || p.steps_per_adjust != b.steps_per_adjust || p.use_x0 != b.use_x0 ||
+        p.bend_mod != b.bend_mod || p.bend_angle != b.bend_angle || p.uniform_bits != b.uniform_bits)
+      return fail(PSTAT_ERR_INVALID_ARG, "case %d differs from case 0 in a non-physics field", i);
+  }
+  // valid options of the reference that the device path lacks
+  if (b.precision != PSTAT_F64)
+    return fail(PSTAT_ERR_UNSUPPORTED, "the planar main runs in PSTAT_F64 only (no f32 / q16 planar state)");
+  if (b.energy_type == PSTAT_INTERACTING)
+    return fail(PSTAT_ERR_UNSUPPORTED, "energy-type 'interacting' (all pairs) is not implemented for the planar main");
+  if (choose_lanes(Planar, b.precision, b.n) == 0)
+    return fail(PSTAT_ERR_UNSUPPORTED, "num-monomers = %lld: a planar chain's 8-byte cells must fit the 160 KiB LDS of a CU "
+                "eight chains at a time, num-monomers <= %d", (long long)b.n, kLdsBudget / (8 * 8));
+  return PSTAT_OK;
 }
 
 // queue layout: [0] error flag (sticky: never cleared by a launch), [1] job counter, [2 ..] per-block "segments done"
@@ -269,10 +336,10 @@ size_t queue_ints(const SweepArgs &a) { return 2 + (size_t)a.nblocks; }
 int resolve_kernel(const LaunchCfg &cfg, int64_t n, StepKernel *out) {
   static StepKernel (*const of_home[])(const LaunchCfg &, int64_t) = {   // indexed by Home
       sweep_step_kernel, sweep_step_kernel, cluster_step_kernel, cluster_gm_step_kernel,
-      cluster_cw_step_kernel, cluster_wave_step_kernel, interacting_step_kernel};
-  static_assert(sizeof of_home / sizeof *of_home == Interacting + 1, "one resolver per Home");
+      cluster_cw_step_kernel, cluster_wave_step_kernel, interacting_step_kernel, planar_step_kernel};
+  static_assert(sizeof of_home / sizeof *of_home == Planar + 1, "one resolver per Home");
   *out = of_home[cfg.home](cfg, n);
-  if (cfg.home == SweepLds || cfg.home == SweepMem || cfg.home == ClusterLds)
+  if (cfg.home == SweepLds || cfg.home == SweepMem || cfg.home == ClusterLds || cfg.home == Planar)
     HIP_TRY(hipFuncSetAttribute(out->fn, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget));
   return PSTAT_OK;
 }
@@ -433,7 +500,7 @@ hipError_t launch_steps(pstat_handle *h, int64_t step0, int64_t nsteps, int rein
   void *argv[6] = {&A, &h->S, &h->d_cases};
   switch (cfg.home) {
     case SweepLds: case SweepMem: argv[3] = &rare; argv[4] = &h->d_queue; break;
-    case ClusterLds: case ClusterMem: argv[3] = &umbrella; argv[4] = &h->d_queue; break;
+    case ClusterLds: case ClusterMem: case Planar: argv[3] = &umbrella; argv[4] = &h->d_queue; break;
     case ClusterChainWave: argv[3] = &umbrella; break;
     case ClusterAllPairs: argv[3] = &umbrella; argv[4] = &cutoff; break;
     case Interacting: argv[3] = &do_flips; argv[4] = &lag; argv[5] = &reinit_mode; break;
@@ -553,10 +620,12 @@ void pstat_default_params(pstat_params *p) {
   p->cutoff_radius = 7.5;
 }
 
-int pstat_create(const pstat_params *cases, int32_t ncases, void *stream, pstat_handle **out) {
+// pstat_create and pstat_create_planar: the same handle, allocations and launch shape; `planar` picks the validation,
+// the one-angle state and home Planar
+static int create_handle(const pstat_params *cases, int32_t ncases, void *stream, pstat_handle **out, const bool planar) {
   if (!cases || !out) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
   *out = nullptr;
-  int rc = validate(cases, ncases);
+  int rc = planar ? validate_planar(cases, ncases) : validate(cases, ncases);
   if (rc) return rc;
   int ndev = pstat_device_count();
   if (ndev < 1) return fail(PSTAT_ERR_NO_DEVICE, "no HIP device is visible (this library has no CPU path)");
@@ -569,6 +638,10 @@ int pstat_create(const pstat_params *cases, int32_t ncases, void *stream, pstat_
   if (!h) return fail(PSTAT_ERR_NOMEM, "host allocation failed");
   try {   // std::vector growth may throw: nothing propagates through the C ABI
   h->base = cases[0];
+  if (planar) {   // what a planar handle ignores is normalised, so that checkpoints of equal runs match
+    h->base.theta_step = 0.0;
+    h->base.move_set = PSTAT_MOVES_CLUSTER;
+  }
   h->ncases = ncases;
   h->device = cases[0].device;
   h->elem = cases[0].precision == PSTAT_F64 ? 8 : (cases[0].precision == PSTAT_Q16 ? 2 : 4);
@@ -583,9 +656,10 @@ int pstat_create(const pstat_params *cases, int32_t ncases, void *stream, pstat_
   h->ov = read_overrides();
   h->cfg = {h->base.precision, h->base.chain_type, h->base.energy_type, h->base.do_flips ? 1 : 0,
             h->base.umbrella ? 1 : 0, any_fx ? 1 : 0, 0, h->base.rng, h->base.move_set};
+  h->cfg.planar = planar ? 1 : 0;
   const Home home = h->cfg.home = choose_home(h->cfg, h->base.n, h->base.num_chains, ncases, h->ov);
 
-  const int lanes = (home == SweepLds || home == ClusterLds) ? choose_lanes(h->base.precision, h->base.n) : 64;
+  const int lanes = (home == SweepLds || home == ClusterLds || home == Planar) ? choose_lanes(home, h->base.precision, h->base.n) : 64;
   if (lanes == 0)
     return fail(PSTAT_ERR_UNSUPPORTED, "num-monomers = %lld does not fit the 160 KiB LDS of a CU",
                 (long long)cases[0].n);
@@ -690,6 +764,14 @@ int pstat_create(const pstat_params *cases, int32_t ncases, void *stream, pstat_
   }
   *out = owner.release();
   return PSTAT_OK;
+}
+
+int pstat_create(const pstat_params *cases, int32_t ncases, void *stream, pstat_handle **out) {
+  return create_handle(cases, ncases, stream, out, false);
+}
+
+int pstat_create_planar(const pstat_params *cases, int32_t ncases, void *stream, pstat_handle **out) {
+  return create_handle(cases, ncases, stream, out, true);
 }
 
 void pstat_destroy(pstat_handle *h) {
@@ -816,6 +898,8 @@ int pstat_sync(pstat_handle *h) {
 
 int pstat_reinit(pstat_handle *h, int32_t force_init) {
   if (!h) return fail(PSTAT_ERR_INVALID_ARG, "null handle");
+  if (h->cfg.planar)
+    return fail(PSTAT_ERR_UNSUPPORTED, "2D/mcmc_clustering_eap_chain.jl has no --num-inits: nothing to re-initialise");
   if (h->cfg.move_set == PSTAT_MOVES_CLUSTER)
     return fail(PSTAT_ERR_UNSUPPORTED, "mcmc_clustering_eap_chain.jl has no --num-inits: nothing to re-initialise");
   int rc = set_device(h);
@@ -865,6 +949,7 @@ int pstat_set_kT(pstat_handle *h, int32_t icase, double kT) {
 
 int pstat_restart_from_x0(pstat_handle *h, const double *x0, int64_t len, double dx0_phi, double dx0_theta) {
   if (!h || !x0) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
+  if (h->cfg.planar) return fail(PSTAT_ERR_UNSUPPORTED, "2D/mcmc_clustering_eap_chain.jl has no --x0: a planar chain starts uniform");
   if (len != 2 && len != 2 * h->base.n)
     return fail(PSTAT_ERR_INVALID_ARG, "Invalid input for 'x0': length %lld is neither 2 nor 2 * num-monomers",
                 (long long)len);                                                      // inc/eap_chain.jl:77
@@ -1095,7 +1180,8 @@ struct CkptHeader {
   uint64_t magic;
   int32_t abi_version, header_bytes;
   int64_t n, C, ncases, steps_recorded, step_in_init;
-  int32_t precision, chain_type, energy_type, rng, move_set, umbrella, do_flips, uniform_bits, lag, reserved;
+  int32_t precision, chain_type, energy_type, rng, move_set, umbrella, do_flips, uniform_bits, lag;
+  int32_t planar;               // 1: the image of a planar handle (pstat_create_planar); 0 in every other image
   uint64_t seed, chain_id0;     // case 0's
   uint64_t params_fnv;          // fingerprint of everything else a chain's continuation depends on (params_fingerprint)
 };
@@ -1146,6 +1232,7 @@ int pstat_checkpoint(pstat_handle *h, void *buf, size_t *bytes) {
   hd.precision = h->base.precision; hd.chain_type = h->base.chain_type; hd.energy_type = h->base.energy_type;
   hd.rng = h->base.rng; hd.move_set = h->base.move_set; hd.umbrella = h->base.umbrella ? 1 : 0;
   hd.do_flips = h->base.do_flips ? 1 : 0; hd.uniform_bits = h->args.wide_eps ? 53 : 23; hd.lag = h->cfg.lag;
+  hd.planar = h->cfg.planar;
   hd.seed = h->cases[0].seed; hd.chain_id0 = h->cases[0].chain_id0;
   hd.params_fnv = params_fingerprint(h);
   char *q = (char *)buf;
@@ -1185,6 +1272,7 @@ int pstat_restore(pstat_handle *h, const void *buf, size_t bytes) {
   CKPT_SAME(umbrella, h->base.umbrella ? 1 : 0, "umbrella-sampling");
   CKPT_SAME(do_flips, h->base.do_flips ? 1 : 0, "do-flips");
   CKPT_SAME(uniform_bits, h->args.wide_eps ? 53 : 23, "uniform_bits");
+  CKPT_SAME(planar, h->cfg.planar, "planar (1: a handle of pstat_create_planar, 0: of pstat_create)");
 #undef CKPT_SAME
   if (hd.seed != h->cases[0].seed || hd.chain_id0 != h->cases[0].chain_id0)
     return fail(PSTAT_ERR_BAD_CHECKPOINT, "checkpoint does not match this handle: seed / chain_id0 %llu / %llu in the "

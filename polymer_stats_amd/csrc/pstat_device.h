@@ -23,7 +23,7 @@ enum { S_R1 = 0, S_R2, S_R3, S_R1SQ, S_R2SQ, S_R3SQ, S_P1, S_P2, S_P3, S_P1SQ, S
        S_U, S_USQ, NSUMS_BASE, S_C2 = NSUMS_BASE, S_PSI, NSUMS };
 
 struct DevState {
-  void *ang;            // R  [2][n][C]   plane 0 = theta, plane 1 = phi (radians)
+  void *ang;            // R  [2][n][C]   plane 0 = theta, plane 1 = phi (radians); planar handles: plane 0 is zero
   void *ang_tmp;        // R  [2][n][C]   scratch for re-initialisation
   uint32_t *rng;        // u32[4][C]      xoshiro128++ state
   double *stepsz;       // f64[2][C]      phi_step, theta_step (mcmc_eap_chain.jl:172)
@@ -50,7 +50,7 @@ struct CaseConst {      // physics scalars of one case (inc/eap_chain.jl:89-108)
   double E0, K1, K2, mu, kT, Fz, Fx, b;
   uint64_t seed, chain_id0;
   double kappa, psi0;     // --bend-mod, --bend-angle (clustering main; 0 in mcmc_eap_chain.jl)
-  double cluster_prob;    // --cluster-prob: probability of NOT attempting a cluster flip
+  double cluster_prob;    // --cluster-prob: probability of NOT attempting a cluster flip (planar main: OF flipping)
   double cutoff_radius;   // --cutoff-radius in monomer lengths (energy-type cutoff)
 };
 
@@ -267,8 +267,8 @@ __device__ __forceinline__ void run_job_queue(const SweepArgs &A, int *__restric
 }
 #endif  // __HIPCC__
 
-// The kernel family that runs a handle's steps, chosen once by choose_home() (pstat_api.hip).  The first four run one chain
-// per lane in chain blocks from the job queue (run_job_queue), the others one chain per wavefront.
+// The kernel family that runs a handle's steps, chosen once by choose_home() (pstat_api.hip).  The first four and the last
+// run one chain per lane in chain blocks from the job queue (run_job_queue), the others one chain per wavefront.
 enum Home {
   SweepLds,          // fixed-force main, cells in LDS (pstat_kernels.hip)
   SweepMem,          // fixed-force main, f64, cells in the global working buffer DevState::work (run_segment, ST = 2)
@@ -277,6 +277,7 @@ enum Home {
   ClusterChainWave,  // clustering main, small f64 ensembles: one chain per wavefront (pstat_cluster_cw.hip)
   ClusterAllPairs,   // clustering main with the all-pairs energies (pstat_cluster_wave.hip)
   Interacting,       // fixed-force main with the all-pairs energy (pstat_interacting.hip)
+  Planar,            // planar (2D) clustering main, one chain per lane, 8-byte phi cells in LDS (pstat_planar.hip)
 };
 
 // What pstat_api.hip chooses and reads once per handle; the host entry points below are asynchronous on `stream`.
@@ -287,6 +288,7 @@ struct LaunchCfg {
   int move_set;  // PSTAT_MOVES_SINGLE (mcmc_eap_chain.jl) | PSTAT_MOVES_CLUSTER (mcmc_clustering_eap_chain.jl)
   Home home;     // the kernel family
   int packed;    // chain blocks straddle cases (SweepArgs::packed): the kernel instantiation with per-lane case scalars
+  int planar;    // a handle of pstat_create_planar (2D/mcmc_clustering_eap_chain.jl): one angle per monomer, home Planar
 };
 
 struct SweepRare {  // wave-uniform switches of the sweep's rarely used options (RARE instantiations only)
@@ -311,6 +313,7 @@ StepKernel cluster_gm_step_kernel(const LaunchCfg &cfg, int64_t n);    // Cluste
 StepKernel cluster_cw_step_kernel(const LaunchCfg &cfg, int64_t n);    // ClusterChainWave (n <= 256): int umbrella
 StepKernel cluster_wave_step_kernel(const LaunchCfg &cfg, int64_t n);  // ClusterAllPairs (n <= 512): int umbrella, int cutoff
 StepKernel interacting_step_kernel(const LaunchCfg &cfg, int64_t n);   // Interacting (n <= 512): int do_flips, int lag, int reinit_mode
+StepKernel planar_step_kernel(const LaunchCfg &cfg, int64_t n);        // Planar: int umbrella, int *queue
 // bytes of DevState::work for home ClusterMem
 size_t cluster_gm_work_bytes(const LaunchCfg &cfg, const SweepArgs &a);
 
@@ -318,6 +321,9 @@ size_t cluster_gm_work_bytes(const LaunchCfg &cfg, const SweepArgs &a);
 hipError_t launch_init(const LaunchCfg &cfg, const SweepArgs &a, const DevState &s,
                        const CaseConst *cases, double phi_step, double theta_step,
                        const InitOpts &io, hipStream_t stream);
+// the planar handle's initialisation (pstat_planar.hip; launch_init hands over to it): n words per chain, phi plane only
+hipError_t launch_planar_init(const LaunchCfg &cfg, const SweepArgs &a, const DevState &s, const CaseConst *cases,
+                              double phi_step, hipStream_t stream);
 hipError_t launch_reset_sampler(const DevState &s, double phi_step, double theta_step, hipStream_t stream);
 hipError_t launch_reinit(const LaunchCfg &cfg, const SweepArgs &a, const DevState &s,
                          const CaseConst *cases, int force_init, hipStream_t stream);

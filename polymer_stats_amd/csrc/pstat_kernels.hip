@@ -1182,6 +1182,7 @@ hipError_t launch_reset_sampler(const DevState &s, double phi_step, double theta
 hipError_t launch_init(const LaunchCfg &cfg, const SweepArgs &a, const DevState &s,
                        const CaseConst *cases, double phi_step, double theta_step,
                        const InitOpts &io, hipStream_t stream) {
+  if (cfg.planar) return launch_planar_init(cfg, a, s, cases, phi_step, stream);   // one angle per monomer, no x0 start
   const unsigned grid = (unsigned)((s.C + 255) / 256);
   if (cfg.rng == PSTAT_RNG_XOSHIRO128PP) launch_init_g<Xoshiro128pp>(cfg, a, s, cases, phi_step, theta_step, io, grid, stream);
   else launch_init_g<Mwc64x>(cfg, a, s, cases, phi_step, theta_step, io, grid, stream);

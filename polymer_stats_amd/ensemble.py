@@ -12,9 +12,11 @@ from ._lib import NOBS, NRED, Params, Summary, LaunchInfo, check
 
 class Ensemble:
     """`cases`: one Params or a list of Params that differ only in physics scalars (a sweep grid).
-    `stream`: raw hipStream_t (int) to launch on, e.g. torch.cuda.current_stream().cuda_stream."""
+    `stream`: raw hipStream_t (int) to launch on, e.g. torch.cuda.current_stream().cuda_stream.
+    `planar`: the planar main (2D/mcmc_clustering_eap_chain.jl, pstat_create_planar): one angle per monomer; observables
+    are the 16-vectors with the y slots 0 (PLANAR_OBS_NAMES / PLANAR_OBS_INDEX), chain_state()["theta"] is zeros."""
 
-    def __init__(self, cases: Params | Sequence[Params], stream: int | None = None):
+    def __init__(self, cases: Params | Sequence[Params], stream: int | None = None, planar: bool = False):
         self._L = _lib.load()
         if isinstance(cases, Params):
             cases = [cases]
@@ -22,8 +24,9 @@ class Ensemble:
         self.ncases = len(self.cases)
         arr = (Params * self.ncases)(*self.cases)
         self._h = C.c_void_p()
-        check(self._L.pstat_create(arr, self.ncases, C.c_void_p(stream) if stream else None,
-                                   C.byref(self._h)))
+        self.planar = bool(planar)
+        create = self._L.pstat_create_planar if self.planar else self._L.pstat_create
+        check(create(arr, self.ncases, C.c_void_p(stream) if stream else None, C.byref(self._h)))
         self.n = int(self.cases[0].n)
         self.num_chains = int(self.cases[0].num_chains)
 

@@ -185,7 +185,7 @@ class _Pool:
     in their physics scalars, pstat_create) --, every case's chains sharded over one or more devices in this process;
     reductions merged on the host (every entry of the reduction vector is additive)."""
 
-    def __init__(self, pargs, factory=None):
+    def __init__(self, pargs, factory=None, planar=False):
         self.plist = plist = pargs if isinstance(pargs, list) else [pargs]
         factory = factory or params_from_pargs
         for p in plist:
@@ -207,7 +207,7 @@ class _Pool:
         first = 0
         for i, dev in enumerate(devices):
             cnt = base + (1 if i < extra else 0)
-            self.parts.append(Ensemble([factory(p, cnt, first, dev) for p in plist]))
+            self.parts.append(Ensemble([factory(p, cnt, first, dev) for p in plist], planar=planar))
             self.counts.append(cnt)
             first += cnt
         self.steps = 0

@@ -24,6 +24,8 @@ across partitions, not trajectory-identical, once an ensemble is large enough to
         --axis run=1:5 --axis kT='10^(-2:0.2:2)' --axis E0=0:0.2:5 --axis K1=1 --axis K2=0 --axis Fz=0 --axis Fx=0 \
         --axis n=100 --axis b=1 --axis kappa=0 --name E0,K1,K2,kT,Fz,Fx,n,b,kappa,run:raw \
         -- --chain-type dielectric --energy-type Ising --num-steps 2500000 --burn-in 100000 -v 2
+
+The planar main's sweeps (2D/run/*.jl) are the same thing with `--main mcmc_clustering_eap_chain_2d`.
 """
 from __future__ import annotations
 
@@ -37,10 +39,12 @@ import numpy as np
 
 from . import _lib          # (tools/run_sweep.py counts the devices through it)
 from . import mcmc_clustering_eap_chain as cluster_main
+from . import mcmc_clustering_eap_chain_2d as planar_main
 from . import mcmc_eap_chain as fixed_main
 from .mcmc_eap_chain import ReferenceError_
 
-MAINS = {"mcmc_eap_chain": fixed_main, "mcmc_clustering_eap_chain": cluster_main}
+# (the planar main: 2D/run/Ising_2024-11-06.jl and its siblings launch 2D/mcmc_clustering_eap_chain.jl the same way)
+MAINS = {"mcmc_eap_chain": fixed_main, "mcmc_clustering_eap_chain": cluster_main, "mcmc_clustering_eap_chain_2d": planar_main}
 
 # how the reference's run scripts turn a case's keys into flags of the main (run/K1_E0-kT-phase.jl:45)
 KEY_FLAG = {"E0": "--E0", "K1": "--K1", "K2": "--K2", "mu": "--mu", "kT": "--kT", "Fz": "--Fz", "Fx": "--Fx",
@@ -235,7 +239,7 @@ def run_sweep(main_name: str, fixed_argv: list[str], cases: list[dict], workdir:
             plist = plist_all[i:i + per_launch]
             t0 = time.time()
             info = {}
-            if main is cluster_main:      # the main's own protocol, every case of the ensemble at once
+            if main is not fixed_main:    # the clustering mains' own protocol, every case of the ensemble at once
                 res = main.run_cases(plist, write_csv=write_csv, info=info)
             else:
                 res = main.mcmc_cases(int(plist[0]["num-steps"]), plist, write_csv=write_csv, info=info)

@@ -14,6 +14,12 @@ written it (polymer_stats_amd/sweep.py), ready for scripts/aggregate_mcmc.jl (or
         --name E0,K1,K2,kT,Fz,Fx,n,b,kappa,run:raw \
         -- --chain-type dielectric --energy-type Ising --num-steps 2500000 --burn-in 100000 -v 2 --stepout 250
 
+    # 2D/run/Ising_2024-11-06.jl: the planar main, 4 x 22 grid points x 10 runs = 880 single-chain cases of 1e7 steps
+    python tools/run_sweep.py out/ --main mcmc_clustering_eap_chain_2d --num-chains 1 --axis b=1 --axis n=25 --axis Fx=0 \
+        --axis Fz=0,0.1,0.2,0.3,0.4,0.5,1,2,3,4,5,7.5,10,12.5,15,20,25,30,35,40,45,50 --axis kT=1 --axis E0=0.1 \
+        --axis K1=0.01,0.04,0.1,0.4 --axis K2=0 --axis run=1:10 --name E0,K1,K2,kT,Fz,Fx,n,b,run:raw \
+        -- --chain-type dielectric --energy-type Ising --num-steps 10000000 --burn-in 200000 -v 2
+
 The first --axis is the outermost loop (`for b in bs, n in ns, ...`).  Everything after `--` goes to the main unchanged.
 A case whose .out exists is not run again (the run scripts' `isfile(outfile)`); --overwrite runs it anyway.
 """
@@ -34,7 +40,8 @@ def main():
         argv, fixed = argv[:k], argv[k + 1:]
     ap = argparse.ArgumentParser()
     ap.add_argument("workdir")
-    ap.add_argument("--main", choices=["mcmc_eap_chain", "mcmc_clustering_eap_chain"], default="mcmc_eap_chain")
+    ap.add_argument("--main", choices=["mcmc_eap_chain", "mcmc_clustering_eap_chain", "mcmc_clustering_eap_chain_2d"],
+                    default="mcmc_eap_chain")
     ap.add_argument("--axis", action="append", default=[], metavar="KEY=VALUES",
                     help="values: a,b,c | start:step:stop (also several, comma-separated) | 10^(start:step:stop); first axis = outermost loop")
     ap.add_argument("--cases", default="", help="JSON array of case objects instead of (or appended to) the axes' product")
