@@ -1,10 +1,14 @@
 """polymer_stats_amd -- MI355X (gfx950) implementation of the fixed-force-ensemble MCMC hot path of
-grasingerm/polymer-stats (mcmc_eap_chain.jl), behind the C ABI of include/pstat.h."""
+grasingerm/polymer-stats (mcmc_eap_chain.jl), behind the C ABI of include/pstat.h.
+
+_lib, ensemble: the binding.  mcmc_eap_chain, mcmc_clustering_eap_chain, mcmc_clustering_eap_chain_2d: the drop-in hosts of the
+reference's three mains (python -m polymer_stats_amd.<name>), short modules over _host, which holds what they share.  sweep,
+aggregate_mcmc: the reference's run/*.jl sweeps and scripts/aggregate_mcmc.jl.  julia_fmt: Julia's number formatting."""
 from ._lib import (DIELECTRIC, POLAR, NONINTERACTING, INTERACTING, ISING, CUTOFF, F32, F64, Q16, RNG_MWC64X, RNG_XOSHIRO128PP, NOBS, NRED, NQ, MOVES_SINGLE, MOVES_CLUSTER,
                    OBS_NAMES, PLANAR_OBS_NAMES, PLANAR_OBS_INDEX, Params, PstatError, default_params, default_planar_params)
 from .ensemble import Ensemble, summary_from_reduction
 
-__all__ = ["DIELECTRIC", "POLAR", "NONINTERACTING", "INTERACTING", "ISING", "F32", "F64", "Q16", "RNG_MWC64X", "RNG_XOSHIRO128PP", "NOBS",
+__all__ = ["DIELECTRIC", "POLAR", "NONINTERACTING", "INTERACTING", "ISING", "CUTOFF", "F32", "F64", "Q16", "RNG_MWC64X", "RNG_XOSHIRO128PP", "NOBS",
            "NRED", "NQ", "MOVES_SINGLE", "MOVES_CLUSTER", "OBS_NAMES", "PLANAR_OBS_NAMES", "PLANAR_OBS_INDEX", "Params", "PstatError",
            "default_params", "default_planar_params", "Ensemble",
            "summary_from_reduction"]

@@ -1,0 +1,544 @@
+"""What the three hosts (mcmc_eap_chain, mcmc_clustering_eap_chain, mcmc_clustering_eap_chain_2d) share: the option
+table, the seed and the logging, pargs -> the common pstat_params fields, the pool of one ensemble's shards, the recorded
+stage that writes the two CSV files, the stdout lines and the body of main().  What differs between the mains comes in from
+them as data or as a function (their option names in their order, their headers, their row formatter, their protocol);
+nothing here asks which main is running.  The hosts are thin: every number they print comes out of the library.
+"""
+from __future__ import annotations
+
+import argparse
+import ast
+import math
+import operator
+import os
+import sys
+import time
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _lib
+from .ensemble import Ensemble, summary_from_reduction
+from .julia_fmt import jl_float, jl_vector
+
+# Device memory one handle's series may take: the rows of a recorded run are read back and written out in chunks of
+# as many rows as fit (a row is ncases x (NRED + 7 [+ 2n]) doubles; at least one row per chunk).
+SERIES_BUDGET_BYTES = 256 << 20
+
+FIXED, CLUSTER, PLANAR = "mcmc_eap_chain", "mcmc_clustering_eap_chain", "mcmc_clustering_eap_chain_2d"
+
+
+class ReferenceError_(RuntimeError):
+    """Raised where the reference calls error(...) -- same message text."""
+
+
+# ---------------------------------------------------------------------------------------------- the option table
+# name (= dest = ArgParse.jl's dict key; the flag is --name): (short alias, type | "flag" for store_true, default, help
+# [, {main: what that main states differently}]).  A main has the rows it names, in the order it names them (build_parser).
+OPTIONS = {
+    # --- the reference's tables: mcmc_eap_chain.jl:19-153, mcmc_clustering_eap_chain.jl:14-152, 2D/mcmc_clustering_eap_chain.jl:15-129
+    "E0": ("-e", float, 0.0, "magnitude of electric field"),
+    "chain-type": ("-T", str, "dielectric", "chain type (dielectric|polar)"),
+    "K1": ("-J", float, 1.0, "dipole susceptibility along the monomer axis (dielectric chain)"),
+    "K2": ("-K", float, 0.0, "dipole susceptibility orthogonal to the monomer axis (dielectric chain)"),
+    "mu": ("-m", float, 1e-2, "dipole magnitude (electret chain)"),
+    "bend-mod": ("-a", float, 0.0, "bending modulus of chain"),
+    "bend-angle": ("-g", float, 0.0, "zero energy bond angle"),
+    "energy-type": ("-u", str, "noninteracting", "energy type (noninteracting|interacting)",
+                    {CLUSTER: dict(default="Ising", help="energy type (interacting|cutoff|Ising|noninteracting)"),
+                     PLANAR: dict(help="energy type (noninteracting|interacting|Ising)")}),
+    "cutoff-radius": (None, float, 7.5, "cut off radius (units of monomer lengths)"),
+    "kT": ("-k", float, 1.0, "dimensionless temperature"),
+    "ensemble-type": ("-E", str, "force", "ensemble type (force|end-to-end)"),
+    "Fz": ("-F", float, 0.0, "force in the z-direction (direction of E-field; force ensemble)"),
+    "Fx": ("-G", float, 0.0, "force in the x-direction (force ensemble)"),
+    "rz": ("-z", float, 0.0, "end-to-end vector in the z-direction (etoe ensemble)"),
+    "rx": ("-x", float, 0.0, "end-to-end vector in the x-direction (etoe ensemble)"),
+    "mlen": ("-b", float, 1.0, "monomer length"),
+    "num-monomers": ("-n", int, 100, "number of monomers"),
+    "num-steps": ("-N", int, int(1e6), "number of steps", {FIXED: dict(default=int(1e5))}),
+    "num-inits": ("-M", int, 1, "number of random initializations"),
+    "force-init": ("-I", "flag", False, "force each random initialization (false to use metro.)"),
+    "phi-step": ("-p", float, 3 * math.pi / 8, "maximum phi step length"),
+    "do-flips": (None, "flag", False, "trial moves with flipping monomers"),
+    "theta-step": ("-q", float, 3 * math.pi / 16, "maximum theta step length"),
+    "chain-frac-step": ("-f", float, 0.15, "fraction of monomers to step (end-to-end ensemble)"),
+    "cluster-prob": (None, float, 0.5, "probability of flipping a cluster"),
+    "step-adjust-lb": ("-L", float, 0.15, "adjust step sizes if acc. ratio below this threshold"),
+    "step-adjust-ub": ("-U", float, 0.40, "adjust step sizes if acc. ratio above this threshold", {FIXED: dict(default=0.55)}),
+    "step-adjust-scale": ("-A", float, 1.1, "scale factor for adjusting step sizes (> 1.0)"),
+    "steps-per-adjust": ("-S", int, 2500, "steps between step size adjustments"),
+    "acc": ("-a", str, "metropolis", "acceptance function (metropolis|kawasaki)"),
+    "umbrella-sampling": ("-B", "flag", False, "use umbrella sampling (w/ electrostatic weight function)"),
+    "update-freq": (None, float, 15.0, "update frequency (seconds)"),
+    "verbose": ("-v", int, 3, "verbosity level: 0-nothing, 1-errors, 2-warnings, 3-info"),
+    "prefix": ("-P", str, "eap-mcmc", "prefix for output files"),
+    "postfix": ("-Q", str, "", "postfix for output files"),
+    "stepout": ("-s", int, 500, "steps between storing microstates"),
+    "numeric-type": (None, str, "float64", "numerical data type for averaging (float64|float128|dec128|big)"),
+    "burn-in": (None, int, 50000, "steps for burn-in; i.e. steps before averaging",
+                {FIXED: dict(default=0, help="steps discarded before averaging, per rung of --burn-schedule (0 = the reference's "
+                                             "behaviour: record from step 1)")}),
+    "burn-schedule": (None, str, "[1000; 100; 10; 2; 1]", "temperature schedule for burn-in",
+                      {FIXED: dict(default="[1]", help="kT multipliers of the burn-in ladder, e.g. '[1000; 100; 10; 2; 1]' "
+                                                       "(mcmc_clustering_eap_chain.jl:138-141)")}),
+    "x0": (None, str, None, "initial configuration"),
+    "dx0": (None, str, "[2*pi, 1e-1]", "random perturbation of x0"),
+    "profile": ("-Z", "flag", False, "profile the program"),
+    # --- ours
+    "carry-burn-in": (None, "flag", False,
+                      "run the burn-in ladder on the chains and carry them into the production run (the reference's ladder starts "
+                      "every rung and the production run from a fresh chain, so it changes no output: without this option it is "
+                      "not run)"),
+    "num-chains": (None, int, 4096, "independent chains run at once on the GPU(s) and pooled"),
+    "seed": (None, int, None, "seed of the per-chain generators; default: fresh OS entropy per run, like the reference's unseeded "
+                              "RNG (the seed drawn is echoed on stderr at --verbose >= 2)"),
+    "devices": (None, str, "0", "comma-separated HIP device ordinals; chains are sharded over them"),
+    "rng": (None, str, "mwc64x", "per-chain generator: mwc64x | xoshiro128++"),
+    "precision": (None, str, "f64", "device arithmetic: f64 (the reference's Float64; default) | f32 (fast path: f32 state, f64 "
+                                    "running sums; not for collapsed chains of the pair energies) | q16 (lattice angles, f32 arithmetic)"),
+    "uniform-bits": (None, int, 0, "random bits of the Metropolis draw rand(): 0 = the precision's default (53 for f64, 23 for f32) | "
+                                   "23 | 53 (f64 only)",
+                     {FIXED: dict(help="random bits of the Metropolis draw rand() (mcmc_eap_chain.jl:287): 0 = the precision's default "
+                                       "(53 for f64, like Julia's Float64 rand(); 23 for f32 / q16) | 23 | 53 (f64 only)"),
+                      PLANAR: dict(help="random bits of the Metropolis draw rand(): 0 = the default (53, like Julia's Float64 "
+                                        "rand()) | 23 | 53")}),
+}
+
+
+def parser_functions(main: str, names: list[str]):
+    """(build_parser, parse_args, default_pargs) of the main called `main`, which has the rows `names` in that order."""
+    def build_parser() -> argparse.ArgumentParser:
+        p = argparse.ArgumentParser(prog=main, add_help=True, allow_abbrev=False)
+        for name in names:
+            alias, kind, default, text, *own = OPTIONS[name]
+            kw = {"default": default, "help": text, **(own[0].get(main, {}) if own else {})}
+            if kind == "flag":
+                kw = dict(action="store_true", help=kw["help"])
+            else:
+                kw["type"] = kind
+            p.add_argument("--" + name, *([alias] if alias else []), dest=name, **kw)
+        return p
+
+    def parse_args(argv=None) -> dict:
+        return vars(build_parser().parse_args(argv))
+
+    def default_pargs(**overrides) -> dict:
+        d = parse_args([])
+        for k, v in overrides.items():
+            if k not in d:
+                raise KeyError(k)
+            d[k] = v
+        return d
+
+    return build_parser, parse_args, default_pargs
+
+
+# ---------------------------------------------------------------------------------------------- arithmetic literals
+_BIN = {ast.Add: operator.add, ast.Sub: operator.sub, ast.Mult: operator.mul, ast.Div: operator.truediv,
+        ast.Pow: operator.pow}
+
+
+def arith(node, names={}):
+    """The value of a parsed arithmetic literal: numbers (integers stay integers, no bool), + - * / **, and `names`."""
+    if isinstance(node, ast.Constant) and isinstance(node.value, (int, float)) and not isinstance(node.value, bool):
+        return node.value
+    if isinstance(node, ast.Name) and node.id in names:
+        return names[node.id]
+    if isinstance(node, ast.UnaryOp) and isinstance(node.op, (ast.USub, ast.UAdd)):
+        v = arith(node.operand, names)
+        return -v if isinstance(node.op, ast.USub) else v
+    if isinstance(node, ast.BinOp) and type(node.op) in _BIN:
+        return _BIN[type(node.op)](arith(node.left, names), arith(node.right, names))
+    raise ValueError("not a number")
+
+
+def number(text: str, names={}):
+    """`2*pi`, `10^-2`, `1e-1` -> its value (the reference eval()s such strings; only literals and `names` are understood)."""
+    return arith(ast.parse(text.strip().replace("^", "**"), mode="eval").body, names)
+
+
+def julia_vector(text: str) -> list[float]:
+    """A Julia vector literal of arithmetic constants, '[2*pi, 1e-1]' or '[1000; 100; 10]' -> floats."""
+    t = text.strip()
+    if not (t.startswith("[") and t.endswith("]")):
+        raise ValueError(text)
+    return [float(number(x, {"pi": math.pi, "π": math.pi})) for x in t[1:-1].replace(";", ",").split(",") if x.strip()]
+
+
+# ---------------------------------------------------------------------------------------------- seed, logging, checks
+def fresh_seed() -> int:
+    """A new 63-bit seed per call: OS entropy, mixed with the clock and the pid in case the pool is a stub.
+    The reference never seeds Julia's RNG, so repeated identical command lines give independent samples
+    (run/interacting-compare-with-clustering_2021-09-28.jl:26-27 launches each case 25 times and takes the
+    scatter as its error bar); the drop-in must do the same unless --seed is given."""
+    v = int.from_bytes(os.urandom(8), "little") ^ time.time_ns() ^ (os.getpid() << 40)
+    return v & 0x7FFFFFFFFFFFFFFF
+
+
+WIDE_TYPES = {"float128": "80-bit extended (numpy.longdouble)", "dec128": "80-bit extended (numpy.longdouble)",
+              "big": "80-bit extended (numpy.longdouble)"}
+
+
+def _log(pargs, level: int, tag: str, msg: str):
+    # Logging to stderr gated by --verbose (mcmc_eap_chain.jl:157-165): 3 info, 2 warn, 1 error
+    if pargs["verbose"] >= level:
+        print(f"[ {tag}: {msg}", file=sys.stderr)
+
+
+def resolve_seed(pargs: dict) -> int:
+    """--seed as given, or (once per pargs) a fresh one, echoed on stderr at --verbose >= 2 so the run can be repeated."""
+    if pargs.get("seed") is None:
+        pargs["seed"] = fresh_seed()
+        _log(pargs, 2, "Info", f"seed: {pargs['seed']} (fresh entropy; pass --seed {pargs['seed']} to reproduce this run)")
+    return pargs["seed"]
+
+
+def check_numeric_type(pargs: dict):
+    if pargs["numeric-type"] not in ("float64", *WIDE_TYPES):                       # mcmc_eap_chain.jl:195
+        raise ReferenceError_(f"numeric-type '{pargs['numeric-type']}' not understood")
+
+
+def burn_ladder(pargs: dict) -> list[float]:
+    """--burn-schedule of the two clustering mains: a Julia vector literal of kT multipliers."""
+    try:
+        return julia_vector(pargs["burn-schedule"])
+    except (ValueError, SyntaxError):
+        raise ReferenceError_(f"burn-schedule '{pargs['burn-schedule']}' not understood")
+
+
+def common_params(pargs: dict, num_chains: int, chain_id0: int, device: int, energy_types: dict, precisions: dict | None) -> dict:
+    """pargs -> the pstat_params fields every main sets, as keyword arguments of _lib.default_params, with the reference's
+    error() branches (inc/eap_chain.jl:81-105).  `energy_types` / `precisions`: what the main allows (None: it has no
+    --precision and sets the field itself); a main without --theta-step leaves that field alone."""
+    resolve_seed(pargs)
+    ct = {"dielectric": _lib.DIELECTRIC, "polar": _lib.POLAR}.get(pargs["chain-type"])
+    if ct is None:
+        raise ReferenceError_("chain-type is not understood.")                       # inc/eap_chain.jl:86
+    et = energy_types.get(pargs["energy-type"])
+    if et is None:
+        raise ReferenceError_("energy-type is not understood.")                      # inc/eap_chain.jl:104
+    own = {}
+    if precisions is not None:
+        own["precision"] = precisions.get(pargs["precision"])
+        if own["precision"] is None:
+            raise ReferenceError_(f"precision '{pargs['precision']}' not understood")
+    rng = {"mwc64x": _lib.RNG_MWC64X, "xoshiro128++": _lib.RNG_XOSHIRO128PP}.get(pargs["rng"])
+    if rng is None:
+        raise ReferenceError_(f"rng '{pargs['rng']}' not understood")
+    if "theta-step" in pargs:
+        own["theta_step"] = pargs["theta-step"]
+    return dict(
+        E0=pargs["E0"], K1=pargs["K1"], K2=pargs["K2"], mu=pargs["mu"], kT=pargs["kT"],
+        Fz=pargs["Fz"], Fx=pargs["Fx"], b=pargs["mlen"], phi_step=pargs["phi-step"],
+        adj_lb=pargs["step-adjust-lb"], adj_ub=pargs["step-adjust-ub"], adj_scale=pargs["step-adjust-scale"],
+        steps_per_adjust=pargs["steps-per-adjust"], n=pargs["num-monomers"], num_chains=num_chains,
+        seed=pargs["seed"], chain_id0=chain_id0, chain_type=ct, energy_type=et,
+        umbrella=1 if pargs["umbrella-sampling"] else 0, device=device, rng=rng,
+        uniform_bits=int(pargs.get("uniform-bits", 0)), **own)
+
+
+# ---------------------------------------------------------------------------------------------- averagers
+@dataclass
+class Averager:
+    """What the caller of mcmc() gets back in place of a StandardAverager (inc/average.jl:8-48)."""
+    value: object
+    stderr: object
+
+    def get_avg(self):
+        return self.value
+
+
+def get_avg(a: Averager):
+    return a.get_avg()
+
+
+def _averagers(s):
+    avg, se = np.array(s.avg), np.array(s.stderr)
+    sas = [Averager(avg[6], se[6]), Averager(avg[13], se[13]), Averager(avg[14], se[14]), Averager(avg[15], se[15])]
+    vas = [Averager(avg[0:3], se[0:3]), Averager(avg[3:6], se[3:6]), Averager(avg[7:10], se[7:10]),
+           Averager(avg[10:13], se[10:13])]
+    return sas, vas, s.acceptance_ratio
+
+
+# ---------------------------------------------------------------------------------------------- the pool
+class _Pool:
+    """The cases of one ensemble -- one for the command line, many for a sweep (polymer_stats_amd/sweep.py; they differ only
+    in their physics scalars, pstat_create) --, every case's chains sharded over one or more devices in this process;
+    reductions merged on the host (every entry of the reduction vector is additive).  `factory` is the main's
+    params_from_pargs.  As a context manager it closes its handles, and on success leaves the kernel's name in `info`."""
+
+    def __init__(self, pargs, factory, planar=False, info=None):
+        self.plist = plist = pargs if isinstance(pargs, list) else [pargs]
+        self.info = info
+        for p in plist:
+            resolve_seed(p)      # before the shards are made: every device gets the same seed, disjoint chain ids
+        p0 = plist[0]
+        self.numeric_type = p0.get("numeric-type", "float64")
+        if self.numeric_type != "float64":
+            # mcmc_eap_chain.jl:186-197 switches the averagers' accumulation type.  Here the per-chain sums are
+            # Float64 on the device (the reference's default); what the option changes is the merge over chains.
+            _log(p0, 2, "Warning", f"--numeric-type {self.numeric_type}: per-chain sums are Float64 on the device; the "
+                                   f"merge over chains is carried out in {WIDE_TYPES[self.numeric_type]}")
+        devices = [int(d) for d in str(p0["devices"]).split(",") if d != ""]
+        total = int(p0["num-chains"])
+        if total < 1:
+            raise ReferenceError_("num-chains must be >= 1")
+        devices = devices[:total] or [0]
+        base, extra = divmod(total, len(devices))
+        self.parts, self.counts = [], []
+        first = 0
+        for i, dev in enumerate(devices):
+            cnt = base + (1 if i < extra else 0)
+            self.parts.append(Ensemble([factory(p, cnt, first, dev) for p in plist], planar=planar))
+            self.counts.append(cnt)
+            first += cnt
+        self.steps = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        try:
+            if exc_type is None and self.info is not None:
+                self.info["kernel"] = self.kernel()
+        finally:
+            self.close()
+
+    def advance(self, n):
+        for e in self.parts:
+            e.advance(n)            # asynchronous: the devices run concurrently
+        self.steps += n
+
+    def reinit(self, force):
+        for e in self.parts:
+            e.reinit(force)
+
+    def burn_in(self, nsteps, multipliers):
+        """Run the temperature ladder (every case's own kT times the rung's multiplier) without keeping anything it records."""
+        for mult in multipliers:
+            for e in self.parts:
+                e.scale_kT(mult)
+            for e in self.parts:
+                e.advance(nsteps)
+        for e in self.parts:
+            e.scale_kT(1.0)
+            e.reset_averages()
+        self.steps = 0
+
+    def stage(self, mult):
+        """Start of a fresh mcmc(nsteps, pargs, chain) call of the clustering main: new temperature (kT x mult),
+        default step sizes, empty acceptor cache and averagers (mcmc_clustering_eap_chain.jl:172-181)."""
+        for e in self.parts:
+            e.scale_kT(mult)
+            e.reset_sampler()
+            e.reset_averages()
+        self.steps = 0
+
+    def recorded(self, nsteps, stepout, angles=False, tick=None):
+        """advance(nsteps), yielding after every `stepout`-th step (step, micro, ang, summaries): per case the microstate
+        [7] of its first chain, with `angles` that chain's theta[n] then phi[n], and its pooled summary.  The rows are
+        recorded on the device for all cases at once (Ensemble.advance_series) and come back a chunk at a time: shard
+        vectors are added as in summary(), the microstate is shard 0's.  `tick(step)` is called once per chunk.
+        --numeric-type other than float64 needs every chain's means at every row (summary()): it takes the per-row calls."""
+        ncases = len(self.plist)
+        nrows = nsteps // stepout if stepout > 0 else 0
+        if self.numeric_type != "float64":
+            for r in range(1, nrows + 1):
+                self.advance(stepout)
+                if tick:
+                    tick(r * stepout)
+                st = [self.chain0(k) for k in range(ncases)] if angles else None
+                yield (r * stepout, [self.microstate(k) for k in range(ncases)],
+                       [np.concatenate([c["theta"], c["phi"]]) for c in st] if angles else None,
+                       [self.summary(k) for k in range(ncases)])
+        elif nrows:
+            n = self.parts[0].n
+            row_bytes = 8 * ncases * (_lib.NRED + 7 + (2 * n if angles else 0))
+            chunk = min(nrows, max(1, SERIES_BUDGET_BYTES // row_bytes))
+            series = [e.open_series(chunk, angles=angles and i == 0) for i, e in enumerate(self.parts)]
+            try:
+                done = 0
+                while done < nrows:
+                    m = min(chunk, nrows - done)
+                    for e, s in zip(self.parts, series):
+                        e.advance_series(s, m * stepout, stepout)      # asynchronous: the devices run concurrently
+                    self.steps += m * stepout
+                    reads = [s.read() for s in series]
+                    for s in series:
+                        s.clear()
+                    steps, _, micro, ang = reads[0]
+                    red = np.zeros((m, ncases, _lib.NRED))
+                    for rd in reads:
+                        red += rd[1]
+                    if tick:
+                        tick((done + m) * stepout)
+                    for r in range(m):
+                        yield ((done + r + 1) * stepout, micro[r], ang[r] if angles else None,
+                               [summary_from_reduction(red[r, k], int(steps[r])) for k in range(ncases)])
+                    done += m
+            finally:
+                for s in series:
+                    s.close()
+        rest = nsteps - nrows * stepout      # not recorded
+        if rest > 0:
+            self.advance(rest)
+            if tick:
+                tick(nsteps)
+
+    def chain0(self, k=0):
+        return self.parts[0].chain_state(k * self.counts[0])      # the first chain of case k
+
+    def microstate(self, k=0):
+        return self.parts[0].microstate(k * self.counts[0])
+
+    def summary(self, k=0):
+        red = np.zeros(_lib.NRED)
+        for e in self.parts:
+            red += e.reduce_host(k)
+        s = summary_from_reduction(red, self.steps)
+        if self.numeric_type != "float64":
+            # --numeric-type: pooled mean and across-chain standard error re-done in the wide type from the per-chain
+            # means (the same quantities the device reduction folds in Float64)
+            m = np.concatenate([e.chain_means(k) for e in self.parts], axis=1).astype(np.longdouble)
+            C = m.shape[1]
+            mean = m.sum(axis=1) / C
+            se = np.sqrt(((m - mean[:, None]) ** 2).sum(axis=1) / (C - 1) / C) if C > 1 else np.zeros_like(mean)
+            for q in range(_lib.NOBS):
+                s.avg[q], s.stderr[q] = float(mean[q]), float(se[q])
+            s.acceptance_ratio, s.ar_stderr = float(mean[16]), float(se[16])
+            for q in range(2):
+                s.extra_avg[q], s.extra_stderr[q] = float(mean[17 + q]), float(se[17 + q])
+        return s
+
+    def report_failures(self, k, s):
+        """stderr only (stdout stays the reference's lines): what the reference hides -- proposals it rejected because
+        their energy was NaN/Inf, and chains sitting in a 1/r^3 singularity (no excluded volume, inc/eap_chain.jl:200-207)."""
+        pargs = self.plist[k]
+        who = f"{os.path.basename(pargs['prefix'])}: " if len(self.plist) > 1 else ""
+        if s.nan_rejects:
+            _log(pargs, 2, "Warning", f"{who}{s.nan_rejects} proposals had a non-finite energy and were rejected "
+                                      f"({s.nan_rejects / max(1.0, s.attempted_updates):.3g} of all attempts)")
+        if s.chains_collapsed:
+            _log(pargs, 2, "Warning", f"{who}{s.chains_collapsed} of {s.num_chains} chains have collapsed "
+                                      f"(|U| a thousand times beyond field + force + thermal energy: monomers on top of each other)")
+
+    def kernel(self) -> str:
+        return self.parts[0].launch_info().kernel.decode()
+
+    def close(self):
+        for e in self.parts:
+            e.close()
+
+
+# ---------------------------------------------------------------------------------------------- the two CSV files
+class CsvFiles:
+    """The `<prefix>_trajectory.csv` / `<prefix>_rolling.csv` pair of every case of an ensemble.  The reference holds its two
+    files open for the whole run (mcmc_eap_chain.jl:256-258,372-373); a batched sweep has thousands of cases, so the handles
+    stay open only while two per case fit the process's descriptor limit with room to spare -- beyond that every row is
+    appended by open/write/close (same bytes on disk)."""
+
+    def __init__(self, prefixes, traj_headers, roll_header):
+        try:
+            import resource
+            limit = resource.getrlimit(resource.RLIMIT_NOFILE)[0]
+        except Exception:
+            limit = 256
+        self.paths = [(f"{p}_trajectory.csv", f"{p}_rolling.csv") for p in prefixes]
+        self.keep_open = 2 * len(self.paths) <= max(0, limit - 64) // 2
+        self.handles = []
+        for (tp, rp), th in zip(self.paths, traj_headers):
+            ft, fr = open(tp, "w"), open(rp, "w")
+            ft.write(th + "\n")
+            fr.write(roll_header + "\n")
+            if self.keep_open:
+                self.handles.append((ft, fr))
+            else:
+                ft.close()
+                fr.close()
+
+    def __len__(self):
+        return len(self.paths)
+
+    def rows(self, k, traj_row, roll_row):
+        if self.keep_open:
+            ft, fr = self.handles[k]
+            ft.write(traj_row + "\n")
+            fr.write(roll_row + "\n")
+        else:
+            for path, row in zip(self.paths[k], (traj_row, roll_row)):
+                with open(path, "a") as f:
+                    f.write(row + "\n")
+
+    def close(self):
+        for ft, fr in self.handles:
+            ft.close()
+            fr.close()
+        self.handles = []
+
+
+def recorded_stage(pool, nsteps, write: bool, traj_header, roll_header, rows, angles=False, runs=(None,), report=None):
+    """One recorded run of `nsteps` for every case of the pool, the body of the reference's mcmc(nsteps, pargs[, chain]):
+    with `write` the two CSV files of every case (headers `traj_header(pargs)` and `roll_header`, a row per --stepout
+    steps: `rows(pargs, step, micro, ang, summary)` -> the case's (trajectory row, rolling row)), then the summaries, the
+    total time and the acceptance rates on stderr (`report(k, summary)` right after case k's rate).  `runs` yields the
+    progress line of each run of `nsteps` into the same files (the fixed-force main's inits; it is resumed after the run)."""
+    plist = pool.plist
+    pargs = plist[0]
+    stepout = int(pargs["stepout"]) if write else 0
+    files = None
+    try:
+        if write:
+            files = CsvFiles([p["prefix"] for p in plist], [traj_header(p) for p in plist], roll_header)
+        start = time.time()
+        last_update = [start]
+        for progress in runs:
+            def tick(step):                                             # per chunk of rows
+                if time.time() - last_update[0] > pargs["update-freq"]:
+                    _log(pargs, 3, "Info", f"elapsed: {time.time() - start}")
+                    if progress:
+                        _log(pargs, 3, "Info", progress)
+                    _log(pargs, 3, "Info", f"step:    {step} / {nsteps}")
+                    last_update[0] = time.time()
+            for step, micro, ang, sums in pool.recorded(nsteps, stepout, angles=angles, tick=tick):
+                for k in range(len(files)):
+                    files.rows(k, *rows(plist[k], step, micro[k], ang[k] if angles else None, sums[k]))
+        out = [pool.summary(k) for k in range(len(plist))]
+        _log(pargs, 3, "Info", f"total time elapsed: {time.time() - start}")
+        for k, s in enumerate(out):
+            _log(plist[k], 3, "Info", f"acceptance rate: {s.acceptance_ratio}")
+            if report:
+                report(k, s)
+        return out
+    finally:
+        if files:
+            files.close()
+
+
+# ---------------------------------------------------------------------------------------------- stdout
+def summary_lines(sas, vas, ar, pargs, extra=()) -> list[str]:
+    """The println lines every main ends with (mcmc_eap_chain.jl:386-395); `extra`: a main's own lines in front of AR."""
+    nb = pargs["mlen"] * pargs["num-monomers"]
+    return [
+        f"<r>    =   {jl_vector(get_avg(vas[0]))}",
+        f"<r/nb> =   {jl_vector(np.asarray(get_avg(vas[0])) / nb)}",
+        f"<rj2>  =   {jl_vector(get_avg(vas[1]))}",
+        f"<r2>   =   {jl_float(get_avg(sas[0]))}",
+        f"<p>    =   {jl_vector(get_avg(vas[2]))}",
+        f"<pj2>  =   {jl_vector(get_avg(vas[3]))}",
+        f"<p2>   =   {jl_float(get_avg(sas[1]))}",
+        f"<U>    =   {jl_float(get_avg(sas[2]))}",
+        f"<U2>   =   {jl_float(get_avg(sas[3]))}",
+        *extra,
+        f"AR     =   {jl_float(ar)}",
+    ]
+
+
+def main(pargs: dict, profile_message: str, run, lines) -> int:
+    """What a main does with its parsed command line: `run(pargs)` -> (scalar_averagers, vector_averagers, ar), printed."""
+    if pargs["profile"]:
+        raise ReferenceError_(profile_message)
+    sas, vas, ar = run(pargs)
+    for line in lines(sas, vas, ar, pargs):
+        print(line)
+    return 0

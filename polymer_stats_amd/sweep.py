@@ -8,7 +8,7 @@ writes the ten (twelve) stdout lines to `workdir/<name>.out` unless that file al
 then reads the values back out of the file NAMES and the stdout lines.
 
 Here the cases of a sweep that share everything but their physics scalars become ONE ensemble (`pstat_create` with
-ncases > 1) and one launch per stage of the main's protocol -- the hosts' own `mcmc_cases` / `run_cases`, which the command
+ncases > 1) and one launch per stage of the main's protocol -- the hosts' own `run_cases`, which the command
 line calls with one case --; cases are dealt to ranks round-robin (independent work, no exchange: `pmap`'s own partitioning),
 and every case's `.out` holds the lines the single-case host prints for the same options, seed and chains.
 
@@ -41,7 +41,7 @@ from . import _lib          # (tools/run_sweep.py counts the devices through it)
 from . import mcmc_clustering_eap_chain as cluster_main
 from . import mcmc_clustering_eap_chain_2d as planar_main
 from . import mcmc_eap_chain as fixed_main
-from .mcmc_eap_chain import ReferenceError_
+from ._host import ReferenceError_, arith, fresh_seed, number
 
 # (the planar main: 2D/run/Ising_2024-11-06.jl and its siblings launch 2D/mcmc_clustering_eap_chain.jl the same way)
 MAINS = {"mcmc_eap_chain": fixed_main, "mcmc_clustering_eap_chain": cluster_main, "mcmc_clustering_eap_chain_2d": planar_main}
@@ -56,29 +56,10 @@ PER_CASE = {"E0", "K1", "K2", "mu", "kT", "Fz", "Fx", "mlen", "bend-mod", "bend-
 
 
 # ---------------------------------------------------------------------------------------------- the case list
-_BIN = {ast.Add: lambda a, b: a + b, ast.Sub: lambda a, b: a - b, ast.Mult: lambda a, b: a * b, ast.Div: lambda a, b: a / b,
-        ast.Pow: lambda a, b: a ** b}
-
-
-def _arith(node) -> float:
-    if isinstance(node, ast.Constant) and isinstance(node.value, (int, float)) and not isinstance(node.value, bool):
-        return node.value
-    if isinstance(node, ast.UnaryOp) and isinstance(node.op, (ast.USub, ast.UAdd)):
-        v = _arith(node.operand)
-        return -v if isinstance(node.op, ast.USub) else v
-    if isinstance(node, ast.BinOp) and type(node.op) in _BIN:
-        return _BIN[type(node.op)](_arith(node.left), _arith(node.right))
-    raise ValueError("not a number")
-
-
-def _number(text: str):
-    return _arith(ast.parse(text.strip().replace("^", "**"), mode="eval").body)
-
-
 def julia_range(text: str) -> list:
     """`a:b` or `a:s:b` the way Julia enumerates it: a, a+s, ... while <= b (count from the rounded quotient, values
     as a + k*s -- Julia's own StepRangeLen is a shade more careful, equal to this to an ulp; names are rounded to 1e-3)."""
-    parts = [_number(p) for p in text.split(":")]
+    parts = [number(p) for p in text.split(":")]
     if len(parts) == 2:
         a, s, b = parts[0], 1, parts[1]
     elif len(parts) == 3:
@@ -103,7 +84,7 @@ def axis_values(text: str) -> list:
     out = []
     for item in t.split(","):
         if item.strip():
-            out += julia_range(item) if ":" in item else [_number(item)]
+            out += julia_range(item) if ":" in item else [number(item)]
     return out
 
 
@@ -135,7 +116,7 @@ def _cond(node, case):
         if node.id not in case:
             raise ValueError(f"--skip names '{node.id}', which is not a key of the cases")
         return case[node.id]
-    return _arith(node)
+    return arith(node)
 
 
 def skip_case(expr: str, case: dict) -> bool:
@@ -191,7 +172,7 @@ def plan(main_name: str, fixed_argv: list[str], cases: list[dict], workdir: str,
     if not cases:
         return []
     spec = name_spec(name, list(cases[0].keys()))
-    base = fixed_main.fresh_seed() & 0x7FFFFFFFFFFF if seed is None else int(seed)
+    base = fresh_seed() & 0x7FFFFFFFFFFF if seed is None else int(seed)
     extra = ["--num-chains", str(int(num_chains)), "--devices", str(int(device))]
     if precision:
         extra += ["--precision", precision]
@@ -239,10 +220,7 @@ def run_sweep(main_name: str, fixed_argv: list[str], cases: list[dict], workdir:
             plist = plist_all[i:i + per_launch]
             t0 = time.time()
             info = {}
-            if main is not fixed_main:    # the clustering mains' own protocol, every case of the ensemble at once
-                res = main.run_cases(plist, write_csv=write_csv, info=info)
-            else:
-                res = main.mcmc_cases(int(plist[0]["num-steps"]), plist, write_csv=write_csv, info=info)
+            res = main.run_cases(plist, write_csv=write_csv, info=info)    # the main's own protocol, every case of the ensemble at once
             for p, (sas, vas, ar) in zip(plist, res):
                 tmp = p["_out"] + f".tmp{os.getpid()}"
                 with open(tmp, "w") as f:           # println x 10 (12); complete or absent: an interrupted sweep re-runs the case

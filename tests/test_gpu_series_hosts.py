@@ -88,7 +88,7 @@ FIXED = [
 
 @pytest.mark.parametrize("argv", FIXED, ids=["remainder", "two-forced-inits", "two-inits-umbrella-f32"])
 def test_fixed_force_main_writes_the_per_row_loops_bytes(tmp_path, monkeypatch, argv):
-    from polymer_stats_amd import mcmc_eap_chain as host
+    from polymer_stats_amd import _host, mcmc_eap_chain as host
     argv = argv + ["-v", "0"]
     want = _fixed_force_twin(host, argv + ["--prefix", "unused"])
     assert want[0].count(b"\n") == 1 + host.parse_args(argv)["num-inits"] * (int(argv[argv.index("-N") + 1]) // int(argv[argv.index("-s") + 1]))
@@ -97,7 +97,7 @@ def test_fixed_force_main_writes_the_per_row_loops_bytes(tmp_path, monkeypatch, 
     # the same run with room for two rows, then one row, per chunk
     row_bytes = 8 * (host._lib.NRED + 7)
     for tag, budget in (("b", 2 * row_bytes + 8), ("c", 1)):
-        monkeypatch.setattr(host, "SERIES_BUDGET_BYTES", budget)
+        monkeypatch.setattr(_host, "SERIES_BUDGET_BYTES", budget)
         _run_main(host, argv + ["--prefix", str(tmp_path / tag)])
         assert _files(str(tmp_path / tag)) == want, budget
 
@@ -126,7 +126,7 @@ def test_fixed_force_main_sharded_over_two_handles(tmp_path):
 
 @pytest.mark.parametrize("energy,chains", [("Ising", "24"), ("interacting", "6")])
 def test_clustering_main_writes_the_per_row_loops_bytes(tmp_path, monkeypatch, energy, chains):
-    from polymer_stats_amd import mcmc_clustering_eap_chain as host, mcmc_eap_chain as fixed
+    from polymer_stats_amd import mcmc_clustering_eap_chain as host, _host as fixed
     argv = ["-n", "12", "-e", "1.0", "-J", "0.4", "-F", "0.5", "-u", energy, "-a", "0.5", "-g", "0.2", "--cluster-prob", "0.5",
             "-N", "1300", "--burn-in", "300", "--burn-schedule", "[10; 1]", "-s", "400", "-v", "0", "--num-chains", chains,
             "--seed", "4", "-S", "250"]

@@ -178,6 +178,32 @@ def test_cluster_output_shapes():
     np.testing.assert_allclose(mu, [[0.0, 0.0, 0.5]], atol=1e-15)   # n = x: mu = K2 E0 z
 
 
+# ------------------------------------------------------------------ the three hosts against their recorded tables
+def test_hosts_state_what_the_recorded_tables_hold():
+    """tests/golden/host_tables.json was recorded (tests/golden/make_host_tables.py) from the commit before the hosts' shared
+    text moved to polymer_stats_amd/_host.py: every parser action in order, every pstat_params field for command lines that
+    set all the options a main maps into the struct, the type and message of every error() branch, and the stdout lines.
+    The tree under test must produce exactly that."""
+    import importlib.util
+    import json
+    import os
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    spec = importlib.util.spec_from_file_location("make_host_tables", os.path.join(golden, "make_host_tables.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    with open(os.path.join(golden, "host_tables.json"), encoding="utf-8") as f:
+        want = json.load(f)
+    got = json.loads(gen.dumps(gen.tables()))
+    assert list(got) == list(want) == gen.MAINS
+    for name in gen.MAINS:
+        assert list(got[name]) == list(want[name]) == ["options", "params", "errors", "summary"]
+        for section in want[name]:
+            assert len(got[name][section]) == len(want[name][section]), (name, section)
+            for g, w in zip(got[name][section], want[name][section]):
+                assert g == w, (name, section, g, w)
+        assert all(e["type"] is not None for e in want[name]["errors"])          # every recorded branch did raise
+
+
 # ------------------------------------------------------------------ seed contract
 def test_default_seed_is_fresh_entropy_and_echoed(capsys):
     """The reference never seeds its RNG (its sweeps launch one command 25x and use the scatter,

@@ -96,7 +96,7 @@ def main():
         # drawn HERE: every rank must name the same seed for case k
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         from rank_spawn import spawn_ranks
-        extra = [] if args.seed is not None else ["--seed", str(sw.fixed_main.fresh_seed() & 0x7FFFFFFFFFFF)]
+        extra = [] if args.seed is not None else ["--seed", str(sw.fresh_seed() & 0x7FFFFFFFFFFF)]
         pre = sys.argv[1:sys.argv.index("--")] if "--" in sys.argv else sys.argv[1:]
         agg = bool(args.aggregate)              # the ranks only run; the parent aggregates when all of them are done
         kept, skip = [], False

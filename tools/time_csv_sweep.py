@@ -6,7 +6,8 @@ spent formatting text.  The grid of run/K1_E0-kT-phase.jl, fixe
     python tools/time_csv_sweep.py WORKDIR --tree OTHER_CHECKOUT  # the same sweep through another checkout's package
 
 `--tree` names a checkout (with a built libpstat.so) whose polymer_stats_amd is imported instead of this one's: the two are
-compared by running them one after the other.  jl_row -- every row of both files goes through it -- is wrapped with a clock.
+compared by running them one after the other.  jl_row -- every row of both files goes through it -- is wrapped with a clock
+in every module of the imported package that holds it, wherever that checkout formats its rows.
 Prints one JSON line."""
 import argparse
 import json
@@ -23,7 +24,7 @@ def main():
     ap.add_argument("-n", type=int, default=100)
     ap.add_argument("--steps", type=int, default=250000)
     ap.add_argument("--stepout", type=int, default=250)
-    ap.add_argument("--main", default="mcmc_eap_chain", choices=["mcmc_eap_chain", "mcmc_clustering_eap_chain"])
+    ap.add_argument("--main", default="mcmc_eap_chain", choices=["mcmc_eap_chain", "mcmc_clustering_eap_chain", "mcmc_clustering_eap_chain_2d"])
     args = ap.parse_args()
     sys.path.insert(0, os.path.abspath(args.tree))
     from polymer_stats_amd import sweep as sw, julia_fmt
@@ -38,8 +39,9 @@ def main():
         spent[1] += 1
         return out
 
-    for mod in (sw.fixed_main, sw.cluster_main):
-        mod.jl_row = timed_row
+    for name, mod in list(sys.modules.items()):
+        if name.startswith("polymer_stats_amd.") and hasattr(mod, "jl_row"):
+            mod.jl_row = timed_row
     cases = sw.product_cases([("kT", sw.axis_values("10^(-2:0.2:2)")), ("E0", sw.axis_values("0:0.2:5")), ("K1", [1]), ("K2", [0]),
                               ("n", [args.n])])
     fixed = ["--chain-type", "dielectric", "--energy-type", "Ising", "--num-steps", str(args.steps), "--stepout", str(args.stepout),
