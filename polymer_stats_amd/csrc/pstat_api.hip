@@ -15,6 +15,7 @@
 #include "../../include/pstat.h"
 #include "pstat_cluster_common.h"
 #include "pstat_device.h"
+#include "pstat_math.h"
 
 using namespace pstat;
 
@@ -1076,25 +1077,13 @@ int pstat_chain_state(pstat_handle *h, int64_t chain, double *angles, double sum
     HIP_TRY(hipMemcpy2D(tmp.get(), h->elem, (char *)h->S.ang + (size_t)chain * h->elem, C * h->elem,
                         h->elem, 2 * n, hipMemcpyDeviceToHost));
     // storage formats: pstat_math.h (radians | turns | lattice index); the ABI speaks radians
-    for (size_t i = 0; i < 2 * n; ++i) {
-      const bool is_theta = i < n;
-      if (h->elem == 8) angles[i] = ((double *)tmp.get())[i];
-      else if (h->elem == 4) angles[i] = (double)((float *)tmp.get())[i] * 6.28318530717958647692;
-      else angles[i] = (is_theta ? 3.14159265358979323846 : 6.28318530717958647692) *
-                       ((double)((uint16_t *)tmp.get())[i] + 0.5) / 65536.0;
-    }
+    for (size_t i = 0; i < 2 * n; ++i) angles[i] = load_angle(tmp.get(), (int64_t)i, h->elem, i < n);
   }
   if (sums) {
     double s[NSUMS];
     HIP_TRY(hipMemcpy2D(s, sizeof(double), h->S.sums + chain, C * sizeof(double), sizeof(double), NSUMS,
                         hipMemcpyDeviceToHost));
-    sums[PSTAT_R1] = s[S_R1]; sums[PSTAT_R2] = s[S_R2]; sums[PSTAT_R3] = s[S_R3];
-    sums[PSTAT_R1SQ] = s[S_R1SQ]; sums[PSTAT_R2SQ] = s[S_R2SQ]; sums[PSTAT_R3SQ] = s[S_R3SQ];
-    sums[PSTAT_RSQ] = s[S_R1SQ] + s[S_R2SQ] + s[S_R3SQ];
-    sums[PSTAT_P1] = s[S_P1]; sums[PSTAT_P2] = s[S_P2]; sums[PSTAT_P3] = s[S_P3];
-    sums[PSTAT_P1SQ] = s[S_P1SQ]; sums[PSTAT_P2SQ] = s[S_P2SQ]; sums[PSTAT_P3SQ] = s[S_P3SQ];
-    sums[PSTAT_PSQ] = s[S_P1SQ] + s[S_P2SQ] + s[S_P3SQ];
-    sums[PSTAT_U] = s[S_U]; sums[PSTAT_USQ] = s[S_USQ];
+    sums_in_abi_order(s, 1, sums);
   }
   if (counters) {
     int64_t w[2];
@@ -1132,24 +1121,7 @@ int pstat_chain_means(pstat_handle *h, int32_t icase, double *out) {
                         hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(nacc.data(), h->S.nacc_total + c0, m * sizeof(int64_t), hipMemcpyDeviceToHost));
     if (h->cfg.umbrella) HIP_TRY(hipMemcpy(wn.data(), h->S.wnorm + c0, m * sizeof(double), hipMemcpyDeviceToHost));
-    const double steps = (double)h->steps_recorded;
-    // same arithmetic as reduce_stage1 (pstat_kernels.hip)
-    static const int src[PSTAT_NOBS] = {S_R1, S_R2, S_R3, S_R1SQ, S_R2SQ, S_R3SQ, -1, S_P1, S_P2, S_P3,
-                                        S_P1SQ, S_P2SQ, S_P3SQ, -2, S_U, S_USQ};
-    for (size_t k = 0; k < m; ++k) {
-      const double norm = h->cfg.umbrella ? wn[k] : steps;
-      const double inv = norm != 0.0 ? 1.0 / norm : 0.0;
-      for (int q = 0; q < PSTAT_NOBS; ++q) {
-        double v;
-        if (src[q] == -1) v = sums[S_R1SQ * m + k] + sums[S_R2SQ * m + k] + sums[S_R3SQ * m + k];
-        else if (src[q] == -2) v = sums[S_P1SQ * m + k] + sums[S_P2SQ * m + k] + sums[S_P3SQ * m + k];
-        else v = sums[(size_t)src[q] * m + k];
-        out[(size_t)q * m + k] = v * inv;
-      }
-      out[16 * m + k] = steps > 0 ? (double)nacc[k] / steps : 0.0;
-      out[17 * m + k] = sums[S_C2 * m + k] * inv;
-      out[18 * m + k] = sums[S_PSI * m + k] * inv;
-    }
+    chain_means_host(sums.data(), h->cfg.umbrella ? wn.data() : nullptr, nacc.data(), h->steps_recorded, (int64_t)m, out);
   } catch (const std::bad_alloc &) {
     return fail(PSTAT_ERR_NOMEM, "host allocation failed");
   }

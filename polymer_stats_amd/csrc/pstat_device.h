@@ -317,7 +317,7 @@ StepKernel planar_step_kernel(const LaunchCfg &cfg, int64_t n);        // Planar
 // bytes of DevState::work for home ClusterMem
 size_t cluster_gm_work_bytes(const LaunchCfg &cfg, const SweepArgs &a);
 
-// initialisation, re-initialisation and reduction (pstat_kernels.hip)
+// initialisation and re-initialisation (pstat_kernels.hip)
 hipError_t launch_init(const LaunchCfg &cfg, const SweepArgs &a, const DevState &s,
                        const CaseConst *cases, double phi_step, double theta_step,
                        const InitOpts &io, hipStream_t stream);
@@ -329,15 +329,21 @@ hipError_t launch_reinit(const LaunchCfg &cfg, const SweepArgs &a, const DevStat
                          const CaseConst *cases, int force_init, hipStream_t stream);
 // true iff x is NaN or +-Inf (one v_cmp_class)
 template <typename R> __host__ __device__ inline bool not_finite(R x) { return !__builtin_isfinite(x); }
+// The ensemble reduction (pstat_reduce.hip), kernels and host statements of the same arithmetic.
 // reduction of chains [c0, c1) into out[PSTAT_NRED]; partial = scratch of reduce_scratch_doubles()
 hipError_t launch_reduce(const DevState &s, int64_t c0, int64_t c1, int64_t steps_recorded,
                          int umbrella, const CaseConst *cases, int64_t chains_per_case, int64_t n,
                          double *partial, double *out, hipStream_t stream);
 size_t reduce_scratch_doubles();
-// one row of a series (pstat_series.hip): for every case k of the handle, red[k][PSTAT_NRED] = what launch_reduce gives for
+// one row of a series: for every case k of the handle, red[k][PSTAT_NRED] = what launch_reduce gives for
 // the case's chains, micro[k][7] = obs of the case's first chain, and, unless angles is null, angles[k][2n] = that chain's
 // theta then phi in radians
 hipError_t launch_record(const LaunchCfg &cfg, const SweepArgs &a, const DevState &s, const CaseConst *cases,
                          int64_t steps_recorded, double *red, double *micro, double *angles, hipStream_t stream);
+// host: out[PSTAT_NOBS] = the sums in include/pstat.h order from the S_* rows of a [NSUMS][stride] array
+void sums_in_abi_order(const double *sums, int64_t stride, double *out);
+// host: out[PSTAT_NQ][m] = the mean vectors the reduction folds, of m chains gathered as sums[NSUMS][m], nacc[m] and, under
+// umbrella sampling, wnorm[m] (null otherwise: the normaliser is `steps`)
+void chain_means_host(const double *sums, const double *wnorm, const int64_t *nacc, int64_t steps, int64_t m, double *out);
 
 }  // namespace pstat

@@ -931,93 +931,6 @@ __global__ __launch_bounds__(64) void sweep_kernel(SweepArgs A, DevState S,
 }
 
 #ifndef PSTAT_PART
-// ------------------------------------------------------------------------------------------ reduce
-
-constexpr int RED_BLOCKS = 256;
-constexpr int RED_THREADS = 256;
-constexpr int NQ = 19;  // 16 observables + acceptance ratio + the clustering main's two extras
-constexpr int NX = 2;   // plain sums: non-finite-energy rejections, collapsed chains (pstat.h)
-constexpr int NP = 2 * NQ + NX;   // entries of one block's partial
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
-// stage 1: every block folds a strided slice of chains into partial[block][2*NQ] (deterministic)
-__global__ __launch_bounds__(RED_THREADS) void reduce_stage1(DevState S, int64_t c0, int64_t c1,
-                                                             int64_t steps, int umbrella,
-                                                             const CaseConst *__restrict__ cases,
-                                                             int64_t chains_per_case, int64_t n,
-                                                             double *__restrict__ partial) {
-  __shared__ double red[RED_THREADS / 64][NP];
-  double m1[NQ], m2[NQ], mx[NX] = {0, 0};
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) { m1[q] = 0; m2[q] = 0; }
-  const int64_t C = S.C;
-  for (int64_t c = c0 + (int64_t)blockIdx.x * RED_THREADS + threadIdx.x; c < c1;
-       c += (int64_t)RED_BLOCKS * RED_THREADS) {
-    const double norm = umbrella ? S.wnorm[c] : (double)steps;
-    const double inv = norm != 0.0 ? 1.0 / norm : 0.0;
-    double v[NQ];
-    v[PSTAT_R1] = S.sums[S_R1 * C + c]; v[PSTAT_R2] = S.sums[S_R2 * C + c]; v[PSTAT_R3] = S.sums[S_R3 * C + c];
-    v[PSTAT_R1SQ] = S.sums[S_R1SQ * C + c]; v[PSTAT_R2SQ] = S.sums[S_R2SQ * C + c];
-    v[PSTAT_R3SQ] = S.sums[S_R3SQ * C + c];
-    v[PSTAT_RSQ] = v[PSTAT_R1SQ] + v[PSTAT_R2SQ] + v[PSTAT_R3SQ];
-    v[PSTAT_P1] = S.sums[S_P1 * C + c]; v[PSTAT_P2] = S.sums[S_P2 * C + c]; v[PSTAT_P3] = S.sums[S_P3 * C + c];
-    v[PSTAT_P1SQ] = S.sums[S_P1SQ * C + c]; v[PSTAT_P2SQ] = S.sums[S_P2SQ * C + c];
-    v[PSTAT_P3SQ] = S.sums[S_P3SQ * C + c];
-    v[PSTAT_PSQ] = v[PSTAT_P1SQ] + v[PSTAT_P2SQ] + v[PSTAT_P3SQ];
-    v[PSTAT_U] = S.sums[S_U * C + c]; v[PSTAT_USQ] = S.sums[S_USQ * C + c];
-#pragma unroll
-    for (int q = 0; q < PSTAT_NOBS; ++q) v[q] *= inv;
-    v[16] = steps > 0 ? (double)S.nacc_total[c] / (double)steps : 0.0;
-    v[17] = S.sums[S_C2 * C + c] * inv;    // sum cos^2(theta)
-    v[18] = S.sums[S_PSI * C + c] * inv;   // mean bond angle
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) { m1[q] += v[q]; m2[q] = fma(v[q], v[q], m2[q]); }
-    mx[0] += (double)S.nanrej[c];
-    // collapsed: |U| of the current configuration is 1e3 times beyond what n separated monomers can hold in field,
-    // force and thermal energy -- only a 1/r^3 contact gets there (pstat.h, pstat_summary.chains_collapsed)
-    const CaseConst &cc = cases[c / chains_per_case];
-    const double mu_max = fmax(fmax(fabs(cc.K1), fabs(cc.K2)) * fabs(cc.E0), fabs(cc.mu));
-    const double per_monomer = cc.kT + 0.5 * fabs(cc.E0) * mu_max + fabs(cc.b) * (fabs(cc.Fx) + fabs(cc.Fz));
-    mx[1] += !(fabs(S.obs[OBS_U * C + c]) <= 1e3 * (double)n * per_monomer) ? 1.0 : 0.0;
-  }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) {
-    double a = wave_sum(m1[q]), b = wave_sum(m2[q]);
-    if (lane == 0) { red[wave][q] = a; red[wave][NQ + q] = b; }
-  }
-#pragma unroll
-  for (int q = 0; q < NX; ++q) {
-    double a = wave_sum(mx[q]);
-    if (lane == 0) red[wave][2 * NQ + q] = a;
-  }
-  __syncthreads();
-  if (threadIdx.x < NP) {
-    double t = 0;
-#pragma unroll
-    for (int w = 0; w < RED_THREADS / 64; ++w) t += red[w][threadIdx.x];
-    partial[blockIdx.x * NP + threadIdx.x] = t;
-  }
-}
-
-// stage 2: one wave per output folds the RED_BLOCKS partials in a fixed order
-__global__ __launch_bounds__(64) void reduce_stage2(const double *__restrict__ partial,
-                                                    int64_t nchains, double *__restrict__ out) {
-  const int q = blockIdx.x;  // 0 .. NP-1
-  double t = 0;
-  for (int blk = threadIdx.x; blk < RED_BLOCKS; blk += 64) t += partial[blk * NP + q];
-  t = wave_sum(t);
-  if (threadIdx.x == 0) {
-    out[1 + q] = t;
-    if (q == 0) out[0] = (double)nchains;
-  }
-}
-
 // ------------------------------------------------------------------------------------------ re-init
 
 // What a fresh mcmc(nsteps, pargs, chain) call starts from (mcmc_clustering_eap_chain.jl:172-181):
@@ -1208,20 +1121,6 @@ hipError_t launch_reinit(const LaunchCfg &cfg, const SweepArgs &a, const DevStat
   const unsigned grid = (unsigned)((s.C + 255) / 256);
   if (cfg.rng == PSTAT_RNG_XOSHIRO128PP) launch_reinit_g<Xoshiro128pp>(cfg, a, s, cases, force_init, grid, stream);
   else launch_reinit_g<Mwc64x>(cfg, a, s, cases, force_init, grid, stream);
-  return hipGetLastError();
-}
-
-size_t reduce_scratch_doubles() { return (size_t)RED_BLOCKS * NP; }
-static_assert(NQ == PSTAT_NQ && NX == PSTAT_NX && 1 + NP == PSTAT_NRED, "reduction layout of include/pstat.h");
-
-hipError_t launch_reduce(const DevState &s, int64_t c0, int64_t c1, int64_t steps_recorded,
-                         int umbrella, const CaseConst *cases, int64_t chains_per_case, int64_t n,
-                         double *partial, double *out, hipStream_t stream) {
-  hipLaunchKernelGGL(reduce_stage1, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, stream, s, c0, c1,
-                     steps_recorded, umbrella, cases, chains_per_case, n, partial);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(reduce_stage2, dim3(NP), dim3(64), 0, stream, partial, c1 - c0, out);
   return hipGetLastError();
 }
 

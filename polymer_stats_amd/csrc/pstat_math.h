@@ -277,6 +277,15 @@ template <typename T> __host__ __device__ inline double load_theta(T raw) {   //
   else if constexpr (sizeof(T) == 4) return 6.28318530717958647692 * (double)raw;
   else return (double)raw;
 }
+// element `at` of a stored angle plane of `elem` bytes per angle (8 radians | 4 turns | 2 lattice index) -> radians
+template <typename T> __host__ __device__ inline double load_angle_as(const void *ang, int64_t at, bool is_theta) {
+  const T raw = ((const T *)ang)[at];
+  return is_theta ? load_theta<T>(raw) : load_phi<T>(raw);
+}
+__host__ __device__ inline double load_angle(const void *ang, int64_t at, size_t elem, bool is_theta) {
+  return elem == 8 ? load_angle_as<double>(ang, at, is_theta)
+                   : elem == 4 ? load_angle_as<float>(ang, at, is_theta) : load_angle_as<uint16_t>(ang, at, is_theta);
+}
 // lattice index -> turns, exactly, without the quarter-rate v_cvt_f32_u32: 0x4B000000 | m is the
 // float 2^23 + m
 __device__ __forceinline__ float q16_theta_turns(uint32_t k) {  // (2k+1) 2^-18

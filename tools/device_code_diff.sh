@@ -7,7 +7,8 @@
 # directives).  The listing is cut into one block per symbol, instruction addresses are dropped (encodings and
 # symbol-relative branch targets stay), and the blocks are sorted by symbol name, because the order of instantiation inside
 # an object may move.  Equal means: the same set of symbols, the same instruction text for each, the same descriptor for
-# each kernel.  Prints a summary and exits 0 when equal; prints the diff's head and exits 1 otherwise.
+# each kernel.  Prints a summary and exits 0 when equal; otherwise prints the name of every symbol that differs
+# or that only one build has (a kernel whose parameter types changed has another mangled name), the diff's head, and exits 1.
 set -euo pipefail
 [ $# -eq 2 ] || { echo "usage: $0 A/libpstat.so B/libpstat.so" >&2; exit 2; }
 LLVM=${LLVM:-/opt/rocm/llvm/bin}
@@ -43,10 +44,12 @@ listing() {   # $1 library, $2 work directory -> $2/listing: "symbol <tab> line"
 listing "$1" "$TMP/a"
 listing "$2" "$TMP/b"
 if ! diff <(cut -f1 "$TMP/a/listing" | uniq) <(cut -f1 "$TMP/b/listing" | uniq) > "$TMP/symdiff"; then
-  echo "DIFFERENT: the sets of symbols differ"; head -20 "$TMP/symdiff"; exit 1
+  echo "DIFFERENT: the sets of symbols differ"; head -20 "$TMP/symdiff"
 fi
 if ! diff "$TMP/a/listing" "$TMP/b/listing" > "$TMP/diff"; then
-  echo "DIFFERENT: $(cut -f1 "$TMP/diff" | grep '^[<>]' | sed 's/^[<>] //' | sort -u | wc -l) symbols differ"
+  cut -f1 "$TMP/diff" | grep '^[<>]' | sed 's/^[<>] //' | LC_ALL=C sort -u > "$TMP/names"
+  echo "DIFFERENT: $(wc -l < "$TMP/names") symbols differ"
+  cat "$TMP/names"
   head -40 "$TMP/diff"; exit 1
 fi
 echo "IDENTICAL: same symbols, same instructions per symbol, same kernel descriptors (compared per symbol, sorted by name)"
