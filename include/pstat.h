@@ -291,7 +291,7 @@ int pstat_microstate(pstat_handle *h, int64_t chain, double out[7]);
 
 /* The quantities printed at mcmc_eap_chain.jl:365,386-395.  Synchronises.  Like every accessor that
  * synchronises (pstat_sync, pstat_reduce_host, pstat_rolling, pstat_microstate, pstat_chain_state,
- * pstat_chain_extras, pstat_checkpoint, pstat_series_read) it fails with PSTAT_ERR_HIP if a launch since the last successful
+ * pstat_chain_extras, pstat_checkpoint, pstat_series_read, pstat_series_error_bars) it fails with PSTAT_ERR_HIP if a launch since the last successful
  * call did not run to completion (a job of the persistent kernels timed out waiting for its predecessor):
  * the handle's averages are then not the averages of the steps it was asked for. */
 int pstat_summary_get(pstat_handle *h, int32_t icase, pstat_summary *out);
@@ -329,6 +329,53 @@ int pstat_series_read(pstat_handle *h, pstat_series *s, int64_t nrows, int64_t *
                       double *angles /* [nrows][ncases][2n] */);
 int pstat_series_clear(pstat_handle *h, pstat_series *s);
 void pstat_series_close(pstat_handle *h, pstat_series *s);
+
+/* Error bars from one run: blocked standard errors (Flyvbjerg & Petersen, J. Chem. Phys. 91, 461 (1989)) of the batch means
+ * between the rows of a series, computed on the device; the series is not copied to the host.  The reference has no
+ * equivalent: its author gets uncertainties by repeating runs (2D/run/Ising_2024-11-06.jl: run=1:10).
+ * The estimator, for one column of N batch values (DESIGN.md 3.12 states it in full):
+ *   level 0 is the column; level l+1 averages neighbours, x'[j] = (x[2j] + x[2j+1]) / 2, a trailing odd value dropped; levels
+ *   exist while N_l >= 2, at most PSTAT_BLOCK_LEVELS.  se_l = sqrt(sum (x - m_l)^2 / (N_l - 1) / N_l) about the level's own
+ *   mean m_l.  Among the levels with N_l >= min_blocks the one of largest se_l is picked (the lowest on ties);
+ *   converged = 0 if that is the last such level AND se rose into it by more than its own uncertainty, se_l* - se_(l*-1) >
+ *   se_l* / sqrt(2 (N_l* - 1)), or it is level 0: the curve is still rising, the run is too short for this observable.  (The
+ *   last level alone would flag a third of the columns of an amply long series: on the plateau the largest se falls on the
+ *   noisiest level.)
+ *   A non-finite se_l among them: stderr, stderr_err, inefficiency = NaN, level = -1, converged = 0.  se_0 == 0 (a constant
+ *   column, e.g. the y slots of a planar handle): stderr = 0, inefficiency = 1, level = 0, converged = 1.
+ * Per column PSTAT_EB_FIELDS doubles: mean m_0, stderr se_l*, stderr_err se_l* / sqrt(2 (N_l* - 1)), inefficiency
+ * (se_l* / se_0)^2, level l*, converged; `levels` (may be NULL): se_l of every level, 0 beyond the last.
+ *
+ *   pstat_series_error_bars  the columns are the PSTAT_NQ quantities of every case in the order of the reduction vector
+ *       (16 observables, acceptance ratio, sum cos^2 theta, mean bond angle), the batches the differences of consecutive rows
+ *       among [first_row, first_row + nrows): with S_r = red[r][k][1 + q] * steps[r] and d the rows' common spacing in steps,
+ *       batch = (S_r - S_{r-1}) / (d * red[r][k][0]).  If steps[first_row] == d the series began at empty averages (creation,
+ *       pstat_reset_averages): the baseline is zero and nrows rows give nrows batches; otherwise the first row is the
+ *       baseline and they give nrows - 1.  *nbatches receives the count.  Synchronises, and fails like every accessor that
+ *       does after an incomplete launch.  Every precision and every home, planar handles included.
+ *       PSTAT_ERR_INVALID_ARG: a series of another handle; a row range outside the recorded rows; rows that are not equally
+ *       spaced and increasing (two pstat_advance_series calls of different stepout, a pstat_reset_averages between rows: the
+ *       message names the row); min_blocks < 2 other than 0.  PSTAT_ERR_TOO_SMALL: fewer batches than min_blocks (the
+ *       count is written to *nbatches).  PSTAT_ERR_UNSUPPORTED: more than PSTAT_BLOCK_MAX_BATCHES batches (level 1 of a column
+ *       must fit the LDS of a CU); an umbrella-sampling handle -- its recorded means are ratios value / normalizer with
+ *       per-chain normalizers that the rows do not hold, so the rows' differences are not batch means.
+ *   pstat_blocking_device    the same transform of any matrix x[nbatches][stride] in DEVICE memory of which the first `ncols`
+ *       columns are taken (e.g. a torch tensor, or series merged over ranks), on `device` and on `stream` (NULL: the default
+ *       stream); synchronises the stream and leaves the calling thread's current device as it found it.  The argument errors
+ *       above plus stride < ncols, all raised before the device is touched.
+ * NB the constant-column rule holds for se_0 == 0 exactly: a column of one value whose sums are exact (0, 2.5, ...).  A
+ * constant that is not (0.1, say) leaves a rounding-noise stderr of ~1e-17 relative, and level / converged of that noise. */
+#define PSTAT_BLOCK_LEVELS 24
+#define PSTAT_BLOCK_MAX_BATCHES 40960
+enum { PSTAT_EB_MEAN, PSTAT_EB_STDERR, PSTAT_EB_STDERR_ERR, PSTAT_EB_INEFFICIENCY, PSTAT_EB_LEVEL, PSTAT_EB_CONVERGED,
+       PSTAT_EB_FIELDS };
+int pstat_series_error_bars(pstat_handle *h, pstat_series *s, int64_t first_row, int64_t nrows /* < 0: to the last row */,
+                            int32_t min_blocks /* 0: 32 */, int64_t *nbatches /* out, may be NULL */,
+                            double *out /* host [ncases][PSTAT_NQ][PSTAT_EB_FIELDS] */,
+                            double *levels /* host [ncases][PSTAT_NQ][PSTAT_BLOCK_LEVELS] or NULL */);
+int pstat_blocking_device(const double *x /* DEVICE memory, [nbatches][stride] */, int64_t nbatches, int64_t ncols, int64_t stride,
+                          int32_t min_blocks, int32_t device, void *stream, double *out /* host [ncols][PSTAT_EB_FIELDS] */,
+                          double *levels /* host [ncols][PSTAT_BLOCK_LEVELS] or NULL */);
 
 /* Per-chain accessors for tests and tooling (host buffers).  angles: theta[n] then phi[n] as
  * doubles, radians; sums: the 16 per-chain running sums in rolling.csv order;

@@ -199,6 +199,32 @@ def check_numeric_type(pargs: dict):
         raise ReferenceError_(f"numeric-type '{pargs['numeric-type']}' not understood")
 
 
+def check_error_bars(pargs: dict, nbatches: int, write_csv: bool = False, devices: int | None = None):
+    """What --error-bars N (tools/run_sweep.py; run_cases(..., error_bars=N)) cannot be combined with, refused before any
+    GPU work.  `devices`: how many hold the chains (default: those --devices names)."""
+    if devices is None:
+        devices = len([d for d in str(pargs["devices"]).split(",") if d != ""][:max(1, int(pargs["num-chains"]))])
+    if nbatches < 32:
+        raise ReferenceError_(f"--error-bars {nbatches}: the blocking transform needs at least 32 batches")
+    if int(pargs["num-steps"]) < nbatches:
+        raise ReferenceError_(f"--error-bars {nbatches} needs --num-steps >= {nbatches}: a batch is num-steps / {nbatches} steps")
+    if write_csv:
+        raise ReferenceError_("--error-bars cannot be combined with --csv: the production run is recorded as batches, not as "
+                              "--stepout rows")
+    if devices > 1:
+        raise ReferenceError_(f"--error-bars needs one device, not {devices}: the devices hold different chains of a case and "
+                              "their series are not merged")
+    if int(pargs.get("num-inits", 1)) != 1:
+        raise ReferenceError_(f"--error-bars cannot be combined with --num-inits {pargs['num-inits']}: a re-initialisation "
+                              "between batches is not a stationary series")
+    if pargs["umbrella-sampling"]:
+        raise ReferenceError_("--error-bars cannot be combined with --umbrella-sampling: the recorded means are ratios with "
+                              "per-chain normalizers that the rows do not hold")
+    if pargs["numeric-type"] != "float64":
+        raise ReferenceError_(f"--error-bars cannot be combined with --numeric-type {pargs['numeric-type']}: the batches are "
+                              "differences of the device's Float64 reductions")
+
+
 def burn_ladder(pargs: dict) -> list[float]:
     """--burn-schedule of the two clustering mains: a Julia vector literal of kT multipliers."""
     try:
@@ -386,6 +412,30 @@ class _Pool:
             if tick:
                 tick(nsteps)
 
+    def error_bars(self, nsteps, nbatches):
+        """advance(nsteps), recorded on the device as exactly `nbatches` batches of nsteps // nbatches steps (no angles; the
+        remainder, nsteps % nbatches steps, is not part of any batch) -> the blocked standard errors of every case
+        (Series.error_bars).  Called where the
+        averages are empty (after burn_in / stage / creation), so the rows' differences are the batch means.  The chains
+        are sharded over one device only: the shards of a case hold different chains, and their series are not merged.
+        The run is made TWICE from the same state: recorded for the error bars, then, from a checkpoint taken before it, as
+        the one launch of advance(nsteps), which leaves the handle -- and so the averages the caller prints -- exactly as
+        a run without error bars does.  (Recording leaves trajectories alone, but N launches add the running sums in another
+        order than one launch: the step kernels fold them in blocks that start at a launch's first step.)"""
+        check_error_bars(self.plist[0], nbatches, devices=len(self.parts))
+        e = self.parts[0]
+        image = e.checkpoint()
+        series = e.open_series(nbatches)
+        try:
+            q = nsteps // nbatches
+            e.advance_series(series, nbatches * q, q)      # (the remainder would be lost with the restore anyway)
+            eb = series.error_bars()
+        finally:
+            series.close()
+        e.restore(image)
+        self.advance(nsteps)
+        return eb
+
     def chain0(self, k=0):
         return self.parts[0].chain_state(k * self.counts[0])      # the first chain of case k
 
@@ -477,12 +527,15 @@ class CsvFiles:
         self.handles = []
 
 
-def recorded_stage(pool, nsteps, write: bool, traj_header, roll_header, rows, angles=False, runs=(None,), report=None):
+def recorded_stage(pool, nsteps, write: bool, traj_header, roll_header, rows, angles=False, runs=(None,), report=None,
+                   error_bars: int = 0):
     """One recorded run of `nsteps` for every case of the pool, the body of the reference's mcmc(nsteps, pargs[, chain]):
     with `write` the two CSV files of every case (headers `traj_header(pargs)` and `roll_header`, a row per --stepout
     steps: `rows(pargs, step, micro, ang, summary)` -> the case's (trajectory row, rolling row)), then the summaries, the
     total time and the acceptance rates on stderr (`report(k, summary)` right after case k's rate).  `runs` yields the
-    progress line of each run of `nsteps` into the same files (the fixed-force main's inits; it is resumed after the run)."""
+    progress line of each run of `nsteps` into the same files (the fixed-force main's inits; it is resumed after the run).
+    `error_bars` = N > 0 (without `write`): the run is recorded as N batches instead (_Pool.error_bars) and the pool's `info`
+    gets their blocked standard errors under "error_bars"."""
     plist = pool.plist
     pargs = plist[0]
     stepout = int(pargs["stepout"]) if write else 0
@@ -500,6 +553,11 @@ def recorded_stage(pool, nsteps, write: bool, traj_header, roll_header, rows, an
                         _log(pargs, 3, "Info", progress)
                     _log(pargs, 3, "Info", f"step:    {step} / {nsteps}")
                     last_update[0] = time.time()
+            if error_bars:
+                eb = pool.error_bars(nsteps, error_bars)
+                if pool.info is not None:
+                    pool.info["error_bars"] = eb
+                continue
             for step, micro, ang, sums in pool.recorded(nsteps, stepout, angles=angles, tick=tick):
                 for k in range(len(files)):
                     files.rows(k, *rows(plist[k], step, micro[k], ang[k] if angles else None, sums[k]))
@@ -516,6 +574,27 @@ def recorded_stage(pool, nsteps, write: bool, traj_header, roll_header, rows, an
 
 
 # ---------------------------------------------------------------------------------------------- stdout
+def error_summary(eb, k: int):
+    """The blocked standard errors of case k laid out like the summary of its averages (a main's `averagers` and
+    `summary_lines` then print them under the names of the quantities they belong to)."""
+    s = _lib.Summary()
+    se = eb.stderr[k]
+    for q in range(_lib.NOBS):
+        s.avg[q] = se[q]
+    s.acceptance_ratio = se[16]
+    s.extra_avg[0], s.extra_avg[1] = se[17], se[18]
+    return s
+
+
+def error_lines(main, eb, k: int, pargs) -> list[str]:
+    """`<case>.err`: the left-hand names of the `.out` (the main's own summary_lines) with the blocked standard errors as
+    right-hand sides, then the batch count and, over the 19 quantities of _lib.EB_NAMES, inefficiency and converged."""
+    return [*main.summary_lines(*main.averagers(error_summary(eb, k)), pargs),
+            f"batches = {eb.nbatches}",
+            f"inefficiency = {jl_vector(eb.inefficiency[k])}",
+            f"converged = {jl_vector(eb.converged[k].astype(float))}"]
+
+
 def summary_lines(sas, vas, ar, pargs, extra=()) -> list[str]:
     """The println lines every main ends with (mcmc_eap_chain.jl:386-395); `extra`: a main's own lines in front of AR."""
     nb = pargs["mlen"] * pargs["num-monomers"]

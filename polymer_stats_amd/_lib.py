@@ -26,6 +26,12 @@ OBS_NAMES = ["r1", "r2", "r3", "r1sq", "r2sq", "r3sq", "rsq",
 # 16-vector: component 1 in the x slots, component 2 in the z slots, the y slots exactly 0
 PLANAR_OBS_NAMES = ["r1", "r3", "r1sq", "r3sq", "rsq", "p1", "p3", "p1sq", "p3sq", "psq", "U", "Usq"]
 PLANAR_OBS_INDEX = [OBS_NAMES.index(k) for k in PLANAR_OBS_NAMES]
+# blocked standard errors (pstat_series_error_bars, pstat_blocking_device): the columns of a series' error bars, the six
+# doubles per column in the order of the PSTAT_EB_* enum, and the kernel's bounds
+EB_NAMES = OBS_NAMES + ["AR", "cos2", "psi"]
+EB_FIELDS = ["mean", "stderr", "stderr_err", "inefficiency", "level", "converged"]
+BLOCK_LEVELS = 24
+BLOCK_MAX_BATCHES = 40960
 
 # every symbol include/pstat.h declares (tests check the built library exports all of them)
 SYMBOLS = [
@@ -35,7 +41,7 @@ SYMBOLS = [
     "pstat_summary_get", "pstat_summary_from_reduction", "pstat_chain_state", "pstat_chain_extras", "pstat_restart_from_x0",
     "pstat_checkpoint", "pstat_restore", "pstat_launch_info_get", "pstat_chain_means",
     "pstat_series_open", "pstat_advance_series", "pstat_series_read", "pstat_series_clear", "pstat_series_close",
-    "pstat_create_planar",
+    "pstat_create_planar", "pstat_series_error_bars", "pstat_blocking_device",
 ]
 ABI_VERSION = 6
 
@@ -124,6 +130,8 @@ def load():
     L.pstat_series_clear.argtypes = [vp, vp]
     L.pstat_series_close.argtypes = [vp, vp]
     L.pstat_series_close.restype = None
+    L.pstat_series_error_bars.argtypes = [vp, vp, i64, i64, i32, C.POINTER(C.c_int64), dp, dp]
+    L.pstat_blocking_device.argtypes = [vp, i64, i64, i64, i32, i32, vp, dp, dp]
     if L.pstat_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI version {L.pstat_abi_version()}, this binding needs {ABI_VERSION}: "
                           "rebuild it with `make -C polymer_stats_amd/csrc`")

@@ -564,6 +564,31 @@ void free_series(pstat_series *s) {
   delete s;
 }
 
+// device scratch of one call
+struct DeviceDoubles {
+  double *p = nullptr;
+  int alloc(size_t doubles) {
+    hipError_t e = hipMalloc((void **)&p, doubles * sizeof(double));
+    if (e != hipSuccess) return fail(PSTAT_ERR_NOMEM, "hipMalloc(%zu) failed: %s", doubles * sizeof(double), hipGetErrorString(e));
+    return PSTAT_OK;
+  }
+  ~DeviceDoubles() { (void)hipFree(p); }
+};
+
+// the blocking transform of x[nbatches][stride] (device) on `stream`, results to host memory; waits for the stream
+int blocking_to_host(const double *x, int64_t nbatches, int64_t ncols, int64_t stride, int min_blocks, hipStream_t stream,
+                     double *out, double *levels) {
+  DeviceDoubles d_out, d_levels;
+  PSTAT_TRY(d_out.alloc((size_t)ncols * PSTAT_EB_FIELDS));
+  if (levels) PSTAT_TRY(d_levels.alloc((size_t)ncols * PSTAT_BLOCK_LEVELS));
+  HIP_TRY(launch_blocking(x, nbatches, ncols, stride, min_blocks, d_out.p, d_levels.p, stream));
+  HIP_TRY(hipMemcpyAsync(out, d_out.p, (size_t)ncols * PSTAT_EB_FIELDS * sizeof(double), hipMemcpyDeviceToHost, stream));
+  if (levels)
+    HIP_TRY(hipMemcpyAsync(levels, d_levels.p, (size_t)ncols * PSTAT_BLOCK_LEVELS * sizeof(double), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  return PSTAT_OK;
+}
+
 int reduce_to_host(pstat_handle *h, int icase, double red[PSTAT_NRED]) {
   int rc = pstat_reduce_device(h, icase, h->d_red);
   if (rc) return rc;
@@ -888,6 +913,65 @@ void pstat_series_close(pstat_handle *h, pstat_series *s) {
   for (size_t i = 0; i < h->series.size(); ++i)
     if (h->series[i] == s) { h->series.erase(h->series.begin() + (long)i); break; }
   free_series(s);
+}
+
+int pstat_series_error_bars(pstat_handle *h, pstat_series *s, int64_t first_row, int64_t nrows, int32_t min_blocks,
+                            int64_t *nbatches, double *out, double *levels) {
+  if (!h || !s || !out) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
+  if (!own_series(h, s)) return fail(PSTAT_ERR_INVALID_ARG, "the series is not an open series of this handle");
+  if (h->cfg.umbrella)
+    return fail(PSTAT_ERR_UNSUPPORTED, "error bars under --umbrella-sampling: the recorded means are ratios with per-chain "
+                "normalizers that the rows do not hold");
+  if (min_blocks == 0) min_blocks = 32;
+  if (min_blocks < 2) return fail(PSTAT_ERR_INVALID_ARG, "min_blocks must be >= 2 (or 0 for the default 32), not %d", min_blocks);
+  if (nrows < 0) nrows = s->rows - first_row;
+  if (first_row < 0 || nrows < 0 || first_row > s->rows || nrows > s->rows - first_row)
+    return fail(PSTAT_ERR_INVALID_ARG, "rows [%lld, %lld) asked for, %lld recorded", (long long)first_row,
+                (long long)(first_row + nrows), (long long)s->rows);
+  // the rows' common spacing; a row that breaks it was recorded with another stepout or after a pstat_reset_averages
+  const int64_t *steps = s->steps.data() + first_row;
+  const int64_t d = nrows >= 2 ? steps[1] - steps[0] : (nrows == 1 ? steps[0] : 1);
+  for (int64_t r = 1; r < nrows; ++r)
+    if (d < 1 || steps[r] - steps[r - 1] != d)
+      return fail(PSTAT_ERR_INVALID_ARG, "row %lld was recorded at step %lld, row %lld at step %lld: the rows are not "
+                  "equally spaced%s", (long long)(first_row + r), (long long)steps[r], (long long)(first_row + r - 1),
+                  (long long)steps[r - 1], d < 1 ? " and increasing" : "");
+  const bool zero_base = nrows >= 1 && steps[0] == d;   // the series began at empty averages
+  const int64_t nb = zero_base ? nrows : (nrows > 0 ? nrows - 1 : 0);
+  if (nbatches) *nbatches = nb;
+  if (nb < min_blocks)
+    return fail(PSTAT_ERR_TOO_SMALL, "%lld batches, min_blocks = %d", (long long)nb, min_blocks);
+  if (nb > blocking_max_batches())
+    return fail(PSTAT_ERR_UNSUPPORTED, "%lld batches: the blocking kernel takes at most %lld (level 1 of a column must fit "
+                "the LDS of a CU)", (long long)nb, (long long)blocking_max_batches());
+  PSTAT_TRY(set_device(h));
+  PSTAT_TRY(sync_checked(h));
+  const int64_t ncols = (int64_t)h->ncases * PSTAT_NQ;
+  DeviceDoubles x;
+  PSTAT_TRY(x.alloc((size_t)nb * (size_t)ncols));
+  const int64_t row0 = first_row + (zero_base ? 0 : 1);
+  HIP_TRY(launch_series_batches(s->d_red, row0, nb, h->ncases, s->steps[(size_t)row0], d, zero_base ? 1 : 0, x.p, h->stream));
+  return blocking_to_host(x.p, nb, ncols, ncols, min_blocks, h->stream, out, levels);
+}
+
+int pstat_blocking_device(const double *x, int64_t nbatches, int64_t ncols, int64_t stride, int32_t min_blocks, int32_t device,
+                          void *stream, double *out, double *levels) {
+  if (!x || !out) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
+  if (min_blocks == 0) min_blocks = 32;
+  if (min_blocks < 2) return fail(PSTAT_ERR_INVALID_ARG, "min_blocks must be >= 2 (or 0 for the default 32), not %d", min_blocks);
+  if (ncols < 1 || ncols > 0x7fffffff) return fail(PSTAT_ERR_INVALID_ARG, "ncols must be in 1 .. 2^31 - 1");
+  if (stride < ncols) return fail(PSTAT_ERR_INVALID_ARG, "stride %lld < ncols %lld", (long long)stride, (long long)ncols);
+  if (nbatches < min_blocks)
+    return fail(PSTAT_ERR_TOO_SMALL, "%lld batches, min_blocks = %d", (long long)nbatches, min_blocks);
+  if (nbatches > blocking_max_batches())
+    return fail(PSTAT_ERR_UNSUPPORTED, "%lld batches: the blocking kernel takes at most %lld (level 1 of a column must fit "
+                "the LDS of a CU)", (long long)nbatches, (long long)blocking_max_batches());
+  int before = -1;      // the caller's current device is put back: the callers are programs with a device of their own (torch)
+  if (hipGetDevice(&before) != hipSuccess) before = -1;
+  if (hipSetDevice(device) != hipSuccess) return fail(PSTAT_ERR_NO_DEVICE, "device %d is not available", device);
+  const int rc = blocking_to_host(x, nbatches, ncols, stride, min_blocks, (hipStream_t)stream, out, levels);
+  if (before >= 0 && before != device) (void)hipSetDevice(before);
+  return rc;
 }
 
 int pstat_sync(pstat_handle *h) {

@@ -329,6 +329,13 @@ hipError_t launch_reinit(const LaunchCfg &cfg, const SweepArgs &a, const DevStat
                          const CaseConst *cases, int force_init, hipStream_t stream);
 // true iff x is NaN or +-Inf (one v_cmp_class)
 template <typename R> __host__ __device__ inline bool not_finite(R x) { return !__builtin_isfinite(x); }
+// sum over the 64 lanes of a wavefront, valid in lane 0: the shfl_down tree whose order is part of every reduced result
+// (pstat_reduce.hip, pstat_blocking.hip)
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;
+}
 // The ensemble reduction (pstat_reduce.hip), kernels and host statements of the same arithmetic.
 // reduction of chains [c0, c1) into out[PSTAT_NRED]; partial = scratch of reduce_scratch_doubles()
 hipError_t launch_reduce(const DevState &s, int64_t c0, int64_t c1, int64_t steps_recorded,
@@ -345,5 +352,16 @@ void sums_in_abi_order(const double *sums, int64_t stride, double *out);
 // host: out[PSTAT_NQ][m] = the mean vectors the reduction folds, of m chains gathered as sums[NSUMS][m], nacc[m] and, under
 // umbrella sampling, wnorm[m] (null otherwise: the normaliser is `steps`)
 void chain_means_host(const double *sums, const double *wnorm, const int64_t *nacc, int64_t steps, int64_t m, double *out);
+
+// Blocked standard errors (pstat_blocking.hip; the estimator: DESIGN.md 3.12).
+// x[nbatches][ncases * PSTAT_NQ] = the batch means between consecutive rows of a series' red[row][ncases][PSTAT_NRED], batch b
+// ending at row row0 + b, where every chain had recorded steps0 + b d steps; zero_base: batch 0 starts from empty averages
+hipError_t launch_series_batches(const double *red, int64_t row0, int64_t nbatches, int64_t ncases, int64_t steps0, int64_t d,
+                                 int zero_base, double *x, hipStream_t stream);
+// the blocking transform of every column of x[nbatches][stride]: out[ncols][PSTAT_EB_FIELDS] and, unless null,
+// levels[ncols][PSTAT_BLOCK_LEVELS]; 2 <= nbatches <= blocking_max_batches(), stride >= ncols
+hipError_t launch_blocking(const double *x, int64_t nbatches, int64_t ncols, int64_t stride, int min_blocks, double *out,
+                           double *levels, hipStream_t stream);
+int64_t blocking_max_batches();
 
 }  // namespace pstat

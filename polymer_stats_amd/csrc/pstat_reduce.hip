@@ -63,12 +63,6 @@ __host__ __device__ __forceinline__ void chain_mean(const double *sums, const in
   v[18] = sums[S_PSI * stride] * inv;   // mean bond angle
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
 // chain c of case `cc`, folded into a thread's partial
 __device__ __forceinline__ void fold_chain(const DevState &S, const ReduceArgs &a, const CaseConst &cc, const int64_t c,
                                            double (&p)[NP]) {

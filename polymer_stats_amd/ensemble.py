@@ -184,6 +184,19 @@ class Series:
                                      micro.ctypes.data_as(dp), ang.ctypes.data_as(dp) if self.angles else None))
         return steps, red, micro, ang
 
+    def error_bars(self, first_row: int = 0, nrows: int | None = None, min_blocks: int = 32, levels: bool = False) -> "ErrorBars":
+        """Blocked standard errors of the batch means between the rows [first_row, first_row + nrows) (default: to the
+        last row), computed on the device (pstat_series_error_bars): arrays of shape [ncases, NQ], columns EB_NAMES.
+        Synchronises."""
+        e = self._e
+        out = np.zeros((e.ncases, _lib.NQ, len(_lib.EB_FIELDS)))
+        lev = np.zeros((e.ncases, _lib.NQ, _lib.BLOCK_LEVELS)) if levels else None
+        nb = C.c_int64(0)
+        dp = C.POINTER(C.c_double)
+        check(e._L.pstat_series_error_bars(e._h, self._s, int(first_row), -1 if nrows is None else int(nrows), int(min_blocks),
+                                           C.byref(nb), out.ctypes.data_as(dp), lev.ctypes.data_as(dp) if levels else None))
+        return ErrorBars(out, int(nb.value), lev)
+
     def clear(self):
         check(self._e._L.pstat_series_clear(self._e._h, self._s))
         self.rows = 0
@@ -192,6 +205,34 @@ class Series:
         if self._s and self._e._h:      # (closing the ensemble closes its series)
             self._e._L.pstat_series_close(self._e._h, self._s)
         self._s = None
+
+
+class ErrorBars:
+    """What the blocking transform gives per column (include/pstat.h, PSTAT_EB_*): `mean`, `stderr` (the blocked standard
+    error), `stderr_err` (its own uncertainty), `inefficiency` ((stderr / naive stderr)^2), `level` (blocking level picked),
+    `converged` (False: the curve was still rising at the last level, the run is too short for this column); `nbatches`;
+    `levels`: se_l of every level, 0 beyond the last, or None."""
+
+    def __init__(self, out: np.ndarray, nbatches: int, levels: np.ndarray | None):
+        self.mean, self.stderr, self.stderr_err, self.inefficiency = (out[..., i] for i in range(4))
+        self.level = out[..., 4].astype(np.int64)
+        self.converged = out[..., 5] != 0
+        self.nbatches, self.levels = nbatches, levels
+
+
+def blocking_device(ptr: int, nbatches: int, ncols: int, stride: int | None = None, min_blocks: int = 32, levels: bool = False,
+                    device: int = 0, stream: int | None = None) -> ErrorBars:
+    """The blocking transform of a float64 matrix x[nbatches][stride] in DEVICE memory at `ptr` (e.g. tensor.data_ptr() of a
+    contiguous torch tensor, or a series merged over ranks), first `ncols` columns: arrays of shape [ncols]
+    (pstat_blocking_device).  `stream`: raw hipStream_t the matrix was produced on.  Synchronises that stream."""
+    stride = int(ncols) if stride is None else int(stride)
+    out = np.zeros((max(int(ncols), 0), len(_lib.EB_FIELDS)))
+    lev = np.zeros((max(int(ncols), 0), _lib.BLOCK_LEVELS)) if levels else None
+    dp = C.POINTER(C.c_double)
+    check(_lib.load().pstat_blocking_device(C.c_void_p(ptr), int(nbatches), int(ncols), stride, int(min_blocks), int(device),
+                                            C.c_void_p(stream) if stream else None, out.ctypes.data_as(dp),
+                                            lev.ctypes.data_as(dp) if levels else None))
+    return ErrorBars(out, int(nbatches), lev)
 
 
 def summary_from_reduction(red: Iterable[float], steps_per_chain: int) -> Summary:

@@ -87,11 +87,21 @@ def run(pargs: dict):
     return run_cases([pargs])[0]
 
 
-def run_cases(plist: list, write_csv: bool = True, info: dict | None = None) -> list:
+def averagers(s):
+    """A summary -> (scalar_averagers with the two extras, vector_averagers, ar)."""
+    sas, vas, ar = _host._averagers(s)
+    ex, exse = np.array(s.extra_avg), np.array(s.extra_stderr)
+    return sas + [Averager(ex[0], exse[0]), Averager(ex[1], exse[1])], vas, ar
+
+
+def run_cases(plist: list, write_csv: bool = True, info: dict | None = None, error_bars: int = 0) -> list:
     """The top level of the clustering main for every case of `plist` at once -- parsed options that differ only in their
     physics scalars, prefix and seed (one case: the command line; many: a sweep, polymer_stats_amd/sweep.py) -- as ONE
-    ensemble: every rung of the ladder and the recorded run are one launch (per segment) for all of them."""
+    ensemble: every rung of the ladder and the recorded run are one launch (per segment) for all of them.  `error_bars` = N:
+    the production run is recorded as N batches and info["error_bars"] holds the blocked standard errors of every case."""
     pargs = plist[0]
+    if error_bars:
+        _host.check_error_bars(pargs, error_bars, write_csv)
     _host.check_numeric_type(pargs)                                     # :191
     ladder = _host.burn_ladder(pargs)
     with _host._Pool(plist, params_from_pargs, info=info) as pool:
@@ -103,18 +113,13 @@ def run_cases(plist: list, write_csv: bool = True, info: dict | None = None) -> 
                     e.restart_from_x0(x0, dx0[0], dx0[1])
         # every stage is one call of the reference's mcmc(nsteps, pargs, chain) (:172-352) at kT x mult: the rungs (:366-383), then
         # the production run (:385-386).  Every call rewrites the two CSV files, so only the last one's survive: the rungs skip them
-        for mult, nsteps, write in [(m, pargs["burn-in"], False) for m in ladder] + [(1.0, pargs["num-steps"], write_csv)]:
+        for mult, nsteps, write, eb in [(m, pargs["burn-in"], False, 0) for m in ladder] + [(1.0, pargs["num-steps"], write_csv, error_bars)]:
             pool.stage(mult)
             out = _host.recorded_stage(pool, int(nsteps), write, lambda p: traj_header(p["num-monomers"]), ROLL_HEADER, _rows,
-                                       angles=True)
+                                       angles=True, error_bars=eb)
         for k, s in enumerate(out):
             pool.report_failures(k, s)
-    res = []
-    for s in out:
-        sas, vas, ar = _host._averagers(s)
-        ex, exse = np.array(s.extra_avg), np.array(s.extra_stderr)
-        res.append((sas + [Averager(ex[0], exse[0]), Averager(ex[1], exse[1])], vas, ar))
-    return res
+    return [averagers(s) for s in out]
 
 
 def summary_lines(sas, vas, ar, pargs) -> list[str]:

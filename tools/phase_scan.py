@@ -8,6 +8,9 @@ and the only exchange is one all-reduce(SUM) of the [points x 41] reduction tens
     python tools/phase_scan.py --chains 128 --steps 50000 --burn-in 20000 --energy Ising --out scan.csv
     python tools/phase_scan.py --main clustering --burn-schedule "1000,100,10,2,1" ...   # what the reference's
         # run/K1_E0-kT-phase.jl:45 launches per grid point: mcmc_clustering_eap_chain.jl with its annealed ladder
+    python tools/phase_scan.py --chains 1 --steps 2500000 --error-bars 1000 ...   # error bars from ONE chain per point: the
+        # production run is recorded on the device as 1000 batches; their blocked standard errors (Flyvbjerg-Petersen,
+        # Series.error_bars) are the columns r3_blocked ... converged (0: the run is too short for r3, p3 or U at that point)
     python tools/phase_scan.py --gpus 8 ...                      # starts its own 8 ranks, one per GPU (RCCL)
     python tools/phase_scan.py --gpus 2 --backend gloo ...       # rehearsal: ranks may share a GPU, all-reduce via host
     python -m torch.distributed.run --nproc-per-node 8 tools/phase_scan.py --gpus 8 ...   (also fine)
@@ -49,8 +52,17 @@ def main():
     ap.add_argument("--gpus", type=int, default=1, help="ranks; > 1 from a bare shell starts them (one per GPU)")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="collective backend; gloo (through host memory, ranks may share a GPU) to rehearse N > 1 on a box with fewer GPUs")
+    ap.add_argument("--error-bars", type=int, default=0, metavar="N",
+                    help="record the production run as N batches of steps / N steps and add their blocked standard errors as the columns "
+                         "r3_blocked, p3_blocked, U_blocked, r3_ineff, U_ineff, converged (one rank only; a remainder steps %% N is run and belongs to no batch)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
+
+    if args.error_bars:
+        if args.gpus > 1:       # the ranks hold different chains of the same point; their series are not merged
+            raise SystemExit(f"--error-bars needs one rank, not --gpus {args.gpus}")
+        if args.error_bars < 32 or args.steps < args.error_bars:
+            raise SystemExit(f"--error-bars {args.error_bars}: at least 32 batches of at least one step each (--steps {args.steps})")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # start the ranks BEFORE anything touches the GPU; this process never imports torch
@@ -110,7 +122,18 @@ def main():
             if args.main == "clustering":
                 e.reset_sampler()
             e.reset_averages()
-        e.advance(args.steps)
+        eb = None
+        if args.error_bars:
+            series = e.open_series(args.error_bars)
+            try:        # exactly N rows of steps // N steps; the remainder is advanced and belongs to no batch
+                q = args.steps // args.error_bars
+                e.advance_series(series, args.error_bars * q, q)
+                e.advance(args.steps - args.error_bars * q)
+                eb = series.error_bars()
+            finally:
+                series.close()
+        else:
+            e.advance(args.steps)
         for k in range(len(grid)):
             e.reduce_into(red[k].data_ptr(), icase=k)
         if world > 1:
@@ -126,11 +149,15 @@ def main():
         info = e.launch_info()
     if rank == 0:
         host = red.cpu().numpy()
-        rows = ["E0,kT,chains,r3,r3_stderr,rsq,p3,p3_stderr,psq,U,U_stderr,AR"]
-        for (E0, kT), v in zip(grid, host):
+        rows = ["E0,kT,chains,r3,r3_stderr,rsq,p3,p3_stderr,psq,U,U_stderr,AR" +
+                (",r3_blocked,p3_blocked,U_blocked,r3_ineff,U_ineff,converged" if eb else "")]
+        R3, P3, U = (ps.EB_NAMES.index(q) for q in ("r3", "p3", "U"))
+        for k, ((E0, kT), v) in enumerate(zip(grid, host)):
             s = ps.summary_from_reduction(v, args.steps)
+            blocked = (eb.stderr[k, R3], eb.stderr[k, P3], eb.stderr[k, U], eb.inefficiency[k, R3], eb.inefficiency[k, U],
+                       int(eb.converged[k, [R3, P3, U]].min())) if eb else ()
             rows.append(",".join(f"{x:.12g}" for x in (E0, kT, s.num_chains, s.avg[2], s.stderr[2], s.avg[6], s.avg[9],
-                                                        s.stderr[9], s.avg[13], s.avg[14], s.stderr[14], s.acceptance_ratio)))
+                                                        s.stderr[9], s.avg[13], s.avg[14], s.stderr[14], s.acceptance_ratio, *blocked)))
         text = "\n".join(rows) + "\n"
         if args.out:
             open(args.out, "w").write(text)

@@ -56,6 +56,13 @@ def main():
     ap.add_argument("--overwrite", action="store_true")
     ap.add_argument("--csv", action="store_true", help="also write every case's _trajectory.csv and _rolling.csv, one row per --stepout steps: the rows of all cases are "
                          "recorded on the device by one launch each and read back in chunks (formatting their text is then the larger part of a big run)")
+    ap.add_argument("--error-bars", type=int, default=0, metavar="N",
+                    help="record the production run as N batches (of num-steps / N steps) on the device and write, next to every <case>.out, "
+                         "a <case>.err: the same names with the blocked standard errors (Flyvbjerg-Petersen) as values, then batches, "
+                         "inefficiency and converged over the 19 quantities.  One device, --num-inits 1, float64, no --csv, no umbrella sampling.  "
+                         "ROUGHLY DOUBLES the production time: the stage is run recorded for the .err and then again, from a checkpoint, as "
+                         "the one launch of a plain run, so that the .out is byte for byte the plain run's (the two runs' means agree to "
+                         "~1e-15; a remainder num-steps %% N belongs to no batch).  A case whose .out is there but whose .err is not is run again")
     ap.add_argument("--max-chains", type=int, default=262144, help="chains per launch (cases per ensemble = this / num-chains)")
     ap.add_argument("--dry-run", action="store_true", help="print the plan (cases, file names, ensembles) and stop: no GPU needed")
     ap.add_argument("--aggregate", default="", help="afterwards write scripts/aggregate_mcmc.jl's CSV of the whole directory here")
@@ -75,6 +82,11 @@ def main():
     if not cases:
         raise SystemExit("no cases: give --axis and/or --cases")
 
+    if args.error_bars:
+        try:
+            sw.check_error_bars(args.main, fixed, args.error_bars, write_csv=args.csv, world=args.gpus)
+        except sw.ReferenceError_ as e:
+            raise SystemExit(str(e))
     if args.dry_run:
         pl = sw.plan(args.main, fixed, cases, args.workdir, name=args.name or None, num_chains=args.num_chains,
                      seed=0 if args.seed is None else args.seed, precision=args.precision, rng=args.rng)
@@ -132,7 +144,7 @@ def main():
     t0 = time.time()
     res = sw.run_sweep(args.main, fixed, cases, args.workdir, name=args.name or None, num_chains=args.num_chains, seed=args.seed,
                        precision=args.precision, rng=args.rng, rank=rank, world=world, device=local % ndev,
-                       overwrite=args.overwrite, write_csv=args.csv, max_chains=args.max_chains,
+                       overwrite=args.overwrite, write_csv=args.csv, max_chains=args.max_chains, error_bars=args.error_bars,
                        log=lambda m: print("# " + m, file=sys.stderr, flush=True))
     print(f"# rank {rank} of {world}: {len(res['ran'])} cases run in {res['launches']} ensembles, {len(res['skipped'])} already "
           f"there; {time.time() - t0:.2f} s", file=sys.stderr, flush=True)
