@@ -377,6 +377,44 @@ int pstat_blocking_device(const double *x /* DEVICE memory, [nbatches][stride] *
                           int32_t min_blocks, int32_t device, void *stream, double *out /* host [ncols][PSTAT_EB_FIELDS] */,
                           double *levels /* host [ncols][PSTAT_BLOCK_LEVELS] or NULL */);
 
+/* Replica exchange (parallel tempering) between the cases of one handle, on the device.  The reference has no equivalent:
+ * it gets cold chains out of metastable states with an annealed burn-in ladder and by repeating runs (run=1:25).  A handle
+ * already holds every rung of a temperature ladder side by side; one exchange round is two small launches on its stream.
+ * The contract (DESIGN.md 3.13 states it in full; polymer_stats_amd/csrc/pstat_exchange.hip is the device's statement):
+ *   ladder     cases that differ in nothing but kT, seed and chain_id0; rungs = its cases by kT ascending at open time, ties by
+ *              case index.  ladder[i] >= 0 names case i's ladder, -1 keeps it out of every exchange.
+ *   pairing    round t pairs rungs (2j + (t & 1), 2j + 1 + (t & 1)); a rung without a partner sits the round out; chain k of
+ *              one case pairs with chain k of the other.  t starts at 0, advances by one per call and is 32-bit: the call
+ *              that would overflow it fails with PSTAT_ERR_INVALID_ARG.
+ *   criterion  f64, every operation rounded: d = (1 / kT_a - 1 / kT_b) (U_a - U_b); accept iff U_a, U_b are finite and
+ *              (d >= 0 or u < exp(d)), with the cases' CURRENT kT (a burn-in rung set by pstat_scale_kT exchanges at its
+ *              scaled temperatures).
+ *   stream     o = Philox4x32-10(key = (seed_lo, seed_hi), ctr = (k, lower rung's case index, 0x7e3a9e0d, t)), `seed` the
+ *              tempering object's own; u = ((o[0] << 21) | (o[1] >> 11)) 2^-53.  The chains' generators are not touched.
+ *   an accepted exchange swaps the two chains' configurations (angles, r, p, U and the other cached observables) and resets
+ *   the acceptor's cache offset of both; running sums, normalizers, generators, step sizes, adaptation windows and acceptance
+ *   counts stay with the case (the temperature), so every case's averages remain averages at its own kT.
+ *
+ *   pstat_tempering_open      checks the ladders and uploads both parities' partner tables.  Before the device is touched,
+ *                             PSTAT_ERR_INVALID_ARG: null arguments; a ladder id below -1; a ladder whose cases differ in a
+ *                             physics field other than kT (the message names the field and the case).
+ *                             PSTAT_ERR_UNSUPPORTED: umbrella-sampling handles (their weights and reference energy are per
+ *                             chain, relative to the chain's first configuration).  A ladder of one case is allowed and
+ *                             never exchanges.
+ *   pstat_tempering_exchange  one round; asynchronous on the handle's stream, no host synchronisation.
+ *   pstat_tempering_stats     per case, counted on the LOWER rung of a pair: exchanges attempted and accepted (one per pair
+ *                             of chains and round); *rounds = exchange calls so far.  Any output may be NULL.  Synchronises.
+ *   pstat_tempering_close     pstat_destroy closes the ones still open.
+ * The round counter and the counts are not part of a checkpoint.  Results are Boltzmann-exact only where the step itself is:
+ * the fixed-force main without re-initialisation, or the clustering mains with single moves only. */
+typedef struct pstat_tempering pstat_tempering;
+int pstat_tempering_open(pstat_handle *h, const int32_t *ladder /* [ncases]: ladder id >= 0, or -1: takes no part */,
+                         uint64_t seed, pstat_tempering **out);
+int pstat_tempering_exchange(pstat_handle *h, pstat_tempering *t);
+int pstat_tempering_stats(pstat_handle *h, pstat_tempering *t, int64_t *attempted /* [ncases] */, int64_t *accepted /* [ncases] */,
+                          int64_t *rounds);
+void pstat_tempering_close(pstat_handle *h, pstat_tempering *t);
+
 /* Per-chain accessors for tests and tooling (host buffers).  angles: theta[n] then phi[n] as
  * doubles, radians; sums: the 16 per-chain running sums in rolling.csv order;
  * counters: {accepted_total, steps_recorded, nacc_window, natt_window};

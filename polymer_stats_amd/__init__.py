@@ -6,9 +6,9 @@ reference's three mains (python -m polymer_stats_amd.<name>), short modules over
 aggregate_mcmc: the reference's run/*.jl sweeps and scripts/aggregate_mcmc.jl.  julia_fmt: Julia's number formatting."""
 from ._lib import (DIELECTRIC, POLAR, NONINTERACTING, INTERACTING, ISING, CUTOFF, F32, F64, Q16, RNG_MWC64X, RNG_XOSHIRO128PP, NOBS, NRED, NQ, MOVES_SINGLE, MOVES_CLUSTER,
                    OBS_NAMES, PLANAR_OBS_NAMES, PLANAR_OBS_INDEX, EB_NAMES, Params, PstatError, default_params, default_planar_params)
-from .ensemble import Ensemble, ErrorBars, blocking_device, summary_from_reduction
+from .ensemble import Ensemble, ErrorBars, Tempering, blocking_device, ladders_by, summary_from_reduction
 
 __all__ = ["DIELECTRIC", "POLAR", "NONINTERACTING", "INTERACTING", "ISING", "CUTOFF", "F32", "F64", "Q16", "RNG_MWC64X", "RNG_XOSHIRO128PP", "NOBS",
            "NRED", "NQ", "MOVES_SINGLE", "MOVES_CLUSTER", "OBS_NAMES", "PLANAR_OBS_NAMES", "PLANAR_OBS_INDEX", "EB_NAMES", "Params", "PstatError",
-           "default_params", "default_planar_params", "Ensemble", "ErrorBars", "blocking_device",
+           "default_params", "default_planar_params", "Ensemble", "ErrorBars", "Tempering", "blocking_device", "ladders_by",
            "summary_from_reduction"]

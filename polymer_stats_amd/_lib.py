@@ -42,6 +42,7 @@ SYMBOLS = [
     "pstat_checkpoint", "pstat_restore", "pstat_launch_info_get", "pstat_chain_means",
     "pstat_series_open", "pstat_advance_series", "pstat_series_read", "pstat_series_clear", "pstat_series_close",
     "pstat_create_planar", "pstat_series_error_bars", "pstat_blocking_device",
+    "pstat_tempering_open", "pstat_tempering_exchange", "pstat_tempering_stats", "pstat_tempering_close",
 ]
 ABI_VERSION = 6
 
@@ -132,6 +133,11 @@ def load():
     L.pstat_series_close.restype = None
     L.pstat_series_error_bars.argtypes = [vp, vp, i64, i64, i32, C.POINTER(C.c_int64), dp, dp]
     L.pstat_blocking_device.argtypes = [vp, i64, i64, i64, i32, i32, vp, dp, dp]
+    L.pstat_tempering_open.argtypes = [vp, C.POINTER(C.c_int32), C.c_uint64, C.POINTER(vp)]
+    L.pstat_tempering_exchange.argtypes = [vp, vp]
+    L.pstat_tempering_stats.argtypes = [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.pstat_tempering_close.argtypes = [vp, vp]
+    L.pstat_tempering_close.restype = None
     if L.pstat_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI version {L.pstat_abi_version()}, this binding needs {ABI_VERSION}: "
                           "rebuild it with `make -C polymer_stats_amd/csrc`")

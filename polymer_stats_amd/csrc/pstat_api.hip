@@ -10,6 +10,7 @@
 #include <cstring>
 #include <memory>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "../../include/pstat.h"
@@ -110,6 +111,7 @@ struct pstat_handle {
   size_t elem = 4;                  // sizeof(R)
   int failed_job = 0;               // sticky: 1 + the job of a persistent launch that timed out (0 = none)
   std::vector<pstat_series *> series;   // series still open (pstat_destroy closes them)
+  std::vector<pstat_tempering *> tempering;   // tempering objects still open (likewise)
 };
 
 // The stepout time series of one handle: rows recorded on the device by launch_record, read back in bulk.
@@ -119,6 +121,16 @@ struct pstat_series {
   double *d_micro = nullptr;        // [capacity][ncases][7]
   double *d_angles = nullptr;       // [capacity][ncases][2n], PSTAT_SERIES_ANGLES only
   std::vector<int64_t> steps;       // [capacity]: the handle's steps_recorded at each row (known when the row is enqueued)
+};
+
+// Replica exchange between the cases of one handle (pstat_exchange.hip).
+struct pstat_tempering {
+  uint64_t seed = 0;
+  uint64_t round = 0;               // the next round's t; 32 bits on the device
+  int64_t npairs[2] = {0, 0};       // pairs of the even and of the odd rounds
+  int32_t *d_pairs[2] = {nullptr, nullptr};   // [npairs][2] = (lower, upper rung's case)
+  unsigned char *d_flags = nullptr; // [max npairs * chains per case]
+  int64_t *d_counts = nullptr;      // [2][ncases]: attempted, accepted, on the lower rung's case
 };
 
 namespace {
@@ -564,6 +576,20 @@ void free_series(pstat_series *s) {
   delete s;
 }
 
+pstat_tempering *own_tempering(pstat_handle *h, pstat_tempering *t) {
+  for (pstat_tempering *mine : h->tempering)
+    if (mine == t) return t;
+  return nullptr;
+}
+
+void free_tempering(pstat_tempering *t) {
+  (void)hipFree(t->d_pairs[0]);
+  (void)hipFree(t->d_pairs[1]);
+  (void)hipFree(t->d_flags);
+  (void)hipFree(t->d_counts);
+  delete t;
+}
+
 // device scratch of one call
 struct DeviceDoubles {
   double *p = nullptr;
@@ -806,6 +832,7 @@ void pstat_destroy(pstat_handle *h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   for (auto &b : h->bufs) (void)hipFree(b.ptr);
   for (pstat_series *s : h->series) free_series(s);
+  for (pstat_tempering *t : h->tempering) free_tempering(t);
   if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }
@@ -972,6 +999,120 @@ int pstat_blocking_device(const double *x, int64_t nbatches, int64_t ncols, int6
   const int rc = blocking_to_host(x, nbatches, ncols, stride, min_blocks, (hipStream_t)stream, out, levels);
   if (before >= 0 && before != device) (void)hipSetDevice(before);
   return rc;
+}
+
+int pstat_tempering_open(pstat_handle *h, const int32_t *ladder, uint64_t seed, pstat_tempering **out) {
+  if (!h || !ladder || !out) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
+  *out = nullptr;
+  const int nc = h->ncases;
+  for (int i = 0; i < nc; ++i)
+    if (ladder[i] < -1) return fail(PSTAT_ERR_INVALID_ARG, "ladder[%d] = %d: a ladder id is >= 0, or -1 for a case that takes no part", i, ladder[i]);
+  if (h->cfg.umbrella)
+    return fail(PSTAT_ERR_UNSUPPORTED, "replica exchange under --umbrella-sampling: the weights and their reference energy are "
+                "per chain, relative to the chain's first configuration");
+  pstat_tempering *t = nullptr;
+  try {
+    // a ladder's cases agree with its first one in every physics scalar but kT
+    std::vector<int> first((size_t)nc, -1), order;
+    for (int i = 0; i < nc; ++i) {
+      if (ladder[i] < 0) continue;
+      int f = -1;
+      for (int j = 0; j < i && f < 0; ++j)
+        if (ladder[j] == ladder[i]) f = j;
+      first[(size_t)i] = f < 0 ? i : first[(size_t)f];
+      if (f < 0) continue;
+      const CaseConst &a = h->cases[(size_t)first[(size_t)i]], &b = h->cases[(size_t)i];
+      const struct { const char *name; double x, y; } fields[] = {
+          {"E0", a.E0, b.E0}, {"K1", a.K1, b.K1}, {"K2", a.K2, b.K2}, {"mu", a.mu, b.mu}, {"Fz", a.Fz, b.Fz}, {"Fx", a.Fx, b.Fx},
+          {"b", a.b, b.b}, {"bend_mod", a.kappa, b.kappa}, {"bend_angle", a.psi0, b.psi0},
+          {"cluster_prob", a.cluster_prob, b.cluster_prob}, {"cutoff_radius", a.cutoff_radius, b.cutoff_radius}};
+      for (const auto &fd : fields)
+        if (fd.x != fd.y)
+          return fail(PSTAT_ERR_INVALID_ARG, "ladder %d: case %d differs from case %d in %s (%.17g against %.17g); the cases of "
+                      "a ladder differ in kT, seed and chain_id0 only", ladder[i], i, first[(size_t)i], fd.name, fd.y, fd.x);
+    }
+    // rungs: each ladder's cases by (kT, case index) ascending; pairs of both parities
+    std::vector<int32_t> pairs[2];
+    for (int i = 0; i < nc; ++i) {
+      if (first[(size_t)i] != i) continue;
+      order.clear();
+      for (int j = i; j < nc; ++j)
+        if (ladder[j] == ladder[i]) order.push_back(j);
+      for (size_t x = 1; x < order.size(); ++x)   // insertion sort: stable, so ties keep the case order
+        for (size_t y = x; y > 0 && h->cases[(size_t)order[y]].kT < h->cases[(size_t)order[y - 1]].kT; --y)
+          std::swap(order[y], order[y - 1]);
+      for (int parity = 0; parity < 2; ++parity)
+        for (size_t r = (size_t)parity; r + 1 < order.size(); r += 2) {
+          pairs[parity].push_back(order[r]);
+          pairs[parity].push_back(order[r + 1]);
+        }
+    }
+    PSTAT_TRY(set_device(h));
+    t = new (std::nothrow) pstat_tempering;
+    if (!t) return fail(PSTAT_ERR_NOMEM, "host allocation failed");
+    t->seed = seed;
+    const size_t per = (size_t)h->base.num_chains;
+    size_t most = 0;
+    hipError_t e = hipSuccess;
+    for (int parity = 0; parity < 2 && e == hipSuccess; ++parity) {
+      t->npairs[parity] = (int64_t)(pairs[parity].size() / 2);
+      most = pairs[parity].size() / 2 > most ? pairs[parity].size() / 2 : most;
+      if (pairs[parity].empty()) continue;
+      e = hipMalloc((void **)&t->d_pairs[parity], pairs[parity].size() * sizeof(int32_t));
+      if (e == hipSuccess)
+        e = hipMemcpy(t->d_pairs[parity], pairs[parity].data(), pairs[parity].size() * sizeof(int32_t), hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess && most) e = hipMalloc((void **)&t->d_flags, most * per);
+    if (e == hipSuccess) e = hipMalloc((void **)&t->d_counts, 2 * (size_t)nc * sizeof(int64_t));
+    if (e == hipSuccess) e = hipMemsetAsync(t->d_counts, 0, 2 * (size_t)nc * sizeof(int64_t), h->stream);   // ahead of the first round
+    if (e != hipSuccess) {
+      free_tempering(t);
+      return fail(e == hipErrorOutOfMemory ? PSTAT_ERR_NOMEM : PSTAT_ERR_HIP, "tempering tables: %s", hipGetErrorString(e));
+    }
+    h->tempering.push_back(t);
+  } catch (const std::bad_alloc &) {
+    if (t) free_tempering(t);
+    return fail(PSTAT_ERR_NOMEM, "host allocation failed");
+  }
+  *out = t;
+  return PSTAT_OK;
+}
+
+int pstat_tempering_exchange(pstat_handle *h, pstat_tempering *t) {
+  if (!h || !t) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
+  if (!own_tempering(h, t)) return fail(PSTAT_ERR_INVALID_ARG, "the tempering object is not an open one of this handle");
+  if (t->round > 0xffffffffull)
+    return fail(PSTAT_ERR_INVALID_ARG, "the 32-bit round counter of this tempering object is used up (2^32 rounds)");
+  PSTAT_TRY(set_device(h));
+  if (h->failed_job) return report_failed_job(h);
+  const int parity = (int)(t->round & 1);
+  const ExchangeArgs a{h->base.num_chains, h->S.C, h->base.n, t->npairs[parity], (uint32_t)t->round,
+                       (uint32_t)t->seed, (uint32_t)(t->seed >> 32), 0u};
+  HIP_TRY(launch_exchange(a, h->S, h->d_cases, t->d_pairs[parity], t->d_flags, t->d_counts, t->d_counts + h->ncases, h->elem,
+                          h->stream));
+  t->round += 1;
+  return PSTAT_OK;
+}
+
+int pstat_tempering_stats(pstat_handle *h, pstat_tempering *t, int64_t *attempted, int64_t *accepted, int64_t *rounds) {
+  if (!h || !t) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
+  if (!own_tempering(h, t)) return fail(PSTAT_ERR_INVALID_ARG, "the tempering object is not an open one of this handle");
+  PSTAT_TRY(set_device(h));
+  PSTAT_TRY(sync_checked(h));
+  const size_t bytes = (size_t)h->ncases * sizeof(int64_t);
+  if (attempted) HIP_TRY(hipMemcpy(attempted, t->d_counts, bytes, hipMemcpyDeviceToHost));
+  if (accepted) HIP_TRY(hipMemcpy(accepted, t->d_counts + h->ncases, bytes, hipMemcpyDeviceToHost));
+  if (rounds) *rounds = (int64_t)t->round;
+  return PSTAT_OK;
+}
+
+void pstat_tempering_close(pstat_handle *h, pstat_tempering *t) {
+  if (!h || !t || !own_tempering(h, t)) return;
+  (void)hipSetDevice(h->device);
+  (void)hipStreamSynchronize(h->stream);   // a round may still be in flight
+  for (size_t i = 0; i < h->tempering.size(); ++i)
+    if (h->tempering[i] == t) { h->tempering.erase(h->tempering.begin() + (long)i); break; }
+  free_tempering(t);
 }
 
 int pstat_sync(pstat_handle *h) {

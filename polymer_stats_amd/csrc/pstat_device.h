@@ -364,4 +364,17 @@ hipError_t launch_blocking(const double *x, int64_t nbatches, int64_t ncols, int
                            double *levels, hipStream_t stream);
 int64_t blocking_max_batches();
 
+// Replica exchange between cases (pstat_exchange.hip states the contract).
+struct ExchangeArgs {
+  int64_t per, C, n;           // chains per case, chains of the handle, monomers
+  int64_t npairs;              // pairs of this round's parity
+  uint32_t round;              // t
+  uint32_t seed_lo, seed_hi;   // the tempering object's seed
+  uint32_t pad_;
+};
+// one round: decisions for every (pair, chain) into flags[npairs * per], counted on the lower rung's case in attempted / accepted
+// [ncases]; then the accepted pairs' ang and obs rows swapped and their lag zeroed.  pairs[npairs][2] = (lower, upper) case.
+hipError_t launch_exchange(const ExchangeArgs &a, const DevState &s, const CaseConst *cases, const int32_t *pairs,
+                           unsigned char *flags, int64_t *attempted, int64_t *accepted, size_t elem, hipStream_t stream);
+
 }  // namespace pstat

@@ -91,6 +91,28 @@ class Ensemble:
         check(self._L.pstat_advance_series(self._h, series._s, int(nsteps), int(stepout)))
         series.rows += int(nsteps) // int(stepout)
 
+    # --- replica exchange between the cases (pstat_tempering_*)
+    def open_tempering(self, ladder, seed: int = 0) -> "Tempering":
+        """`ladder[i]`: the ladder case i belongs to (>= 0; ladders_by builds it), or -1 for a case that takes no part.  The
+        cases of a ladder differ in kT, seed and chain_id0 only; its rungs are ordered by kT."""
+        a = np.ascontiguousarray(ladder, dtype=np.int32)
+        if a.shape != (self.ncases,):
+            raise ValueError(f"ladder must name a ladder for each of the {self.ncases} cases")
+        t = C.c_void_p()
+        check(self._L.pstat_tempering_open(self._h, a.ctypes.data_as(C.POINTER(C.c_int32)), int(seed), C.byref(t)))
+        return Tempering(self, t)
+
+    def advance_tempered(self, t: "Tempering", nsteps: int, every: int):
+        """advance(every) followed by one exchange round, repeated; the remainder nsteps % every is advanced without an
+        exchange (asynchronous)."""
+        nsteps, every = int(nsteps), int(every)
+        if every < 1:
+            raise ValueError("every must be >= 1")
+        for _ in range(nsteps // every):
+            self.advance(every)
+            t.exchange()
+        self.advance(nsteps % every)
+
     # --- read-outs
     def reduce_into(self, dev_ptr: int, icase: int = -1):
         """Device-side reduction into a caller-owned device buffer of NRED doubles (async)."""
@@ -205,6 +227,44 @@ class Series:
         if self._s and self._e._h:      # (closing the ensemble closes its series)
             self._e._L.pstat_series_close(self._e._h, self._s)
         self._s = None
+
+
+class Tempering:
+    """Replica exchange between the cases of an Ensemble (Ensemble.open_tempering)."""
+
+    def __init__(self, ensemble: Ensemble, t):
+        self._e, self._t = ensemble, t
+
+    def exchange(self):
+        """One round: even rounds pair rungs (0, 1), (2, 3), ..., odd rounds (1, 2), (3, 4), ... (asynchronous)."""
+        check(self._e._L.pstat_tempering_exchange(self._e._h, self._t))
+
+    def stats(self):
+        """(attempted[ncases], accepted[ncases], rounds): exchanges of pairs of chains, counted on the lower rung of a pair,
+        and the exchange calls so far.  Synchronises."""
+        e = self._e
+        att = np.zeros(e.ncases, dtype=np.int64)
+        acc = np.zeros(e.ncases, dtype=np.int64)
+        rounds = C.c_int64(0)
+        ip = C.POINTER(C.c_int64)
+        check(e._L.pstat_tempering_stats(e._h, self._t, att.ctypes.data_as(ip), acc.ctypes.data_as(ip), C.byref(rounds)))
+        return att, acc, int(rounds.value)
+
+    def close(self):
+        if self._t and self._e._h:      # (closing the ensemble closes its tempering objects)
+            self._e._L.pstat_tempering_close(self._e._h, self._t)
+        self._t = None
+
+
+def ladders_by(cases, key=None) -> np.ndarray:
+    """The `ladder` array of Ensemble.open_tempering: cases that agree in everything but kT (and seed, chain_id0) share a
+    ladder; ids count the ladders in order of their first case.  `key`: a function of a Params whose equal values mean
+    "same ladder" (default: every field but kT, seed and chain_id0)."""
+    if key is None:
+        names = [f for f, _ in Params._fields_ if f not in ("kT", "seed", "chain_id0")]
+        key = lambda p: tuple(getattr(p, f) for f in names)
+    ids: dict = {}
+    return np.array([ids.setdefault(key(p), len(ids)) for p in cases], dtype=np.int32)
 
 
 class ErrorBars:

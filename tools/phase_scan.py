@@ -11,6 +11,9 @@ and the only exchange is one all-reduce(SUM) of the [points x 41] reduction tens
     python tools/phase_scan.py --chains 1 --steps 2500000 --error-bars 1000 ...   # error bars from ONE chain per point: the
         # production run is recorded on the device as 1000 batches; their blocked standard errors (Flyvbjerg-Petersen,
         # Series.error_bars) are the columns r3_blocked ... converged (0: the run is too short for r3, p3 or U at that point)
+    python tools/phase_scan.py --exchange 50 ...                 # replica exchange along kT: every column of equal E0 is a
+        # ladder, one exchange round after every 50 steps of the burn-in rungs and of the production run; adds the column
+        # swap_acceptance (Ensemble.open_tempering)
     python tools/phase_scan.py --gpus 8 ...                      # starts its own 8 ranks, one per GPU (RCCL)
     python tools/phase_scan.py --gpus 2 --backend gloo ...       # rehearsal: ranks may share a GPU, all-reduce via host
     python -m torch.distributed.run --nproc-per-node 8 tools/phase_scan.py --gpus 8 ...   (also fine)
@@ -34,6 +37,16 @@ def grid_points(points: int):
     return g
 
 
+def _all_reduced(dist, host, backend):
+    """SUM over the ranks of a host tensor (nccl reduces device tensors, gloo host ones)."""
+    if backend == "gloo":
+        dist.all_reduce(host)
+        return host
+    dev = host.cuda()
+    dist.all_reduce(dev)
+    return dev.cpu()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=200)
@@ -55,9 +68,18 @@ def main():
     ap.add_argument("--error-bars", type=int, default=0, metavar="N",
                     help="record the production run as N batches of steps / N steps and add their blocked standard errors as the columns "
                          "r3_blocked, p3_blocked, U_blocked, r3_ineff, U_ineff, converged (one rank only; a remainder steps %% N is run and belongs to no batch)")
+    ap.add_argument("--exchange", type=int, default=0, metavar="EVERY",
+                    help="replica exchange between the grid points of equal E0 (a ladder along kT): one round after every EVERY steps of "
+                         "the burn-in rungs and of the production run; adds the column swap_acceptance = accepted / attempted exchanges "
+                         "the point took part in during production (0: off; each rank exchanges among its own chains)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
 
+    if args.exchange < 0:
+        raise SystemExit(f"--exchange {args.exchange}: a number of steps between exchange rounds, or 0 for none")
+    if args.exchange and args.error_bars:
+        raise SystemExit("--exchange cannot be combined with --error-bars yet: exchanges interleaved with the recorded rows of a "
+                         "series are the follow-up to this option")
     if args.error_bars:
         if args.gpus > 1:       # the ranks hold different chains of the same point; their series are not merged
             raise SystemExit(f"--error-bars needs one rank, not --gpus {args.gpus}")
@@ -108,6 +130,8 @@ def main():
     red = torch.zeros(len(grid), ps.NRED, dtype=torch.float64, device="cuda")
     with torch.cuda.stream(stream):
         e = ps.Ensemble(cases, stream=stream.cuda_stream)
+        temper = e.open_tempering(ps.ladders_by(cases), seed=args.seed) if args.exchange else None
+        advance = (lambda nsteps: e.advance_tempered(temper, nsteps, args.exchange)) if temper else e.advance
         t0 = time.perf_counter()
         ladder = [float(x) for x in args.burn_schedule.split(",") if x.strip()]
         rungs = 0
@@ -116,12 +140,13 @@ def main():
                 e.scale_kT(mult)
                 if args.main == "clustering":
                     e.reset_sampler()
-                e.advance(args.burn_in)
+                advance(args.burn_in)
                 rungs += 1
             e.scale_kT(1.0)
             if args.main == "clustering":
                 e.reset_sampler()
             e.reset_averages()
+        swaps0 = temper.stats() if temper else None     # what the burn-in exchanged is not the production run's acceptance
         eb = None
         if args.error_bars:
             series = e.open_series(args.error_bars)
@@ -133,7 +158,7 @@ def main():
             finally:
                 series.close()
         else:
-            e.advance(args.steps)
+            advance(args.steps)
         for k in range(len(grid)):
             e.reduce_into(red[k].data_ptr(), icase=k)
         if world > 1:
@@ -147,15 +172,32 @@ def main():
         wall = time.perf_counter() - t0
         e.sync()
         info = e.launch_info()
+        swaps = None
+        if temper:
+            # counted on the lower rung of a pair: a point took part in the pairs with its neighbour above and below
+            att, acc, rounds = temper.stats()
+            att, acc, rounds = att - swaps0[0], acc - swaps0[1], rounds - swaps0[2]
+            swaps = torch.zeros(2, len(grid), dtype=torch.float64)
+            ids = ps.ladders_by(cases)
+            for l in set(ids.tolist()):
+                rung = sorted((k for k in range(len(grid)) if ids[k] == l), key=lambda k: (grid[k][1], k))
+                for lo, up in zip(rung, rung[1:]):
+                    for k in (lo, up):
+                        swaps[0, k] += float(att[lo])
+                        swaps[1, k] += float(acc[lo])
+            if world > 1:
+                swaps = _all_reduced(dist, swaps, args.backend)
     if rank == 0:
         host = red.cpu().numpy()
         rows = ["E0,kT,chains,r3,r3_stderr,rsq,p3,p3_stderr,psq,U,U_stderr,AR" +
-                (",r3_blocked,p3_blocked,U_blocked,r3_ineff,U_ineff,converged" if eb else "")]
+                (",r3_blocked,p3_blocked,U_blocked,r3_ineff,U_ineff,converged" if eb else "") + (",swap_acceptance" if swaps is not None else "")]
         R3, P3, U = (ps.EB_NAMES.index(q) for q in ("r3", "p3", "U"))
         for k, ((E0, kT), v) in enumerate(zip(grid, host)):
             s = ps.summary_from_reduction(v, args.steps)
             blocked = (eb.stderr[k, R3], eb.stderr[k, P3], eb.stderr[k, U], eb.inefficiency[k, R3], eb.inefficiency[k, U],
                        int(eb.converged[k, [R3, P3, U]].min())) if eb else ()
+            if swaps is not None:       # (a point without a partner, or a run shorter than --exchange, attempted none: 0)
+                blocked += (float(swaps[1, k] / swaps[0, k]) if swaps[0, k] > 0 else 0.0,)
             rows.append(",".join(f"{x:.12g}" for x in (E0, kT, s.num_chains, s.avg[2], s.stderr[2], s.avg[6], s.avg[9],
                                                         s.stderr[9], s.avg[13], s.avg[14], s.stderr[14], s.acceptance_ratio, *blocked)))
         text = "\n".join(rows) + "\n"
@@ -167,6 +209,9 @@ def main():
         print(f"# {len(grid)} grid points x {world * args.chains} chains, n={args.n}, {args.main} main, {args.energy}, {args.precision}, "
               f"{world} rank(s) [{args.backend if world > 1 else 'no collective'}]: {wall:.3f} s wall, {upd / wall:.3e} attempted updates/s; "
               f"{info.kernel.decode()}, {info.lanes_per_block} lanes x {info.blocks_per_cu} per CU", file=sys.stderr)
+        if swaps is not None:
+            print(f"# exchange every {args.exchange} steps: {rounds} rounds in production, {int(swaps[0].sum()) // 2} exchanges attempted, "
+                  f"{int(swaps[1].sum()) // 2} accepted", file=sys.stderr)
     e.close()
     if world > 1:
         dist.destroy_process_group()
