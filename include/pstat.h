@@ -291,7 +291,7 @@ int pstat_microstate(pstat_handle *h, int64_t chain, double out[7]);
 
 /* The quantities printed at mcmc_eap_chain.jl:365,386-395.  Synchronises.  Like every accessor that
  * synchronises (pstat_sync, pstat_reduce_host, pstat_rolling, pstat_microstate, pstat_chain_state,
- * pstat_chain_extras, pstat_checkpoint, pstat_series_read, pstat_series_error_bars) it fails with PSTAT_ERR_HIP if a launch since the last successful
+ * pstat_chain_extras, pstat_checkpoint, pstat_series_read, pstat_series_error_bars, pstat_hist_read) it fails with PSTAT_ERR_HIP if a launch since the last successful
  * call did not run to completion (a job of the persistent kernels timed out waiting for its predecessor):
  * the handle's averages are then not the averages of the steps it was asked for. */
 int pstat_summary_get(pstat_handle *h, int32_t icase, pstat_summary *out);
@@ -414,6 +414,65 @@ int pstat_tempering_exchange(pstat_handle *h, pstat_tempering *t);
 int pstat_tempering_stats(pstat_handle *h, pstat_tempering *t, int64_t *attempted /* [ncases] */, int64_t *accepted /* [ncases] */,
                           int64_t *rounds);
 void pstat_tempering_close(pstat_handle *h, pstat_tempering *t);
+
+/* Distributions on the device: per-case histograms of the chains' current configurations.  The reference has no equivalent on
+ * the device side of anything: its run/microstates-F*.jl studies write 10 000 trajectory rows per case only to histogram them
+ * afterwards, and its run/phases_* studies look for a bimodal P(U), P(p).  A histogram object belongs to the handle it was
+ * opened on; one record is one small launch on the handle's stream that reads DevState::obs of EVERY chain (the series keeps
+ * each case's first chain only) and writes the histogram's own buffers only.
+ * The contract (DESIGN.md 3.14 states it in full; polymer_stats_amd/csrc/pstat_hist.hip is the device's statement):
+ *   channel    PSTAT_HC_R1 .. PSTAT_HC_U (0..6): the seven doubles of pstat_microstate.  PSTAT_HC_RMAG (7): sqrt(r1 r1 + r2 r2 +
+ *              r3 r3), PSTAT_HC_PMAG (8) the same over p; products rounded singly, added left to right.
+ *   binning    is the formula, not the real interval.  The host computes inv = (double)nbins / (hi - lo) once; the device
+ *              t = (x - lo) * inv, two rounded operations.  x not finite: tails[2] += 1.  t < 0: tails[0] += 1.  t >= nbins:
+ *              tails[1] += 1.  Otherwise bin (int)t (truncation) += 1.  So lo falls in bin 0 and hi in the upper tail.
+ *   counts     64-bit integers: integer sums do not depend on order, so results are exact and reproducible.
+ *
+ *   pstat_hist_open     per_case = 0: specs[nspecs] is shared by all cases; per_case = 1: specs[ncases][nspecs], where a spec's
+ *                       channel and nbins agree across cases and only lo, hi may differ (U's range follows E0).  Before the
+ *                       device is touched, with a message naming the spec and case, PSTAT_ERR_INVALID_ARG: null arguments;
+ *                       nspecs outside 1..PSTAT_HIST_MAX_SPECS; a channel outside 0..8; nbins < 1; lo or hi not finite;
+ *                       hi <= lo, or inv not finite and positive (hi - lo overflows or is denormal).
+ *                       PSTAT_ERR_UNSUPPORTED: more than PSTAT_HIST_MAX_BINS bins per case (a workgroup keeps a case's bins in
+ *                       LDS); an umbrella-sampling handle (its samples carry
+ *                       per-chain weights whose gauge the rows do not hold: the reason error bars and exchange refuse it).
+ *                       PSTAT_ERR_NOMEM: the device allocation fails.
+ *   pstat_hist_record   adds the current configuration of every chain, one sample per chain and spec; asynchronous on the
+ *                       handle's stream, no host synchronisation: what a caller interleaves with pstat_tempering_exchange or
+ *                       pstat_advance_series.
+ *   pstat_advance_hist  pstat_advance(h, nsteps) with a record after every `stepout`-th step counted from the start of the call;
+ *                       a remainder nsteps % stepout is advanced and not recorded.  The chains, generators, counters and running
+ *                       sums end up exactly as after pstat_advance.
+ *   pstat_hist_read     counts[ncases][total_bins] (the specs' bins concatenated in order), tails[ncases][nspecs][3] (below,
+ *                       above, not finite) and *records; any of them may be NULL.  Per case and spec, bins + tails = records *
+ *                       num_chains.  Synchronises, and fails like every accessor that does after an incomplete launch.
+ *   pstat_hist_clear    zeroes the counts and the record count, on the stream.
+ *   pstat_hist_close    pstat_destroy closes the ones still open.  A histogram is not part of a checkpoint.
+ *   A histogram of another handle (or a closed one) is PSTAT_ERR_INVALID_ARG.  Every home, every precision and planar handles
+ *   are accepted; for a planar handle the y channels put every sample in whichever bin holds 0.
+ *   pstat_histogram_device  the same binning of the columns of any matrix x[nrows][stride] in DEVICE memory (a torch tensor, a
+ *                       series merged over ranks): a spec's `channel` is a column index below `stride`.  counts[total_bins] and
+ *                       tails[nspecs][3] are host memory (either may be NULL).  On `device` and `stream` (NULL: the default
+ *                       stream); synchronises the stream and leaves the calling thread's current device as it found it.  The
+ *                       argument errors above (a channel outside 0..stride-1 in place of 0..8) plus nrows < 0, all raised before
+ *                       the device is touched. */
+enum { PSTAT_HC_R1, PSTAT_HC_R2, PSTAT_HC_R3, PSTAT_HC_P1, PSTAT_HC_P2, PSTAT_HC_P3, PSTAT_HC_U, PSTAT_HC_RMAG, PSTAT_HC_PMAG,
+       PSTAT_HC_COUNT };
+#define PSTAT_HIST_MAX_BINS 8192
+#define PSTAT_HIST_MAX_SPECS 16
+typedef struct pstat_hist_spec { int32_t channel; int32_t nbins; double lo, hi; } pstat_hist_spec;
+typedef struct pstat_hist pstat_hist;
+int pstat_hist_open(pstat_handle *h, const pstat_hist_spec *specs /* [nspecs], or [ncases][nspecs] if per_case */, int32_t nspecs,
+                    int32_t per_case, pstat_hist **out);
+int pstat_hist_record(pstat_handle *h, pstat_hist *g);
+int pstat_advance_hist(pstat_handle *h, pstat_hist *g, int64_t nsteps, int64_t stepout);
+int pstat_hist_read(pstat_handle *h, pstat_hist *g, int64_t *counts /* [ncases][total_bins] */,
+                    int64_t *tails /* [ncases][nspecs][3] */, int64_t *records);
+int pstat_hist_clear(pstat_handle *h, pstat_hist *g);
+void pstat_hist_close(pstat_handle *h, pstat_hist *g);
+int pstat_histogram_device(const double *x /* DEVICE memory, [nrows][stride] */, int64_t nrows, int64_t stride,
+                           const pstat_hist_spec *specs, int32_t nspecs, int32_t device, void *stream,
+                           int64_t *counts /* host [total_bins] */, int64_t *tails /* host [nspecs][3] */);
 
 /* Per-chain accessors for tests and tooling (host buffers).  angles: theta[n] then phi[n] as
  * doubles, radians; sums: the 16 per-chain running sums in rolling.csv order;

@@ -225,6 +225,52 @@ def check_error_bars(pargs: dict, nbatches: int, write_csv: bool = False, device
                               "differences of the device's Float64 reductions")
 
 
+def parse_hist(text: str):
+    """One --hist CHANNEL:LO:HI:NBINS of tools/run_sweep.py -> (channel name, lo, hi, nbins)."""
+    parts = str(text).split(":")
+    try:
+        if len(parts) != 4 or parts[0] not in _lib.HC_NAMES:
+            raise ValueError
+        lo, hi, nbins = float(parts[1]), float(parts[2]), int(parts[3])
+    except ValueError:
+        raise ReferenceError_(f"--hist '{text}' not understood: CHANNEL:LO:HI:NBINS with CHANNEL one of {', '.join(_lib.HC_NAMES)}")
+    if not (np.isfinite(lo) and np.isfinite(hi) and hi > lo and nbins >= 1):
+        raise ReferenceError_(f"--hist '{text}': needs finite LO < HI and NBINS >= 1")
+    return parts[0], lo, hi, nbins
+
+
+def check_hist(pargs: dict, specs, write_csv: bool = False, devices: int | None = None, error_bars: int = 0):
+    """What --hist (tools/run_sweep.py; run_cases(..., hist=[...])) cannot be combined with, refused before any GPU work: what
+    --error-bars cannot, for the same reasons (check_error_bars), and --error-bars itself."""
+    if devices is None:
+        devices = len([d for d in str(pargs["devices"]).split(",") if d != ""][:max(1, int(pargs["num-chains"]))])
+    if not 1 <= len(specs) <= _lib.HIST_MAX_SPECS:
+        raise ReferenceError_(f"--hist: between 1 and {_lib.HIST_MAX_SPECS} histograms, not {len(specs)}")
+    if sum(s[3] for s in specs) > _lib.HIST_MAX_BINS:
+        raise ReferenceError_(f"--hist: {sum(s[3] for s in specs)} bins per case, at most {_lib.HIST_MAX_BINS}")
+    stepout = int(pargs["stepout"])
+    if not 1 <= stepout <= int(pargs["num-steps"]):
+        raise ReferenceError_(f"--hist samples every --stepout steps of the production run: --stepout {stepout} must be in 1 .. "
+                              f"--num-steps {pargs['num-steps']}")
+    if error_bars:
+        raise ReferenceError_("--hist cannot be combined with --error-bars: each records the production run in its own way")
+    if write_csv:
+        raise ReferenceError_("--hist cannot be combined with --csv: the production run is recorded as histograms, not as "
+                              "--stepout rows")
+    if devices > 1:
+        raise ReferenceError_(f"--hist needs one device, not {devices}: the devices hold different chains of a case and "
+                              "their histograms are not merged")
+    if int(pargs.get("num-inits", 1)) != 1:
+        raise ReferenceError_(f"--hist cannot be combined with --num-inits {pargs['num-inits']}: a re-initialisation "
+                              "between samples is not a stationary series")
+    if pargs["umbrella-sampling"]:
+        raise ReferenceError_("--hist cannot be combined with --umbrella-sampling: the samples carry per-chain weights whose "
+                              "gauge the counts do not hold")
+    if pargs["numeric-type"] != "float64":
+        raise ReferenceError_(f"--hist cannot be combined with --numeric-type {pargs['numeric-type']}: the samples are the "
+                              "device's Float64 microstates")
+
+
 def burn_ladder(pargs: dict) -> list[float]:
     """--burn-schedule of the two clustering mains: a Julia vector literal of kT multipliers."""
     try:
@@ -436,6 +482,24 @@ class _Pool:
         self.advance(nsteps)
         return eb
 
+    def histograms(self, nsteps, stepout, specs):
+        """advance(nsteps) with every chain's configuration added, after every `stepout`-th step, to the histograms `specs`
+        ((channel name, lo, hi, nbins), shared by all cases) on the device -> HistResult.  Made TWICE from the same state like
+        error_bars, and for the same reason: recorded, then, from a checkpoint taken before it, as the one launch of
+        advance(nsteps), so that the averages the caller prints are exactly those of a run without histograms."""
+        check_hist(self.plist[0], specs, devices=len(self.parts))
+        e = self.parts[0]
+        image = e.checkpoint()
+        h = e.open_hist([_lib.hist_spec(channel, nbins, lo, hi) for channel, lo, hi, nbins in specs])
+        try:
+            e.advance_hist(h, (nsteps // stepout) * stepout, stepout)      # (the remainder would be lost with the restore anyway)
+            res = h.read()
+        finally:
+            h.close()
+            e.restore(image)      # also when the recorded run failed: the handle is never left mid-run
+        self.advance(nsteps)
+        return res
+
     def chain0(self, k=0):
         return self.parts[0].chain_state(k * self.counts[0])      # the first chain of case k
 
@@ -528,14 +592,15 @@ class CsvFiles:
 
 
 def recorded_stage(pool, nsteps, write: bool, traj_header, roll_header, rows, angles=False, runs=(None,), report=None,
-                   error_bars: int = 0):
+                   error_bars: int = 0, hist=None):
     """One recorded run of `nsteps` for every case of the pool, the body of the reference's mcmc(nsteps, pargs[, chain]):
     with `write` the two CSV files of every case (headers `traj_header(pargs)` and `roll_header`, a row per --stepout
     steps: `rows(pargs, step, micro, ang, summary)` -> the case's (trajectory row, rolling row)), then the summaries, the
     total time and the acceptance rates on stderr (`report(k, summary)` right after case k's rate).  `runs` yields the
     progress line of each run of `nsteps` into the same files (the fixed-force main's inits; it is resumed after the run).
     `error_bars` = N > 0 (without `write`): the run is recorded as N batches instead (_Pool.error_bars) and the pool's `info`
-    gets their blocked standard errors under "error_bars"."""
+    gets their blocked standard errors under "error_bars".  `hist` = [(channel, lo, hi, nbins), ...] (without `write`): every
+    chain is histogrammed every --stepout steps of the run (_Pool.histograms) and `info` gets the HistResult under "hist"."""
     plist = pool.plist
     pargs = plist[0]
     stepout = int(pargs["stepout"]) if write else 0
@@ -557,6 +622,11 @@ def recorded_stage(pool, nsteps, write: bool, traj_header, roll_header, rows, an
                 eb = pool.error_bars(nsteps, error_bars)
                 if pool.info is not None:
                     pool.info["error_bars"] = eb
+                continue
+            if hist:
+                res = pool.histograms(nsteps, int(pargs["stepout"]), hist)
+                if pool.info is not None:
+                    pool.info["hist"] = res
                 continue
             for step, micro, ang, sums in pool.recorded(nsteps, stepout, angles=angles, tick=tick):
                 for k in range(len(files)):
@@ -593,6 +663,18 @@ def error_lines(main, eb, k: int, pargs) -> list[str]:
             f"batches = {eb.nbatches}",
             f"inefficiency = {jl_vector(eb.inefficiency[k])}",
             f"converged = {jl_vector(eb.converged[k].astype(float))}"]
+
+
+def hist_lines(res, specs, k: int, chains: int) -> list[str]:
+    """`<case>.hist`: per histogram a header line naming channel, lo, hi, nbins, records and chains, the `bin_lo,bin_hi,count`
+    rows, then the three tails."""
+    out = []
+    for i, (channel, lo, hi, nbins) in enumerate(specs):
+        edges = res.edges(i, k)
+        out.append(f"# channel={channel} lo={lo!r} hi={hi!r} nbins={nbins} records={res.records} chains={chains}")
+        out += [f"{float(edges[j])!r},{float(edges[j + 1])!r},{int(c)}" for j, c in enumerate(res.counts[i][k])]
+        out += [f"{name},{int(c)}" for name, c in zip(("below", "above", "not_finite"), res.tails[k, i])]
+    return out
 
 
 def summary_lines(sas, vas, ar, pargs, extra=()) -> list[str]:

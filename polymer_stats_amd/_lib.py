@@ -32,6 +32,10 @@ EB_NAMES = OBS_NAMES + ["AR", "cos2", "psi"]
 EB_FIELDS = ["mean", "stderr", "stderr_err", "inefficiency", "level", "converged"]
 BLOCK_LEVELS = 24
 BLOCK_MAX_BATCHES = 40960
+# histogram channels (pstat_hist_*, the PSTAT_HC_* enum): the seven doubles of a microstate, then |r| and |p|
+HC_NAMES = ["r1", "r2", "r3", "p1", "p2", "p3", "U", "rmag", "pmag"]
+HIST_MAX_BINS = 8192
+HIST_MAX_SPECS = 16
 
 # every symbol include/pstat.h declares (tests check the built library exports all of them)
 SYMBOLS = [
@@ -43,6 +47,8 @@ SYMBOLS = [
     "pstat_series_open", "pstat_advance_series", "pstat_series_read", "pstat_series_clear", "pstat_series_close",
     "pstat_create_planar", "pstat_series_error_bars", "pstat_blocking_device",
     "pstat_tempering_open", "pstat_tempering_exchange", "pstat_tempering_stats", "pstat_tempering_close",
+    "pstat_hist_open", "pstat_hist_record", "pstat_advance_hist", "pstat_hist_read", "pstat_hist_clear", "pstat_hist_close",
+    "pstat_histogram_device",
 ]
 ABI_VERSION = 6
 
@@ -73,6 +79,20 @@ class Summary(C.Structure):
                 ("attempted_updates", C.c_double),
                 ("extra_avg", C.c_double * 2), ("extra_stderr", C.c_double * 2),
                 ("nan_rejects", C.c_int64), ("chains_collapsed", C.c_int64)]
+
+
+class HistSpec(C.Structure):
+    _fields_ = [("channel", C.c_int32), ("nbins", C.c_int32), ("lo", C.c_double), ("hi", C.c_double)]
+
+
+def hist_spec(channel, nbins: int, lo: float, hi: float) -> HistSpec:
+    """One histogram spec: `channel` a name of HC_NAMES or an index (a column index for histogram_device), `nbins` bins of
+    the formula bin = int((x - lo) * (nbins / (hi - lo)))."""
+    if isinstance(channel, str):
+        if channel not in HC_NAMES:
+            raise ValueError(f"unknown histogram channel {channel!r}: one of {', '.join(HC_NAMES)}")
+        channel = HC_NAMES.index(channel)
+    return HistSpec(int(channel), int(nbins), float(lo), float(hi))
 
 
 class LaunchInfo(C.Structure):
@@ -138,6 +158,15 @@ def load():
     L.pstat_tempering_stats.argtypes = [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.pstat_tempering_close.argtypes = [vp, vp]
     L.pstat_tempering_close.restype = None
+    ip = C.POINTER(C.c_int64)
+    L.pstat_hist_open.argtypes = [vp, C.POINTER(HistSpec), i32, i32, C.POINTER(vp)]
+    L.pstat_hist_record.argtypes = [vp, vp]
+    L.pstat_advance_hist.argtypes = [vp, vp, i64, i64]
+    L.pstat_hist_read.argtypes = [vp, vp, ip, ip, ip]
+    L.pstat_hist_clear.argtypes = [vp, vp]
+    L.pstat_hist_close.argtypes = [vp, vp]
+    L.pstat_hist_close.restype = None
+    L.pstat_histogram_device.argtypes = [vp, i64, i64, C.POINTER(HistSpec), i32, i32, vp, ip, ip]
     if L.pstat_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI version {L.pstat_abi_version()}, this binding needs {ABI_VERSION}: "
                           "rebuild it with `make -C polymer_stats_amd/csrc`")

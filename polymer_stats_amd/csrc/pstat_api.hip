@@ -112,6 +112,7 @@ struct pstat_handle {
   int failed_job = 0;               // sticky: 1 + the job of a persistent launch that timed out (0 = none)
   std::vector<pstat_series *> series;   // series still open (pstat_destroy closes them)
   std::vector<pstat_tempering *> tempering;   // tempering objects still open (likewise)
+  std::vector<pstat_hist *> hists;      // histograms still open (likewise)
 };
 
 // The stepout time series of one handle: rows recorded on the device by launch_record, read back in bulk.
@@ -131,6 +132,15 @@ struct pstat_tempering {
   int32_t *d_pairs[2] = {nullptr, nullptr};   // [npairs][2] = (lower, upper rung's case)
   unsigned char *d_flags = nullptr; // [max npairs * chains per case]
   int64_t *d_counts = nullptr;      // [2][ncases]: attempted, accepted, on the lower rung's case
+};
+
+// Per-case histograms of one handle (pstat_hist.hip).
+struct pstat_hist {
+  int32_t nspecs = 0, total_bins = 0, per_case = 0;
+  int64_t records = 0;              // records enqueued since open / the last clear (known when a record is enqueued)
+  HistSpec *d_specs = nullptr;      // [ncases][nspecs] if per_case, else [nspecs]
+  int64_t *d_counts = nullptr;      // [ncases][total_bins], then tails [ncases][nspecs][3]
+  size_t slots = 0;                 // int64 words of d_counts
 };
 
 namespace {
@@ -590,6 +600,65 @@ void free_tempering(pstat_tempering *t) {
   delete t;
 }
 
+pstat_hist *own_hist(pstat_handle *h, pstat_hist *g) {
+  for (pstat_hist *mine : h->hists)
+    if (mine == g) return g;
+  return nullptr;
+}
+
+void free_hist(pstat_hist *g) {
+  (void)hipFree(g->d_specs);
+  (void)hipFree(g->d_counts);
+  delete g;
+}
+
+// Checks specs[rows][nspecs] (rows = 1, or the cases of a per-case table) and states them as the device reads them; touches no
+// device.  nchannels: channels are 0 .. nchannels - 1 (`what` names that range's owner in the message).
+int hist_specs(const pstat_hist_spec *specs, int32_t nspecs, int64_t rows, int64_t nchannels, const char *what,
+               std::vector<HistSpec> &dev, int32_t *total_bins) {
+  if (nspecs < 1 || nspecs > PSTAT_HIST_MAX_SPECS)
+    return fail(PSTAT_ERR_INVALID_ARG, "nspecs must be in 1 .. %d, not %d", PSTAT_HIST_MAX_SPECS, nspecs);
+  int64_t total = 0;
+  for (int64_t k = 0; k < rows; ++k)
+    for (int32_t i = 0; i < nspecs; ++i) {
+      const pstat_hist_spec &sp = specs[k * nspecs + i];
+      if (sp.channel < 0 || sp.channel >= nchannels)
+        return fail(PSTAT_ERR_INVALID_ARG, "spec %d, case %lld: channel %d is outside 0 .. %lld (%s)", i, (long long)k, sp.channel,
+                    (long long)nchannels - 1, what);
+      if (sp.nbins < 1) return fail(PSTAT_ERR_INVALID_ARG, "spec %d, case %lld: nbins must be >= 1, not %d", i, (long long)k, sp.nbins);
+      if (!std::isfinite(sp.lo) || !std::isfinite(sp.hi))
+        return fail(PSTAT_ERR_INVALID_ARG, "spec %d, case %lld: lo = %g, hi = %g must be finite", i, (long long)k, sp.lo, sp.hi);
+      if (!(sp.hi > sp.lo))
+        return fail(PSTAT_ERR_INVALID_ARG, "spec %d, case %lld: hi = %.17g must be above lo = %.17g", i, (long long)k, sp.hi, sp.lo);
+      const double inv = (double)sp.nbins / (sp.hi - sp.lo);
+      if (!std::isfinite(inv) || !(inv > 0.0))   // t = (x - lo) * inv is then never NaN for a finite x
+        return fail(PSTAT_ERR_INVALID_ARG, "spec %d, case %lld: hi - lo = %g leaves no finite positive nbins / (hi - lo) for %d bins",
+                    i, (long long)k, sp.hi - sp.lo, sp.nbins);
+      if (k > 0 && (sp.channel != specs[i].channel || sp.nbins != specs[i].nbins))
+        return fail(PSTAT_ERR_INVALID_ARG, "spec %d, case %lld: channel %d, nbins %d differ from case 0's %d, %d; only lo and hi "
+                    "may differ between cases", i, (long long)k, sp.channel, sp.nbins, specs[i].channel, specs[i].nbins);
+      if (k == 0) total += sp.nbins;
+    }
+  if (total > PSTAT_HIST_MAX_BINS)
+    return fail(PSTAT_ERR_UNSUPPORTED, "%lld bins per case: at most %d (a workgroup keeps a case's bins in LDS)", (long long)total,
+                PSTAT_HIST_MAX_BINS);
+  dev.resize((size_t)(rows * nspecs));
+  for (int64_t k = 0; k < rows; ++k) {
+    int32_t offset = 0;
+    for (int32_t i = 0; i < nspecs; ++i) {
+      const pstat_hist_spec &sp = specs[k * nspecs + i];
+      dev[(size_t)(k * nspecs + i)] = HistSpec{sp.channel, sp.nbins, offset, 0, sp.lo, (double)sp.nbins / (sp.hi - sp.lo)};
+      offset += sp.nbins;
+    }
+  }
+  *total_bins = (int32_t)total;
+  return PSTAT_OK;
+}
+
+HistArgs hist_args(const pstat_handle *h, const pstat_hist *g) {
+  return HistArgs{h->base.num_chains, h->ncases, h->S.C, 1, g->nspecs, g->total_bins, g->per_case, 0};
+}
+
 // device scratch of one call
 struct DeviceDoubles {
   double *p = nullptr;
@@ -833,6 +902,7 @@ void pstat_destroy(pstat_handle *h) {
   for (auto &b : h->bufs) (void)hipFree(b.ptr);
   for (pstat_series *s : h->series) free_series(s);
   for (pstat_tempering *t : h->tempering) free_tempering(t);
+  for (pstat_hist *g : h->hists) free_hist(g);
   if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }
@@ -1113,6 +1183,143 @@ void pstat_tempering_close(pstat_handle *h, pstat_tempering *t) {
   for (size_t i = 0; i < h->tempering.size(); ++i)
     if (h->tempering[i] == t) { h->tempering.erase(h->tempering.begin() + (long)i); break; }
   free_tempering(t);
+}
+
+int pstat_hist_open(pstat_handle *h, const pstat_hist_spec *specs, int32_t nspecs, int32_t per_case, pstat_hist **out) {
+  if (!h || !specs || !out) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
+  *out = nullptr;
+  pstat_hist *g = nullptr;
+  try {
+    std::vector<HistSpec> dev;
+    int32_t total_bins = 0;
+    PSTAT_TRY(hist_specs(specs, nspecs, per_case ? h->ncases : 1, PSTAT_HC_COUNT, "the PSTAT_HC_* channels", dev, &total_bins));
+    if (h->cfg.umbrella)
+      return fail(PSTAT_ERR_UNSUPPORTED, "histograms under --umbrella-sampling: the samples carry per-chain weights whose gauge "
+                  "the counts do not hold");
+    PSTAT_TRY(set_device(h));
+    g = new (std::nothrow) pstat_hist;
+    if (!g) return fail(PSTAT_ERR_NOMEM, "host allocation failed");
+    g->nspecs = nspecs;
+    g->total_bins = total_bins;
+    g->per_case = per_case ? 1 : 0;
+    g->slots = (size_t)h->ncases * ((size_t)total_bins + 3 * (size_t)nspecs);
+    hipError_t e = hipMalloc((void **)&g->d_specs, dev.size() * sizeof(HistSpec));
+    if (e == hipSuccess) e = hipMalloc((void **)&g->d_counts, g->slots * sizeof(int64_t));
+    if (e != hipSuccess) {
+      const size_t slots = g->slots;
+      free_hist(g);
+      return fail(PSTAT_ERR_NOMEM, "histogram of %zu counters: %s", slots, hipGetErrorString(e));
+    }
+    e = hipMemcpy(g->d_specs, dev.data(), dev.size() * sizeof(HistSpec), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemsetAsync(g->d_counts, 0, g->slots * sizeof(int64_t), h->stream);   // ahead of the first record
+    if (e != hipSuccess) {
+      free_hist(g);
+      return fail(PSTAT_ERR_HIP, "histogram tables: %s", hipGetErrorString(e));
+    }
+    h->hists.push_back(g);
+  } catch (const std::bad_alloc &) {
+    if (g) free_hist(g);
+    return fail(PSTAT_ERR_NOMEM, "host allocation failed");
+  }
+  *out = g;
+  return PSTAT_OK;
+}
+
+int pstat_hist_record(pstat_handle *h, pstat_hist *g) {
+  if (!h || !g) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
+  if (!own_hist(h, g)) return fail(PSTAT_ERR_INVALID_ARG, "the histogram is not an open histogram of this handle");
+  PSTAT_TRY(set_device(h));
+  if (h->failed_job) return report_failed_job(h);
+  HIP_TRY(launch_hist(hist_args(h, g), h->S.obs, g->d_specs, g->d_counts, g->d_counts + (size_t)h->ncases * (size_t)g->total_bins,
+                      h->stream));
+  g->records += 1;
+  return PSTAT_OK;
+}
+
+int pstat_advance_hist(pstat_handle *h, pstat_hist *g, int64_t nsteps, int64_t stepout) {
+  if (!h || !g) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
+  if (!own_hist(h, g)) return fail(PSTAT_ERR_INVALID_ARG, "the histogram is not an open histogram of this handle");
+  if (nsteps < 0) return fail(PSTAT_ERR_INVALID_ARG, "nsteps must be >= 0");
+  if (stepout < 1) return fail(PSTAT_ERR_INVALID_ARG, "stepout must be >= 1");
+  PSTAT_TRY(set_device(h));
+  if (h->failed_job) return report_failed_job(h);
+  const int64_t nrec = nsteps / stepout;
+  for (int64_t i = 0; i < nrec; ++i) {
+    PSTAT_TRY(enqueue_steps(h, stepout));
+    PSTAT_TRY(pstat_hist_record(h, g));
+  }
+  return enqueue_steps(h, nsteps - nrec * stepout);
+}
+
+int pstat_hist_read(pstat_handle *h, pstat_hist *g, int64_t *counts, int64_t *tails, int64_t *records) {
+  if (!h || !g) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
+  if (!own_hist(h, g)) return fail(PSTAT_ERR_INVALID_ARG, "the histogram is not an open histogram of this handle");
+  PSTAT_TRY(set_device(h));
+  PSTAT_TRY(sync_checked(h));
+  const size_t nbins = (size_t)h->ncases * (size_t)g->total_bins;
+  if (counts) HIP_TRY(hipMemcpy(counts, g->d_counts, nbins * sizeof(int64_t), hipMemcpyDeviceToHost));
+  if (tails) HIP_TRY(hipMemcpy(tails, g->d_counts + nbins, (g->slots - nbins) * sizeof(int64_t), hipMemcpyDeviceToHost));
+  if (records) *records = g->records;
+  return PSTAT_OK;
+}
+
+int pstat_hist_clear(pstat_handle *h, pstat_hist *g) {
+  if (!h || !g) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
+  if (!own_hist(h, g)) return fail(PSTAT_ERR_INVALID_ARG, "the histogram is not an open histogram of this handle");
+  PSTAT_TRY(set_device(h));
+  HIP_TRY(hipMemsetAsync(g->d_counts, 0, g->slots * sizeof(int64_t), h->stream));   // behind the records already enqueued
+  g->records = 0;
+  return PSTAT_OK;
+}
+
+void pstat_hist_close(pstat_handle *h, pstat_hist *g) {
+  if (!h || !g || !own_hist(h, g)) return;
+  (void)hipSetDevice(h->device);
+  (void)hipStreamSynchronize(h->stream);   // a record may still be in flight
+  for (size_t i = 0; i < h->hists.size(); ++i)
+    if (h->hists[i] == g) { h->hists.erase(h->hists.begin() + (long)i); break; }
+  free_hist(g);
+}
+
+int pstat_histogram_device(const double *x, int64_t nrows, int64_t stride, const pstat_hist_spec *specs, int32_t nspecs,
+                           int32_t device, void *stream, int64_t *counts, int64_t *tails) {
+  if (!x || !specs) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
+  if (nrows < 0) return fail(PSTAT_ERR_INVALID_ARG, "nrows must be >= 0, not %lld", (long long)nrows);
+  if (stride < 1) return fail(PSTAT_ERR_INVALID_ARG, "stride must be >= 1, not %lld", (long long)stride);
+  std::vector<HistSpec> dev;
+  std::vector<int64_t> host;
+  int32_t total_bins = 0;
+  try {
+    PSTAT_TRY(hist_specs(specs, nspecs, 1, stride, "the columns below stride", dev, &total_bins));
+    host.resize((size_t)total_bins + 3 * (size_t)nspecs);
+  } catch (const std::bad_alloc &) {
+    return fail(PSTAT_ERR_NOMEM, "host allocation failed");
+  }
+  int before = -1;      // the caller's current device is put back, as pstat_blocking_device does
+  if (hipGetDevice(&before) != hipSuccess) before = -1;
+  if (hipSetDevice(device) != hipSuccess) return fail(PSTAT_ERR_NO_DEVICE, "device %d is not available", device);
+  const hipStream_t st = (hipStream_t)stream;
+  const size_t bytes = host.size() * sizeof(int64_t);
+  HistSpec *d_specs = nullptr;
+  int64_t *d_counts = nullptr;
+  int rc = PSTAT_OK;
+  hipError_t e = hipMalloc((void **)&d_specs, dev.size() * sizeof(HistSpec));
+  if (e == hipSuccess) e = hipMalloc((void **)&d_counts, bytes);
+  if (e != hipSuccess) rc = fail(PSTAT_ERR_NOMEM, "hipMalloc failed: %s", hipGetErrorString(e));
+  if (e == hipSuccess) e = hipMemcpyAsync(d_specs, dev.data(), dev.size() * sizeof(HistSpec), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemsetAsync(d_counts, 0, bytes, st);
+  if (e == hipSuccess)
+    e = launch_hist(HistArgs{nrows, 1, 1, stride, nspecs, total_bins, 0, 1}, x, d_specs, d_counts, d_counts + total_bins, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(host.data(), d_counts, bytes, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess && rc == PSTAT_OK) rc = fail(PSTAT_ERR_HIP, "pstat_histogram_device: %s", hipGetErrorString(e));
+  (void)hipFree(d_specs);
+  (void)hipFree(d_counts);
+  if (before >= 0 && before != device) (void)hipSetDevice(before);
+  if (rc) return rc;
+  if (counts) std::memcpy(counts, host.data(), (size_t)total_bins * sizeof(int64_t));
+  if (tails) std::memcpy(tails, host.data() + total_bins, 3 * (size_t)nspecs * sizeof(int64_t));
+  return PSTAT_OK;
 }
 
 int pstat_sync(pstat_handle *h) {

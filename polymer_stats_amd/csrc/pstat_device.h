@@ -377,4 +377,26 @@ struct ExchangeArgs {
 hipError_t launch_exchange(const ExchangeArgs &a, const DevState &s, const CaseConst *cases, const int32_t *pairs,
                            unsigned char *flags, int64_t *attempted, int64_t *accepted, size_t elem, hipStream_t stream);
 
+// Per-case histograms of the chains' current configurations (pstat_hist.hip states the binning contract).
+struct HistSpec {              // one spec as the device reads it
+  int32_t channel;             // PSTAT_HC_* of a handle's histogram; a column of the matrix for pstat_histogram_device
+  int32_t nbins;
+  int32_t offset;              // of the spec's first bin among the case's total_bins
+  int32_t pad_;
+  double lo, inv;              // inv = (double)nbins / (hi - lo), computed once on the host
+};
+struct HistArgs {
+  int64_t per;                 // samples per case: chains per case, or the rows of the matrix
+  int64_t ncases;
+  int64_t stride;              // between the channels of one sample's source: C for DevState::obs, 1 for a matrix
+  int64_t pitch;               // between consecutive samples: 1 for DevState::obs, the matrix's stride
+  int32_t nspecs, total_bins;
+  int32_t per_case;            // specs[ncases][nspecs] instead of specs[nspecs]
+  int32_t matrix;              // channels are plain columns (no magnitude channels)
+};
+// one record: for every case k and spec i, counts[k][offset_i + bin] or tails[k][i][0..2] += 1 per sample; src = DevState::obs,
+// or the matrix
+hipError_t launch_hist(const HistArgs &a, const double *src, const HistSpec *specs, int64_t *counts, int64_t *tails,
+                       hipStream_t stream);
+
 }  // namespace pstat

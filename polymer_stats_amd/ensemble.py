@@ -113,6 +113,24 @@ class Ensemble:
             t.exchange()
         self.advance(nsteps % every)
 
+    # --- per-case histograms of the chains' current configurations (pstat_hist_*)
+    def open_hist(self, specs, per_case: bool = False) -> "Hist":
+        """`specs`: a list of hist_spec(...) shared by all cases, or with `per_case` one such list per case (same channels and
+        bin counts, lo and hi free).  Every record adds one sample per chain and spec."""
+        rows = [list(r) for r in specs] if per_case else [list(specs)]
+        if per_case and (len(rows) != self.ncases or any(len(r) != len(rows[0]) for r in rows)):
+            raise ValueError(f"per-case specs must be {self.ncases} lists of equal length")
+        nspecs = len(rows[0])
+        flat = [s for r in rows for s in r]
+        arr = (_lib.HistSpec * max(len(flat), 1))(*flat)
+        g = C.c_void_p()
+        check(self._L.pstat_hist_open(self._h, arr, nspecs, 1 if per_case else 0, C.byref(g)))
+        return Hist(self, g, rows)
+
+    def advance_hist(self, hist: "Hist", nsteps: int, stepout: int):
+        """advance(nsteps) with a record into `hist` after every `stepout`-th step (asynchronous)."""
+        check(self._L.pstat_advance_hist(self._h, hist._g, int(nsteps), int(stepout)))
+
     # --- read-outs
     def reduce_into(self, dev_ptr: int, icase: int = -1):
         """Device-side reduction into a caller-owned device buffer of NRED doubles (async)."""
@@ -254,6 +272,84 @@ class Tempering:
         if self._t and self._e._h:      # (closing the ensemble closes its tempering objects)
             self._e._L.pstat_tempering_close(self._e._h, self._t)
         self._t = None
+
+
+def _edges(spec) -> np.ndarray:
+    return spec.lo + (spec.hi - spec.lo) * np.arange(spec.nbins + 1) / spec.nbins
+
+
+class HistResult:
+    """What Hist.read returns.  `counts[i]`: int64 [ncases, nbins_i] of spec i; `tails`: int64 [ncases, nspecs, 3] (below lo,
+    at or above hi, not finite); `records`; `samples`: records * chains per case, which bins + tails add up to for every case
+    and spec."""
+
+    def __init__(self, specs, counts, tails, records: int, samples: int):
+        self.specs, self.counts, self.tails, self.records, self.samples = specs, counts, tails, records, samples
+
+    def _spec(self, i: int, case: int):
+        return self.specs[case if len(self.specs) > 1 else 0][i]
+
+    def edges(self, i: int, case: int = 0) -> np.ndarray:
+        """The nbins + 1 nominal bin edges of spec i (the binning itself is the formula of include/pstat.h)."""
+        return _edges(self._spec(i, case))
+
+    def centers(self, i: int, case: int = 0) -> np.ndarray:
+        e = self.edges(i, case)
+        return 0.5 * (e[:-1] + e[1:])
+
+    def density(self, i: int, case: int = 0) -> np.ndarray:
+        """counts / (samples * bin width): integrates to the fraction of the samples that fell inside [lo, hi)."""
+        sp = self._spec(i, case)
+        return self.counts[i][case] / (max(self.samples, 1) * (sp.hi - sp.lo) / sp.nbins)
+
+
+class Hist:
+    """Histograms recorded on the device (Ensemble.open_hist, pstat_hist_*)."""
+
+    def __init__(self, ensemble: Ensemble, g, specs):
+        self._e, self._g, self.specs = ensemble, g, specs
+
+    def record(self):
+        """Adds the current configuration of every chain (asynchronous)."""
+        check(self._e._L.pstat_hist_record(self._e._h, self._g))
+
+    def read(self) -> HistResult:
+        """Synchronises."""
+        e = self._e
+        nb = [int(s.nbins) for s in self.specs[0]]
+        counts = np.zeros((e.ncases, sum(nb)), dtype=np.int64)
+        tails = np.zeros((e.ncases, len(nb), 3), dtype=np.int64)
+        records = C.c_int64(0)
+        ip = C.POINTER(C.c_int64)
+        check(e._L.pstat_hist_read(e._h, self._g, counts.ctypes.data_as(ip), tails.ctypes.data_as(ip), C.byref(records)))
+        off = np.concatenate([[0], np.cumsum(nb)])
+        per = [np.ascontiguousarray(counts[:, off[i]:off[i + 1]]) for i in range(len(nb))]
+        return HistResult(self.specs, per, tails, int(records.value), int(records.value) * e.num_chains)
+
+    def clear(self):
+        check(self._e._L.pstat_hist_clear(self._e._h, self._g))
+
+    def close(self):
+        if self._g and self._e._h:      # (closing the ensemble closes its histograms)
+            self._e._L.pstat_hist_close(self._e._h, self._g)
+        self._g = None
+
+
+def histogram_device(ptr: int, nrows: int, stride: int, specs, device: int = 0, stream: int | None = None):
+    """Histograms of columns of a float64 matrix x[nrows][stride] in DEVICE memory at `ptr` (e.g. tensor.data_ptr() of a
+    contiguous torch tensor); a spec's channel is its column.  Returns (counts: one int64 [nbins] array per spec,
+    tails int64 [nspecs, 3]) (pstat_histogram_device).  Synchronises `stream`."""
+    specs = list(specs)
+    arr = (_lib.HistSpec * max(len(specs), 1))(*specs)
+    nb = [max(int(s.nbins), 0) for s in specs]
+    counts = np.zeros(max(sum(nb), 1), dtype=np.int64)
+    tails = np.zeros((max(len(specs), 1), 3), dtype=np.int64)
+    ip = C.POINTER(C.c_int64)
+    check(_lib.load().pstat_histogram_device(C.c_void_p(ptr), int(nrows), int(stride), arr, len(specs), int(device),
+                                             C.c_void_p(stream) if stream else None, counts.ctypes.data_as(ip),
+                                             tails.ctypes.data_as(ip)))
+    off = np.concatenate([[0], np.cumsum(nb)])
+    return [counts[off[i]:off[i + 1]].copy() for i in range(len(nb))], tails[:len(specs)]
 
 
 def ladders_by(cases, key=None) -> np.ndarray:

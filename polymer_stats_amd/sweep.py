@@ -43,6 +43,7 @@ from . import mcmc_clustering_eap_chain_2d as planar_main
 from . import mcmc_eap_chain as fixed_main
 from ._host import ReferenceError_, arith, error_lines, fresh_seed, number
 from ._host import check_error_bars as _host_check_error_bars
+from ._host import check_hist as _host_check_hist, hist_lines, parse_hist
 
 # (the planar main: 2D/run/Ising_2024-11-06.jl and its siblings launch 2D/mcmc_clustering_eap_chain.jl the same way)
 MAINS = {"mcmc_eap_chain": fixed_main, "mcmc_clustering_eap_chain": cluster_main, "mcmc_clustering_eap_chain_2d": planar_main}
@@ -202,6 +203,16 @@ def check_error_bars(main_name: str, fixed_argv: list[str], nbatches: int, write
     _host_check_error_bars(MAINS[main_name].parse_args(list(fixed_argv)), nbatches, write_csv)
 
 
+def check_hist(main_name: str, fixed_argv: list[str], hist: list[str], write_csv: bool = False, world: int = 1, error_bars: int = 0):
+    """--hist of tools/run_sweep.py: parses the specs and refuses what they cannot be combined with (_host.check_hist, and more
+    than one rank), judged from the options every case shares; no GPU is touched.  Returns [(channel, lo, hi, nbins), ...]."""
+    specs = [parse_hist(t) for t in hist]
+    if world > 1:
+        raise ReferenceError_(f"--hist needs one device, not --gpus {world}")
+    _host_check_hist(MAINS[main_name].parse_args(list(fixed_argv)), specs, write_csv, error_bars=error_bars)
+    return specs
+
+
 def _signature(pargs: dict):
     return tuple(sorted((k, repr(v)) for k, v in pargs.items() if k not in PER_CASE and not k.startswith("_")))
 
@@ -209,20 +220,25 @@ def _signature(pargs: dict):
 def run_sweep(main_name: str, fixed_argv: list[str], cases: list[dict], workdir: str, *, name=None, num_chains: int = 64,
               seed: int | None = None, precision: str | None = None, rng: str | None = None, rank: int = 0, world: int = 1,
               device: int = 0, overwrite: bool = False, write_csv: bool = False, max_chains: int = 262144, log=None,
-              error_bars: int = 0) -> dict:
+              error_bars: int = 0, hist=None) -> dict:
     """Runs the cases whose `.out` does not exist yet (run/interacting_dielectric_study.jl:39) and that fall to this rank
     (position in the full case list modulo `world`).  `write_csv` also writes every case's two time-series files (rows
     recorded on the device for the whole ensemble, _Pool.recorded).  `error_bars` = N: the production run is recorded as N batches
     and every `<case>.out` gets a `<case>.err` beside it (_host.error_lines: blocked standard errors under the .out's names); the
-    .out files are those of a run without it, and a case whose .err is missing is run again.  Returns {"ran": [...], "skipped": [...], "launches": k}."""
+    .out files are those of a run without it, and a case whose .err is missing is run again.  `hist` = ["CHANNEL:LO:HI:NBINS", ...]:
+    every chain is histogrammed every --stepout steps of the production run and every `<case>.out` gets a `<case>.hist` beside it
+    (_host.hist_lines), under the same two rules.  Returns {"ran": [...], "skipped": [...], "launches": k}."""
     main = MAINS[main_name]
     if error_bars:
         check_error_bars(main_name, fixed_argv, error_bars, write_csv=write_csv, world=world)
+    specs = check_hist(main_name, fixed_argv, list(hist), write_csv=write_csv, world=world, error_bars=error_bars) if hist else None
     os.makedirs(workdir, exist_ok=True)
     todo_all = plan(main_name, fixed_argv, cases, workdir, name=name, num_chains=num_chains, seed=seed, precision=precision,
                     rng=rng, device=device)
     # with error bars a case is complete when its .err is there too (a directory first swept without them: run again)
-    done = lambda p: os.path.isfile(p["_out"]) and (not error_bars or os.path.isfile(p["_out"][:-len(".out")] + ".err"))
+    beside = lambda p, ext: p["_out"][:-len(".out")] + ext
+    done = lambda p: (os.path.isfile(p["_out"]) and (not error_bars or os.path.isfile(beside(p, ".err")))
+                      and (not specs or os.path.isfile(beside(p, ".hist"))))
     skipped = [p["_name"] for p in todo_all if done(p) and not overwrite]
     todo = [p for p in todo_all if overwrite or not done(p)]
     mine = [p for p in todo if p["_index"] % world == rank]     # by position in the full list: ranks need not agree on what is done
@@ -237,11 +253,14 @@ def run_sweep(main_name: str, fixed_argv: list[str], cases: list[dict], workdir:
             t0 = time.time()
             info = {}
             # the main's own protocol, every case of the ensemble at once
-            res = main.run_cases(plist, write_csv=write_csv, info=info, **({"error_bars": error_bars} if error_bars else {}))
+            res = main.run_cases(plist, write_csv=write_csv, info=info, **({"error_bars": error_bars} if error_bars else {}),
+                                 **({"hist": specs} if specs else {}))
             for k, (p, (sas, vas, ar)) in enumerate(zip(plist, res)):
                 texts = [(p["_out"], main.summary_lines(sas, vas, ar, p))]      # println x 10 (12)
                 if error_bars:      # (first: a case whose .out is there is complete)
                     texts.insert(0, (p["_out"][:-len(".out")] + ".err", error_lines(main, info["error_bars"], k, p)))
+                if specs:
+                    texts.insert(0, (beside(p, ".hist"), hist_lines(info["hist"], specs, k, int(num_chains))))
                 for path, lines in texts:           # complete or absent: an interrupted sweep re-runs the case
                     tmp = path + f".tmp{os.getpid()}"
                     with open(tmp, "w") as f:

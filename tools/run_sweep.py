@@ -63,6 +63,12 @@ def main():
                          "ROUGHLY DOUBLES the production time: the stage is run recorded for the .err and then again, from a checkpoint, as "
                          "the one launch of a plain run, so that the .out is byte for byte the plain run's (the two runs' means agree to "
                          "~1e-15; a remainder num-steps %% N belongs to no batch).  A case whose .out is there but whose .err is not is run again")
+    ap.add_argument("--hist", action="append", default=[], metavar="CHANNEL:LO:HI:NBINS",
+                    help="repeatable: histogram CHANNEL (r1 r2 r3 p1 p2 p3 U rmag pmag) of EVERY chain every --stepout steps of the "
+                         "production run, on the device, and write next to every <case>.out a <case>.hist: per histogram a header line "
+                         "(channel, lo, hi, nbins, records, chains), bin_lo,bin_hi,count rows and the three tails; tools/free_energy.py "
+                         "turns a force sweep's into A(r).  Refused where --error-bars is, and with it; the .out files stay byte for "
+                         "byte a plain run's, at the same doubled production time")
     ap.add_argument("--max-chains", type=int, default=262144, help="chains per launch (cases per ensemble = this / num-chains)")
     ap.add_argument("--dry-run", action="store_true", help="print the plan (cases, file names, ensembles) and stop: no GPU needed")
     ap.add_argument("--aggregate", default="", help="afterwards write scripts/aggregate_mcmc.jl's CSV of the whole directory here")
@@ -85,6 +91,11 @@ def main():
     if args.error_bars:
         try:
             sw.check_error_bars(args.main, fixed, args.error_bars, write_csv=args.csv, world=args.gpus)
+        except sw.ReferenceError_ as e:
+            raise SystemExit(str(e))
+    if args.hist:
+        try:
+            sw.check_hist(args.main, fixed, args.hist, write_csv=args.csv, world=args.gpus, error_bars=args.error_bars)
         except sw.ReferenceError_ as e:
             raise SystemExit(str(e))
     if args.dry_run:
@@ -144,7 +155,7 @@ def main():
     t0 = time.time()
     res = sw.run_sweep(args.main, fixed, cases, args.workdir, name=args.name or None, num_chains=args.num_chains, seed=args.seed,
                        precision=args.precision, rng=args.rng, rank=rank, world=world, device=local % ndev,
-                       overwrite=args.overwrite, write_csv=args.csv, max_chains=args.max_chains, error_bars=args.error_bars,
+                       overwrite=args.overwrite, write_csv=args.csv, max_chains=args.max_chains, error_bars=args.error_bars, **({"hist": args.hist} if args.hist else {}),
                        log=lambda m: print("# " + m, file=sys.stderr, flush=True))
     print(f"# rank {rank} of {world}: {len(res['ran'])} cases run in {res['launches']} ensembles, {len(res['skipped'])} already "
           f"there; {time.time() - t0:.2f} s", file=sys.stderr, flush=True)
