@@ -291,7 +291,7 @@ int pstat_microstate(pstat_handle *h, int64_t chain, double out[7]);
 
 /* The quantities printed at mcmc_eap_chain.jl:365,386-395.  Synchronises.  Like every accessor that
  * synchronises (pstat_sync, pstat_reduce_host, pstat_rolling, pstat_microstate, pstat_chain_state,
- * pstat_chain_extras, pstat_checkpoint, pstat_series_read, pstat_series_error_bars, pstat_hist_read) it fails with PSTAT_ERR_HIP if a launch since the last successful
+ * pstat_chain_extras, pstat_checkpoint, pstat_corr_read, pstat_corr_rows, pstat_series_read, pstat_series_error_bars, pstat_hist_read) it fails with PSTAT_ERR_HIP if a launch since the last successful
  * call did not run to completion (a job of the persistent kernels timed out waiting for its predecessor):
  * the handle's averages are then not the averages of the steps it was asked for. */
 int pstat_summary_get(pstat_handle *h, int32_t icase, pstat_summary *out);
@@ -473,6 +473,67 @@ void pstat_hist_close(pstat_handle *h, pstat_hist *g);
 int pstat_histogram_device(const double *x /* DEVICE memory, [nrows][stride] */, int64_t nrows, int64_t stride,
                            const pstat_hist_spec *specs, int32_t nspecs, int32_t device, void *stream,
                            int64_t *counts /* host [total_bins] */, int64_t *tails /* host [nspecs][3] */);
+
+/* Chain structure on the device: per-case lag correlations of the monomers' orientations and dipoles.  Everything above reads
+ * the seven numbers r, p, U of a chain; this looks inside it.  The reference can only infer the tangent correlation of its
+ * worm-like-chain check (run/wlc-test_2022-03-14.jl) from <r^2>, and its (E0, kT) phase scans record one-point and nearest-
+ * neighbour order parameters only.  A correlation object belongs to the handle it was opened on; one record is a pair of
+ * launches on the handle's stream that reads the stored angles of EVERY chain where they sit and writes the object's own
+ * buffers only.
+ * The contract (DESIGN.md 3.15 states it in full; polymer_stats_amd/csrc/pstat_corr.hip is the device's statement).  All in f64
+ * from the doubles pstat_chain_state returns for the angles, whatever the handle's precision:
+ *   3D handles      n_i = (cos phi_i sin theta_i, sin phi_i sin theta_i, cos theta_i); the field axis z is component 3.
+ *                   dielectric mu_i = (K1 - K2) E0 cos theta_i n_i + K2 E0 z; polar mu_i = mu n_i; the case's own E0, K1, K2, mu.
+ *   planar handles  n_i = (cos phi_i, sin phi_i); the field axis is component 2.
+ *                   dielectric mu_i = (K1 - K2) E0 sin phi_i n_i + (0, K2 E0); polar mu_i = mu n_i.
+ *   per chain c and lag k = 0 .. max_lag, (1 / (n - k)) sum_{i = 0}^{n - 1 - k} of
+ *                   PSTAT_CORR_NN  n_i . n_{i+k}       (tangent correlation; k = 0 gives 1)
+ *                   PSTAT_CORR_ZZ  n_{i,z} n_{i+k,z}   (along the field; with <r_z> / (n b) it gives the connected correlation)
+ *                   PSTAT_CORR_MM  mu_i . mu_{i+k}     (dipole correlation)
+ *   columns         the channels of the mask in the order NN, ZZ, MM, each max_lag + 1 wide: ncols = (max_lag + 1) * channels.
+ *   totals          per case and column one record adds the sum over the case's chains of the per-chain value to `sum` and the
+ *                   sum of its square to `sumsq`; both are additive across handles.  After ONE record the pooled mean
+ *                   sum / num_chains has the across-chain standard error sqrt((sumsq / N - mean^2) / (N - 1)), N = num_chains,
+ *                   which is rigorous because chains are independent.  Over many records the mean is sum / (records *
+ *                   num_chains) and its error bar comes from the rows through pstat_blocking_device.
+ *   reproducible    no floating-point atomics; the order of every addition depends on (ncases, num_chains, n, max_lag) only:
+ *                   two identical runs give bit-identical totals.
+ *
+ *   pstat_corr_open     max_lag = -1 means n - 1.  capacity_rows = 0 keeps the totals only; > 0 also keeps one row per record.
+ *                       Before the device is touched, with a message naming the argument, PSTAT_ERR_INVALID_ARG: null
+ *                       arguments; channels outside 1 .. 7; max_lag < -1 or > n - 1; capacity_rows < 0.
+ *                       PSTAT_ERR_UNSUPPORTED: an umbrella-sampling handle (its samples carry per-chain weights whose gauge the
+ *                       sums do not hold: the reason error bars, exchange and histograms refuse it); a chain whose unit
+ *                       vectors do not fit the 60 KiB of LDS a workgroup keeps them in: n > 2560 (planar handles: n > 3840).
+ *                       PSTAT_ERR_NOMEM: the device allocation fails.
+ *   pstat_corr_record   one record of the current configuration of every chain; asynchronous on the handle's stream, no host
+ *                       synchronisation: what a caller interleaves with pstat_tempering_exchange or pstat_advance_series.
+ *                       PSTAT_ERR_TOO_SMALL, with nothing enqueued, when capacity_rows > 0 and every row is taken.
+ *   pstat_advance_corr  pstat_advance(h, nsteps) with a record after every `stepout`-th step counted from the start of the call;
+ *                       a remainder nsteps % stepout is advanced and not recorded.  The chains, generators, counters and running
+ *                       sums end up exactly as after pstat_advance.  PSTAT_ERR_TOO_SMALL before anything is enqueued when
+ *                       capacity_rows > 0 and the call's nsteps / stepout rows would not fit; stepout < 1 or nsteps < 0 is
+ *                       PSTAT_ERR_INVALID_ARG.
+ *   pstat_corr_read     sum[ncases][ncols], sumsq[ncases][ncols] (host) and *records; any of them may be NULL.  Synchronises,
+ *                       and fails like every accessor that does after an incomplete launch.
+ *   pstat_corr_rows     *dev_rows = a matrix in DEVICE memory, [*nrows][*stride] with *stride = ncases * ncols: row r holds,
+ *                       for every case and column, record r's sum over the case's chains / num_chains.  It is an input for
+ *                       pstat_blocking_device (on the handle's device and stream).  NULL and 0 rows for an object opened with
+ *                       capacity_rows = 0.  Synchronises like pstat_corr_read.  The pointer is good until the object is closed.
+ *   pstat_corr_clear    zeroes the totals, the record and the row count, on the stream.
+ *   pstat_corr_close    pstat_destroy closes the ones still open.  A correlation object is not part of a checkpoint.
+ *   An object of another handle (or a closed one) is PSTAT_ERR_INVALID_ARG.  Every home, every precision and planar handles
+ *   are accepted. */
+enum { PSTAT_CORR_NN = 1, PSTAT_CORR_ZZ = 2, PSTAT_CORR_MM = 4 };
+typedef struct pstat_corr pstat_corr;
+int pstat_corr_open(pstat_handle *h, int32_t channels, int32_t max_lag, int64_t capacity_rows, pstat_corr **out);
+int pstat_corr_record(pstat_handle *h, pstat_corr *g);
+int pstat_advance_corr(pstat_handle *h, pstat_corr *g, int64_t nsteps, int64_t stepout);
+int pstat_corr_read(pstat_handle *h, pstat_corr *g, double *sum /* [ncases][ncols] */, double *sumsq /* [ncases][ncols] */,
+                    int64_t *records);
+int pstat_corr_rows(pstat_handle *h, pstat_corr *g, const double **dev_rows /* DEVICE memory */, int64_t *nrows, int64_t *stride);
+int pstat_corr_clear(pstat_handle *h, pstat_corr *g);
+void pstat_corr_close(pstat_handle *h, pstat_corr *g);
 
 /* Per-chain accessors for tests and tooling (host buffers).  angles: theta[n] then phi[n] as
  * doubles, radians; sums: the 16 per-chain running sums in rolling.csv order;

@@ -271,6 +271,58 @@ def check_hist(pargs: dict, specs, write_csv: bool = False, devices: int | None 
                               "device's Float64 microstates")
 
 
+CORR_MIN_RECORDS = 32      # the blocking transform's default min_blocks: a .corr's standard errors need that many records
+
+
+def parse_corr(text: str):
+    """--corr MAXLAG[:nn,zz,mm] of tools/run_sweep.py -> (max_lag, channel names in the order of CORR_NAMES)."""
+    head, _, tail = str(text).partition(":")
+    names = [c for c in tail.split(",") if c != ""] if tail else ["nn"]
+    try:
+        max_lag = int(head)
+        if max_lag < 0 or not names or any(c not in _lib.CORR_NAMES for c in names):
+            raise ValueError
+    except ValueError:
+        raise ReferenceError_(f"--corr '{text}' not understood: MAXLAG[:CHANNELS] with MAXLAG >= 0 and CHANNELS a comma-separated "
+                              f"choice of {', '.join(_lib.CORR_NAMES)}")
+    return max_lag, tuple(c for c in _lib.CORR_NAMES if c in names)
+
+
+def check_corr(pargs: dict, spec, write_csv: bool = False, devices: int | None = None, error_bars: int = 0, hist=None):
+    """What --corr (tools/run_sweep.py; run_cases(..., corr=(max_lag, channels))) cannot be combined with, refused before any GPU
+    work: what --hist cannot, for the same reasons (check_hist), --hist itself, a lag beyond n - 1 and a run of fewer records
+    than the blocked standard errors need."""
+    max_lag = spec[0]
+    if devices is None:
+        devices = len([d for d in str(pargs["devices"]).split(",") if d != ""][:max(1, int(pargs["num-chains"]))])
+    if max_lag > int(pargs["num-monomers"]) - 1:
+        raise ReferenceError_(f"--corr: lag {max_lag} is beyond n - 1 = {int(pargs['num-monomers']) - 1}")
+    stepout = int(pargs["stepout"])
+    if not 1 <= stepout <= int(pargs["num-steps"]) or int(pargs["num-steps"]) // stepout < CORR_MIN_RECORDS:
+        raise ReferenceError_(f"--corr takes a record every --stepout steps of the production run and its standard errors from "
+                              f"at least {CORR_MIN_RECORDS} of them: --stepout {stepout} must be in 1 .. --num-steps "
+                              f"{pargs['num-steps']} / {CORR_MIN_RECORDS}")
+    if error_bars:
+        raise ReferenceError_("--corr cannot be combined with --error-bars: each records the production run in its own way")
+    if hist:
+        raise ReferenceError_("--corr cannot be combined with --hist: each records the production run in its own way")
+    if write_csv:
+        raise ReferenceError_("--corr cannot be combined with --csv: the production run is recorded as correlations, not as "
+                              "--stepout rows")
+    if devices > 1:
+        raise ReferenceError_(f"--corr needs one device, not {devices}: the devices hold different chains of a case and "
+                              "their sums are not merged")
+    if int(pargs.get("num-inits", 1)) != 1:
+        raise ReferenceError_(f"--corr cannot be combined with --num-inits {pargs['num-inits']}: a re-initialisation "
+                              "between records is not a stationary series")
+    if pargs["umbrella-sampling"]:
+        raise ReferenceError_("--corr cannot be combined with --umbrella-sampling: the samples carry per-chain weights whose "
+                              "gauge the sums do not hold")
+    if pargs["numeric-type"] != "float64":
+        raise ReferenceError_(f"--corr cannot be combined with --numeric-type {pargs['numeric-type']}: like --hist it is offered "
+                              "for float64 runs only")
+
+
 def burn_ladder(pargs: dict) -> list[float]:
     """--burn-schedule of the two clustering mains: a Julia vector literal of kT multipliers."""
     try:
@@ -500,6 +552,23 @@ class _Pool:
         self.advance(nsteps)
         return res
 
+    def correlations(self, nsteps, stepout, spec):
+        """advance(nsteps) with one record of the lag correlations `spec` = (max_lag, channel names) after every `stepout`-th
+        step, rows kept -> (CorrResult, ErrorBars of the rows).  Made TWICE from the same state like histograms, and for the
+        same reason."""
+        check_corr(self.plist[0], spec, devices=len(self.parts))
+        e = self.parts[0]
+        image = e.checkpoint()
+        g = e.open_corr(spec[1], spec[0], capacity_rows=nsteps // stepout)
+        try:
+            e.advance_corr(g, (nsteps // stepout) * stepout, stepout)      # (the remainder would be lost with the restore anyway)
+            res = g.read(), g.error_bars(min_blocks=CORR_MIN_RECORDS)
+        finally:
+            g.close()
+            e.restore(image)      # also when the recorded run failed: the handle is never left mid-run
+        self.advance(nsteps)
+        return res
+
     def chain0(self, k=0):
         return self.parts[0].chain_state(k * self.counts[0])      # the first chain of case k
 
@@ -592,7 +661,7 @@ class CsvFiles:
 
 
 def recorded_stage(pool, nsteps, write: bool, traj_header, roll_header, rows, angles=False, runs=(None,), report=None,
-                   error_bars: int = 0, hist=None):
+                   error_bars: int = 0, hist=None, corr=None):
     """One recorded run of `nsteps` for every case of the pool, the body of the reference's mcmc(nsteps, pargs[, chain]):
     with `write` the two CSV files of every case (headers `traj_header(pargs)` and `roll_header`, a row per --stepout
     steps: `rows(pargs, step, micro, ang, summary)` -> the case's (trajectory row, rolling row)), then the summaries, the
@@ -600,7 +669,9 @@ def recorded_stage(pool, nsteps, write: bool, traj_header, roll_header, rows, an
     progress line of each run of `nsteps` into the same files (the fixed-force main's inits; it is resumed after the run).
     `error_bars` = N > 0 (without `write`): the run is recorded as N batches instead (_Pool.error_bars) and the pool's `info`
     gets their blocked standard errors under "error_bars".  `hist` = [(channel, lo, hi, nbins), ...] (without `write`): every
-    chain is histogrammed every --stepout steps of the run (_Pool.histograms) and `info` gets the HistResult under "hist"."""
+    chain is histogrammed every --stepout steps of the run (_Pool.histograms) and `info` gets the HistResult under "hist".  `corr` = (max_lag, channels)
+    (without `write`): the lag correlations are recorded every --stepout steps (_Pool.correlations) and `info` gets the
+    (CorrResult, ErrorBars) under "corr"."""
     plist = pool.plist
     pargs = plist[0]
     stepout = int(pargs["stepout"]) if write else 0
@@ -627,6 +698,11 @@ def recorded_stage(pool, nsteps, write: bool, traj_header, roll_header, rows, an
                 res = pool.histograms(nsteps, int(pargs["stepout"]), hist)
                 if pool.info is not None:
                     pool.info["hist"] = res
+                continue
+            if corr:
+                res = pool.correlations(nsteps, int(pargs["stepout"]), corr)
+                if pool.info is not None:
+                    pool.info["corr"] = res
                 continue
             for step, micro, ang, sums in pool.recorded(nsteps, stepout, angles=angles, tick=tick):
                 for k in range(len(files)):
@@ -674,6 +750,17 @@ def hist_lines(res, specs, k: int, chains: int) -> list[str]:
         out.append(f"# channel={channel} lo={lo!r} hi={hi!r} nbins={nbins} records={res.records} chains={chains}")
         out += [f"{float(edges[j])!r},{float(edges[j + 1])!r},{int(c)}" for j, c in enumerate(res.counts[i][k])]
         out += [f"{name},{int(c)}" for name, c in zip(("below", "above", "not_finite"), res.tails[k, i])]
+    return out
+
+
+def corr_lines(res, eb, k: int) -> list[str]:
+    """`<case>.corr`: CSV `k,<ch>,<ch>_stderr,...`, a row per lag: the mean over records and chains and its blocked standard
+    error from the records' rows."""
+    w = res.max_lag + 1
+    out = ["k," + ",".join(f"{ch},{ch}_stderr" for ch in res.channels)]
+    for lag in range(w):
+        out.append(f"{lag}," + ",".join(f"{float(res.mean[ch][k, lag])!r},{float(eb.stderr[k, i * w + lag])!r}"
+                                        for i, ch in enumerate(res.channels)))
     return out
 
 

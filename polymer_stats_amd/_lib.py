@@ -36,6 +36,8 @@ BLOCK_MAX_BATCHES = 40960
 HC_NAMES = ["r1", "r2", "r3", "p1", "p2", "p3", "U", "rmag", "pmag"]
 HIST_MAX_BINS = 8192
 HIST_MAX_SPECS = 16
+# correlation channels (pstat_corr_*): bit i of the PSTAT_CORR_* mask is CORR_NAMES[i]; columns come in this order
+CORR_NAMES = ("nn", "zz", "mm")
 
 # every symbol include/pstat.h declares (tests check the built library exports all of them)
 SYMBOLS = [
@@ -49,6 +51,8 @@ SYMBOLS = [
     "pstat_tempering_open", "pstat_tempering_exchange", "pstat_tempering_stats", "pstat_tempering_close",
     "pstat_hist_open", "pstat_hist_record", "pstat_advance_hist", "pstat_hist_read", "pstat_hist_clear", "pstat_hist_close",
     "pstat_histogram_device",
+    "pstat_corr_open", "pstat_corr_record", "pstat_advance_corr", "pstat_corr_read", "pstat_corr_rows", "pstat_corr_clear",
+    "pstat_corr_close",
 ]
 ABI_VERSION = 6
 
@@ -167,6 +171,15 @@ def load():
     L.pstat_hist_close.argtypes = [vp, vp]
     L.pstat_hist_close.restype = None
     L.pstat_histogram_device.argtypes = [vp, i64, i64, C.POINTER(HistSpec), i32, i32, vp, ip, ip]
+    dp = C.POINTER(C.c_double)
+    L.pstat_corr_open.argtypes = [vp, i32, i32, i64, C.POINTER(vp)]
+    L.pstat_corr_record.argtypes = [vp, vp]
+    L.pstat_advance_corr.argtypes = [vp, vp, i64, i64]
+    L.pstat_corr_read.argtypes = [vp, vp, dp, dp, ip]
+    L.pstat_corr_rows.argtypes = [vp, vp, C.POINTER(vp), ip, ip]
+    L.pstat_corr_clear.argtypes = [vp, vp]
+    L.pstat_corr_close.argtypes = [vp, vp]
+    L.pstat_corr_close.restype = None
     if L.pstat_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI version {L.pstat_abi_version()}, this binding needs {ABI_VERSION}: "
                           "rebuild it with `make -C polymer_stats_amd/csrc`")

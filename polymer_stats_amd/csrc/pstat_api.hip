@@ -113,6 +113,7 @@ struct pstat_handle {
   std::vector<pstat_series *> series;   // series still open (pstat_destroy closes them)
   std::vector<pstat_tempering *> tempering;   // tempering objects still open (likewise)
   std::vector<pstat_hist *> hists;      // histograms still open (likewise)
+  std::vector<pstat_corr *> corrs;      // correlation objects still open (likewise)
 };
 
 // The stepout time series of one handle: rows recorded on the device by launch_record, read back in bulk.
@@ -141,6 +142,16 @@ struct pstat_hist {
   HistSpec *d_specs = nullptr;      // [ncases][nspecs] if per_case, else [nspecs]
   int64_t *d_counts = nullptr;      // [ncases][total_bins], then tails [ncases][nspecs][3]
   size_t slots = 0;                 // int64 words of d_counts
+};
+
+// Per-case lag correlations of one handle (pstat_corr.hip).
+struct pstat_corr {
+  CorrArgs args{};
+  int64_t records = 0;              // records enqueued since open / the last clear (known when a record is enqueued)
+  int64_t capacity = 0, rows = 0;   // rows kept (0: totals only) and taken
+  double *d_totals = nullptr;       // [2][ncases][ncols]: sum, sumsq
+  double *d_partial = nullptr;      // corr_partial_doubles(args): the tiles' partial sums of one record
+  double *d_rows = nullptr;         // [capacity][ncases][ncols]
 };
 
 namespace {
@@ -655,6 +666,19 @@ int hist_specs(const pstat_hist_spec *specs, int32_t nspecs, int64_t rows, int64
   return PSTAT_OK;
 }
 
+pstat_corr *own_corr(pstat_handle *h, pstat_corr *g) {
+  for (pstat_corr *mine : h->corrs)
+    if (mine == g) return g;
+  return nullptr;
+}
+
+void free_corr(pstat_corr *g) {
+  (void)hipFree(g->d_totals);
+  (void)hipFree(g->d_partial);
+  (void)hipFree(g->d_rows);
+  delete g;
+}
+
 HistArgs hist_args(const pstat_handle *h, const pstat_hist *g) {
   return HistArgs{h->base.num_chains, h->ncases, h->S.C, 1, g->nspecs, g->total_bins, g->per_case, 0};
 }
@@ -903,6 +927,7 @@ void pstat_destroy(pstat_handle *h) {
   for (pstat_series *s : h->series) free_series(s);
   for (pstat_tempering *t : h->tempering) free_tempering(t);
   for (pstat_hist *g : h->hists) free_hist(g);
+  for (pstat_corr *g : h->corrs) free_corr(g);
   if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }
@@ -1320,6 +1345,138 @@ int pstat_histogram_device(const double *x, int64_t nrows, int64_t stride, const
   if (counts) std::memcpy(counts, host.data(), (size_t)total_bins * sizeof(int64_t));
   if (tails) std::memcpy(tails, host.data() + total_bins, 3 * (size_t)nspecs * sizeof(int64_t));
   return PSTAT_OK;
+}
+
+int pstat_corr_open(pstat_handle *h, int32_t channels, int32_t max_lag, int64_t capacity_rows, pstat_corr **out) {
+  if (!h || !out) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
+  *out = nullptr;
+  const int64_t n = h->base.n;
+  if (channels < 1 || channels > (PSTAT_CORR_NN | PSTAT_CORR_ZZ | PSTAT_CORR_MM))
+    return fail(PSTAT_ERR_INVALID_ARG, "channels must be a mask of PSTAT_CORR_NN | _ZZ | _MM in 1 .. 7, not %d", channels);
+  if (max_lag < -1 || max_lag > n - 1)
+    return fail(PSTAT_ERR_INVALID_ARG, "max_lag must be in 0 .. n - 1 = %lld (or -1 for n - 1), not %d", (long long)n - 1, max_lag);
+  if (capacity_rows < 0) return fail(PSTAT_ERR_INVALID_ARG, "capacity_rows must be >= 0, not %lld", (long long)capacity_rows);
+  if (h->cfg.umbrella)
+    return fail(PSTAT_ERR_UNSUPPORTED, "correlations under --umbrella-sampling: the samples carry per-chain weights whose gauge "
+                "the sums do not hold");
+  if (n > corr_max_n(h->cfg.planar))
+    return fail(PSTAT_ERR_UNSUPPORTED, "n = %lld: a chain's unit vectors must fit the LDS of a workgroup, n <= %lld for a %s handle",
+                (long long)n, (long long)corr_max_n(h->cfg.planar), h->cfg.planar ? "planar" : "3D");
+  if (max_lag < 0) max_lag = (int32_t)(n - 1);
+  const int nch = (channels & 1) + ((channels >> 1) & 1) + ((channels >> 2) & 1);
+  const size_t stride = (size_t)h->ncases * (size_t)nch * (size_t)(max_lag + 1);
+  if (capacity_rows > 0 && (uint64_t)capacity_rows > (SIZE_MAX / sizeof(double)) / stride)
+    return fail(PSTAT_ERR_NOMEM, "%lld rows of correlations do not fit the address space", (long long)capacity_rows);
+  PSTAT_TRY(set_device(h));
+  pstat_corr *g = new (std::nothrow) pstat_corr;
+  if (!g) return fail(PSTAT_ERR_NOMEM, "host allocation failed");
+  CorrArgs &a = g->args;
+  a.per = h->base.num_chains; a.ncases = h->ncases; a.n = n;
+  a.channels = channels; a.max_lag = max_lag; a.ncols = nch * (max_lag + 1);
+  a.elem = (int32_t)h->elem; a.planar = h->cfg.planar ? 1 : 0; a.polar = h->cfg.chain_type == PSTAT_POLAR ? 1 : 0;
+  corr_shape(a);
+  g->capacity = capacity_rows;
+  hipError_t e = hipMalloc((void **)&g->d_totals, 2 * stride * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc((void **)&g->d_partial, corr_partial_doubles(a) * sizeof(double));
+  if (e == hipSuccess && capacity_rows > 0) e = hipMalloc((void **)&g->d_rows, (size_t)capacity_rows * stride * sizeof(double));
+  if (e != hipSuccess) {
+    free_corr(g);
+    return fail(PSTAT_ERR_NOMEM, "correlations of %zu columns, %lld rows: %s", stride, (long long)capacity_rows, hipGetErrorString(e));
+  }
+  e = hipMemsetAsync(g->d_totals, 0, 2 * stride * sizeof(double), h->stream);   // ahead of the first record
+  if (e != hipSuccess) {
+    free_corr(g);
+    return fail(PSTAT_ERR_HIP, "correlation totals: %s", hipGetErrorString(e));
+  }
+  try {
+    h->corrs.push_back(g);
+  } catch (const std::bad_alloc &) {
+    free_corr(g);
+    return fail(PSTAT_ERR_NOMEM, "host allocation failed");
+  }
+  *out = g;
+  return PSTAT_OK;
+}
+
+// one record, enqueued; the caller has checked that a row is free
+static int enqueue_corr(pstat_handle *h, pstat_corr *g) {
+  const size_t stride = (size_t)h->ncases * (size_t)g->args.ncols;
+  HIP_TRY(launch_corr(g->args, h->S.ang, h->d_cases, g->d_partial, g->d_totals,
+                      g->capacity > 0 ? g->d_rows + (size_t)g->rows * stride : nullptr, h->stream));
+  g->records += 1;
+  if (g->capacity > 0) g->rows += 1;
+  return PSTAT_OK;
+}
+
+int pstat_corr_record(pstat_handle *h, pstat_corr *g) {
+  if (!h || !g) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
+  if (!own_corr(h, g)) return fail(PSTAT_ERR_INVALID_ARG, "the correlation object is not an open one of this handle");
+  if (g->capacity > 0 && g->rows >= g->capacity)
+    return fail(PSTAT_ERR_TOO_SMALL, "the correlation object has 0 of %lld rows free", (long long)g->capacity);
+  PSTAT_TRY(set_device(h));
+  if (h->failed_job) return report_failed_job(h);
+  return enqueue_corr(h, g);
+}
+
+int pstat_advance_corr(pstat_handle *h, pstat_corr *g, int64_t nsteps, int64_t stepout) {
+  if (!h || !g) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
+  if (!own_corr(h, g)) return fail(PSTAT_ERR_INVALID_ARG, "the correlation object is not an open one of this handle");
+  if (nsteps < 0) return fail(PSTAT_ERR_INVALID_ARG, "nsteps must be >= 0");
+  if (stepout < 1) return fail(PSTAT_ERR_INVALID_ARG, "stepout must be >= 1");
+  const int64_t nrec = nsteps / stepout;
+  if (g->capacity > 0 && nrec > g->capacity - g->rows)
+    return fail(PSTAT_ERR_TOO_SMALL, "the correlation object has %lld of %lld rows free, this call would record %lld",
+                (long long)(g->capacity - g->rows), (long long)g->capacity, (long long)nrec);
+  PSTAT_TRY(set_device(h));
+  if (h->failed_job) return report_failed_job(h);
+  for (int64_t i = 0; i < nrec; ++i) {
+    PSTAT_TRY(enqueue_steps(h, stepout));
+    PSTAT_TRY(enqueue_corr(h, g));
+  }
+  return enqueue_steps(h, nsteps - nrec * stepout);
+}
+
+int pstat_corr_read(pstat_handle *h, pstat_corr *g, double *sum, double *sumsq, int64_t *records) {
+  if (!h || !g) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
+  if (!own_corr(h, g)) return fail(PSTAT_ERR_INVALID_ARG, "the correlation object is not an open one of this handle");
+  PSTAT_TRY(set_device(h));
+  PSTAT_TRY(sync_checked(h));
+  const size_t stride = (size_t)h->ncases * (size_t)g->args.ncols;
+  if (sum) HIP_TRY(hipMemcpy(sum, g->d_totals, stride * sizeof(double), hipMemcpyDeviceToHost));
+  if (sumsq) HIP_TRY(hipMemcpy(sumsq, g->d_totals + stride, stride * sizeof(double), hipMemcpyDeviceToHost));
+  if (records) *records = g->records;
+  return PSTAT_OK;
+}
+
+int pstat_corr_rows(pstat_handle *h, pstat_corr *g, const double **dev_rows, int64_t *nrows, int64_t *stride) {
+  if (!h || !g || !dev_rows || !nrows || !stride) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
+  if (!own_corr(h, g)) return fail(PSTAT_ERR_INVALID_ARG, "the correlation object is not an open one of this handle");
+  PSTAT_TRY(set_device(h));
+  PSTAT_TRY(sync_checked(h));
+  *dev_rows = g->d_rows;
+  *nrows = g->rows;
+  *stride = (int64_t)h->ncases * g->args.ncols;
+  return PSTAT_OK;
+}
+
+int pstat_corr_clear(pstat_handle *h, pstat_corr *g) {
+  if (!h || !g) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
+  if (!own_corr(h, g)) return fail(PSTAT_ERR_INVALID_ARG, "the correlation object is not an open one of this handle");
+  PSTAT_TRY(set_device(h));
+  const size_t stride = (size_t)h->ncases * (size_t)g->args.ncols;
+  HIP_TRY(hipMemsetAsync(g->d_totals, 0, 2 * stride * sizeof(double), h->stream));   // behind the records already enqueued
+  g->records = 0;
+  g->rows = 0;
+  return PSTAT_OK;
+}
+
+void pstat_corr_close(pstat_handle *h, pstat_corr *g) {
+  if (!h || !g || !own_corr(h, g)) return;
+  (void)hipSetDevice(h->device);
+  (void)hipStreamSynchronize(h->stream);   // a record may still be in flight
+  for (size_t i = 0; i < h->corrs.size(); ++i)
+    if (h->corrs[i] == g) { h->corrs.erase(h->corrs.begin() + (long)i); break; }
+  free_corr(g);
 }
 
 int pstat_sync(pstat_handle *h) {

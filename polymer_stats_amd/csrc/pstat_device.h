@@ -399,4 +399,25 @@ struct HistArgs {
 hipError_t launch_hist(const HistArgs &a, const double *src, const HistSpec *specs, int64_t *counts, int64_t *tails,
                        hipStream_t stream);
 
+// Per-case lag correlations of the chains' current orientations and dipoles (pstat_corr.hip states the contract).
+struct CorrArgs {
+  int64_t per, ncases, n;      // chains per case, cases, monomers
+  int64_t tiles;               // workgroups per case: ceil(per / tile_chains)
+  int32_t channels;            // PSTAT_CORR_* mask
+  int32_t max_lag;
+  int32_t ncols;               // (max_lag + 1) * channels set
+  int32_t elem;                // bytes per stored angle of DevState::ang
+  int32_t planar, polar;
+  int32_t tile_chains;         // chains per workgroup
+  int32_t lpc, groups, nslots; // threads per group, groups per workgroup (lpc * groups = 256), lags per thread
+};
+// fills tiles, tile_chains, lpc, groups, nslots from the other fields: the shape of the reduction, which is part of the result
+void corr_shape(CorrArgs &a);
+// the longest chain whose unit vectors fit a workgroup's LDS
+int64_t corr_max_n(int planar);
+size_t corr_partial_doubles(const CorrArgs &a);
+// one record: totals[2][ncases][ncols] (sum, then sumsq) += this record's, row[ncases][ncols] (unless null) = the cases' means
+hipError_t launch_corr(const CorrArgs &a, const void *ang, const CaseConst *cases, double *partial, double *totals, double *row,
+                       hipStream_t stream);
+
 }  // namespace pstat

@@ -131,6 +131,25 @@ class Ensemble:
         """advance(nsteps) with a record into `hist` after every `stepout`-th step (asynchronous)."""
         check(self._L.pstat_advance_hist(self._h, hist._g, int(nsteps), int(stepout)))
 
+    # --- per-case lag correlations of the monomers' orientations and dipoles (pstat_corr_*; DESIGN.md 3.15)
+    def open_corr(self, channels=("nn",), max_lag: int | None = None, capacity_rows: int = 0) -> "Corr":
+        """`channels`: names of CORR_NAMES ("nn" tangent, "zz" along the field, "mm" dipole); `max_lag`: lags 0 .. max_lag
+        (default n - 1); `capacity_rows` > 0 also keeps one row of case means per record, for Corr.error_bars."""
+        if isinstance(channels, str):
+            channels = (channels,)
+        unknown = [c for c in channels if c not in _lib.CORR_NAMES]
+        if unknown:
+            raise ValueError(f"unknown correlation channel {unknown[0]!r}: one of {', '.join(_lib.CORR_NAMES)}")
+        names = tuple(c for c in _lib.CORR_NAMES if c in channels)
+        mask = sum(1 << _lib.CORR_NAMES.index(c) for c in names)
+        g = C.c_void_p()
+        check(self._L.pstat_corr_open(self._h, mask, -1 if max_lag is None else int(max_lag), int(capacity_rows), C.byref(g)))
+        return Corr(self, g, names, self.n - 1 if max_lag is None else int(max_lag))
+
+    def advance_corr(self, corr: "Corr", nsteps: int, stepout: int):
+        """advance(nsteps) with a record into `corr` after every `stepout`-th step (asynchronous)."""
+        check(self._L.pstat_advance_corr(self._h, corr._g, int(nsteps), int(stepout)))
+
     # --- read-outs
     def reduce_into(self, dev_ptr: int, icase: int = -1):
         """Device-side reduction into a caller-owned device buffer of NRED doubles (async)."""
@@ -332,6 +351,75 @@ class Hist:
     def close(self):
         if self._g and self._e._h:      # (closing the ensemble closes its histograms)
             self._e._L.pstat_hist_close(self._e._h, self._g)
+        self._g = None
+
+
+class CorrResult:
+    """What Corr.read returns.  `sum`, `sumsq`: the raw totals, float64 [ncases, ncols] with the channels' columns side by side
+    in the order of `channels`, each max_lag + 1 wide; `records`; `mean[channel]`: sum / (records * chains per case), shape
+    [ncases, max_lag + 1]; `chain_stderr[channel]`: the across-chain standard error of that mean, defined after exactly one
+    record (chains are independent, records of one chain are not) and NaN otherwise."""
+
+    def __init__(self, channels, max_lag: int, num_chains: int, sum_: np.ndarray, sumsq: np.ndarray, records: int):
+        self.channels, self.max_lag, self.records, self.sum, self.sumsq = channels, max_lag, records, sum_, sumsq
+        w, N = max_lag + 1, num_chains
+        self.mean, self.chain_stderr = {}, {}
+        for i, ch in enumerate(channels):
+            s, q = sum_[:, i * w:(i + 1) * w], sumsq[:, i * w:(i + 1) * w]
+            with np.errstate(invalid="ignore", divide="ignore"):
+                self.mean[ch] = s / (records * N) if records > 0 else np.full(s.shape, np.nan)
+                if records == 1 and N > 1:
+                    self.chain_stderr[ch] = np.sqrt(np.maximum(q / N - (s / N) ** 2, 0.0) / (N - 1))
+                else:
+                    self.chain_stderr[ch] = np.full(s.shape, np.nan)
+
+
+class Corr:
+    """Lag correlations recorded on the device (Ensemble.open_corr, pstat_corr_*)."""
+
+    def __init__(self, ensemble: Ensemble, g, channels, max_lag: int):
+        self._e, self._g, self.channels, self.max_lag = ensemble, g, channels, max_lag
+        self.ncols = len(channels) * (max_lag + 1)
+
+    def record(self):
+        """One record of the current configuration of every chain (asynchronous)."""
+        check(self._e._L.pstat_corr_record(self._e._h, self._g))
+
+    def read(self) -> CorrResult:
+        """Synchronises."""
+        e = self._e
+        s = np.zeros((e.ncases, self.ncols))
+        q = np.zeros((e.ncases, self.ncols))
+        records = C.c_int64(0)
+        dp = C.POINTER(C.c_double)
+        check(e._L.pstat_corr_read(e._h, self._g, s.ctypes.data_as(dp), q.ctypes.data_as(dp), C.byref(records)))
+        return CorrResult(self.channels, self.max_lag, e.num_chains, s, q, int(records.value))
+
+    def rows(self):
+        """(device pointer, rows, stride) of the per-record case means, a float64 matrix [rows][ncases * ncols] in device
+        memory (pstat_corr_rows).  Synchronises."""
+        e = self._e
+        ptr, nrows, stride = C.c_void_p(), C.c_int64(0), C.c_int64(0)
+        check(e._L.pstat_corr_rows(e._h, self._g, C.byref(ptr), C.byref(nrows), C.byref(stride)))
+        return ptr.value or 0, int(nrows.value), int(stride.value)
+
+    def error_bars(self, min_blocks: int = 32, levels: bool = False, device: int | None = None) -> "ErrorBars":
+        """Blocked standard errors of the recorded rows' columns (pstat_blocking_device on pstat_corr_rows): arrays of shape
+        [ncases, ncols].  Needs capacity_rows > 0 at open_corr and at least `min_blocks` records.  Synchronises."""
+        e = self._e
+        ptr, nrows, stride = self.rows()
+        dev = int(e.cases[0].device) if device is None else int(device)
+        eb = blocking_device(ptr, nrows, stride, stride, min_blocks=min_blocks, levels=levels, device=dev)
+        out = np.stack([eb.mean, eb.stderr, eb.stderr_err, eb.inefficiency, eb.level.astype(float), eb.converged.astype(float)], axis=-1)
+        lev = eb.levels.reshape(e.ncases, self.ncols, -1) if levels else None
+        return ErrorBars(out.reshape(e.ncases, self.ncols, -1), nrows, lev)
+
+    def clear(self):
+        check(self._e._L.pstat_corr_clear(self._e._h, self._g))
+
+    def close(self):
+        if self._g and self._e._h:      # (closing the ensemble closes its correlation objects)
+            self._e._L.pstat_corr_close(self._e._h, self._g)
         self._g = None
 
 

@@ -44,6 +44,7 @@ from . import mcmc_eap_chain as fixed_main
 from ._host import ReferenceError_, arith, error_lines, fresh_seed, number
 from ._host import check_error_bars as _host_check_error_bars
 from ._host import check_hist as _host_check_hist, hist_lines, parse_hist
+from ._host import check_corr as _host_check_corr, corr_lines, parse_corr
 
 # (the planar main: 2D/run/Ising_2024-11-06.jl and its siblings launch 2D/mcmc_clustering_eap_chain.jl the same way)
 MAINS = {"mcmc_eap_chain": fixed_main, "mcmc_clustering_eap_chain": cluster_main, "mcmc_clustering_eap_chain_2d": planar_main}
@@ -213,6 +214,23 @@ def check_hist(main_name: str, fixed_argv: list[str], hist: list[str], write_csv
     return specs
 
 
+def check_corr(main_name: str, fixed_argv: list[str], corr: str, cases: list[dict], write_csv: bool = False, world: int = 1,
+               error_bars: int = 0, hist=None):
+    """--corr of tools/run_sweep.py: parses it and refuses what it cannot be combined with (_host.check_corr, and more than one
+    rank), judged from the options every case shares and from every chain length among the cases; no GPU is touched.  Returns
+    (max_lag, channels)."""
+    spec = parse_corr(corr)
+    if world > 1:
+        raise ReferenceError_(f"--corr needs one device, not --gpus {world}")
+    main = MAINS[main_name]
+    lengths = {}
+    for case in cases or [{}]:
+        lengths.setdefault(repr(case.get("n", case.get("num-monomers"))), case)
+    for case in lengths.values():
+        _host_check_corr(main.parse_args(list(fixed_argv) + case_argv(case)), spec, write_csv, error_bars=error_bars, hist=hist)
+    return spec
+
+
 def _signature(pargs: dict):
     return tuple(sorted((k, repr(v)) for k, v in pargs.items() if k not in PER_CASE and not k.startswith("_")))
 
@@ -220,25 +238,27 @@ def _signature(pargs: dict):
 def run_sweep(main_name: str, fixed_argv: list[str], cases: list[dict], workdir: str, *, name=None, num_chains: int = 64,
               seed: int | None = None, precision: str | None = None, rng: str | None = None, rank: int = 0, world: int = 1,
               device: int = 0, overwrite: bool = False, write_csv: bool = False, max_chains: int = 262144, log=None,
-              error_bars: int = 0, hist=None) -> dict:
+              error_bars: int = 0, hist=None, corr=None) -> dict:
     """Runs the cases whose `.out` does not exist yet (run/interacting_dielectric_study.jl:39) and that fall to this rank
     (position in the full case list modulo `world`).  `write_csv` also writes every case's two time-series files (rows
     recorded on the device for the whole ensemble, _Pool.recorded).  `error_bars` = N: the production run is recorded as N batches
     and every `<case>.out` gets a `<case>.err` beside it (_host.error_lines: blocked standard errors under the .out's names); the
     .out files are those of a run without it, and a case whose .err is missing is run again.  `hist` = ["CHANNEL:LO:HI:NBINS", ...]:
     every chain is histogrammed every --stepout steps of the production run and every `<case>.out` gets a `<case>.hist` beside it
-    (_host.hist_lines), under the same two rules.  Returns {"ran": [...], "skipped": [...], "launches": k}."""
+    (_host.hist_lines), under the same two rules.  `corr` = "MAXLAG[:nn,zz,mm]": the lag correlations are recorded every --stepout
+    steps of the production run and every `<case>.out` gets a `<case>.corr` beside it (_host.corr_lines), likewise.  Returns {"ran": [...], "skipped": [...], "launches": k}."""
     main = MAINS[main_name]
     if error_bars:
         check_error_bars(main_name, fixed_argv, error_bars, write_csv=write_csv, world=world)
     specs = check_hist(main_name, fixed_argv, list(hist), write_csv=write_csv, world=world, error_bars=error_bars) if hist else None
+    cspec = check_corr(main_name, fixed_argv, corr, cases, write_csv=write_csv, world=world, error_bars=error_bars, hist=hist) if corr else None
     os.makedirs(workdir, exist_ok=True)
     todo_all = plan(main_name, fixed_argv, cases, workdir, name=name, num_chains=num_chains, seed=seed, precision=precision,
                     rng=rng, device=device)
     # with error bars a case is complete when its .err is there too (a directory first swept without them: run again)
     beside = lambda p, ext: p["_out"][:-len(".out")] + ext
     done = lambda p: (os.path.isfile(p["_out"]) and (not error_bars or os.path.isfile(beside(p, ".err")))
-                      and (not specs or os.path.isfile(beside(p, ".hist"))))
+                      and (not specs or os.path.isfile(beside(p, ".hist"))) and (not cspec or os.path.isfile(beside(p, ".corr"))))
     skipped = [p["_name"] for p in todo_all if done(p) and not overwrite]
     todo = [p for p in todo_all if overwrite or not done(p)]
     mine = [p for p in todo if p["_index"] % world == rank]     # by position in the full list: ranks need not agree on what is done
@@ -254,13 +274,15 @@ def run_sweep(main_name: str, fixed_argv: list[str], cases: list[dict], workdir:
             info = {}
             # the main's own protocol, every case of the ensemble at once
             res = main.run_cases(plist, write_csv=write_csv, info=info, **({"error_bars": error_bars} if error_bars else {}),
-                                 **({"hist": specs} if specs else {}))
+                                 **({"hist": specs} if specs else {}), **({"corr": cspec} if cspec else {}))
             for k, (p, (sas, vas, ar)) in enumerate(zip(plist, res)):
                 texts = [(p["_out"], main.summary_lines(sas, vas, ar, p))]      # println x 10 (12)
                 if error_bars:      # (first: a case whose .out is there is complete)
                     texts.insert(0, (p["_out"][:-len(".out")] + ".err", error_lines(main, info["error_bars"], k, p)))
                 if specs:
                     texts.insert(0, (beside(p, ".hist"), hist_lines(info["hist"], specs, k, int(num_chains))))
+                if cspec:
+                    texts.insert(0, (beside(p, ".corr"), corr_lines(*info["corr"], k)))
                 for path, lines in texts:           # complete or absent: an interrupted sweep re-runs the case
                     tmp = path + f".tmp{os.getpid()}"
                     with open(tmp, "w") as f:
