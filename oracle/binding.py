@@ -55,6 +55,14 @@ class EapTrace(C.Structure):
                 ("max_rows", C.c_int64), ("rows_written", C.c_int64)]
 
 
+class EapStepOut(C.Structure):
+    _fields_ = [("rng", C.c_uint32 * 4), ("idx", C.c_int64), ("lower", C.c_int64), ("upper", C.c_int64),
+                ("flipped", C.c_int32), ("flip_bit", C.c_int32), ("accept", C.c_int32), ("pad_", C.c_int32),
+                ("ngrow", C.c_int64), ("phi_trial", C.c_double), ("theta_trial", C.c_double),
+                ("d", C.c_double), ("eps", C.c_double), ("mag", C.c_double), ("log_alpha", C.c_double),
+                ("U_cur", C.c_double), ("U_trial", C.c_double)]
+
+
 def build(force: bool = False) -> str:
     src = os.path.join(HERE, "eap_oracle.c")
     if force or not os.path.exists(LIB_PATH) or \
@@ -97,6 +105,15 @@ def lib():
         L.eap_pair_energy.restype = C.c_double
         L.eap_chain_energy.argtypes = [C.POINTER(EapParams)] + [C.POINTER(C.c_double)] * 4
         L.eap_chain_energy.restype = C.c_double
+        dp, up = C.POINTER(C.c_double), C.POINTER(C.c_uint32)
+        L.eap_step_judge.argtypes = [C.POINTER(EapParams), dp, dp, up, C.c_double, C.c_double, dp, C.POINTER(EapStepOut), dp, dp]
+        L.eap_step_judge.restype = C.c_int
+        L.eap_step_judge_cluster.argtypes = L.eap_step_judge.argtypes + [dp, C.c_int64]
+        L.eap_step_judge_cluster.restype = C.c_int
+        L.eap_seed_state.argtypes = [C.POINTER(EapParams), C.c_uint64, up, dp, dp]
+        L.eap_seed_state.restype = None
+        L.eap_adapt.argtypes = [C.POINTER(EapParams), C.c_int64, dp, dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.eap_adapt.restype = None
         _lib = L
     return _lib
 
@@ -264,3 +281,75 @@ def chain_energy(params: EapParams, phi: np.ndarray, theta: np.ndarray):
     U = lib().eap_chain_energy(C.byref(params), phi.ctypes.data_as(dp), theta.ctypes.data_as(dp),
                                r.ctypes.data_as(dp), p.ctypes.data_as(dp))
     return U, r, p
+
+
+@dataclass
+class Step:
+    """One judged step (eap_step_out): see oracle/eap_oracle.h for the meaning of every field."""
+    rng: np.ndarray            # generator words after the step
+    idx: int
+    lower: int
+    upper: int
+    flipped: bool
+    flip_bit: bool
+    accept: bool
+    phi_trial: float
+    theta_trial: float
+    d: float
+    eps: float
+    mag: float
+    log_alpha: float
+    U_cur: float
+    U_trial: float
+    trial_phi: np.ndarray      # [n] every angle of the trial chain
+    trial_theta: np.ndarray
+    grow: np.ndarray           # [ngrow, 3]: draw, link probability, draw - probability
+
+
+def step_judge(params: EapParams, phi, theta, rng, phi_step: float, theta_step: float, cluster: bool = False,
+               moved_to=None) -> Step:
+    """One step of the fixed-force main (or of the clustering main) from an explicit state, judged in f64.
+    moved_to = (phi', theta'): where the single move puts its monomer, in place of the step's own displacement."""
+    L = lib()
+    n = params.n
+    phi = np.ascontiguousarray(phi, dtype=np.float64)
+    theta = np.ascontiguousarray(theta, dtype=np.float64)
+    assert phi.shape == (n,) and theta.shape == (n,)
+    words = (C.c_uint32 * 4)(*[int(w) for w in rng])
+    out = EapStepOut()
+    tphi, tth = np.empty(n), np.empty(n)
+    dp = C.POINTER(C.c_double)
+    to = None if moved_to is None else (C.c_double * 2)(float(moved_to[0]), float(moved_to[1]))
+    args = [C.byref(params), phi.ctypes.data_as(dp), theta.ctypes.data_as(dp), words, float(phi_step), float(theta_step),
+            to, C.byref(out), tphi.ctypes.data_as(dp), tth.ctypes.data_as(dp)]
+    if cluster:
+        grow = np.zeros((n + 2, 3))
+        rc = L.eap_step_judge_cluster(*args, grow.ctypes.data_as(dp), grow.shape[0])
+    else:
+        grow = np.zeros((0, 3))
+        rc = L.eap_step_judge(*args)
+    if rc != 0:
+        raise RuntimeError(f"oracle returned {rc}")
+    return Step(rng=np.array(out.rng[:], dtype=np.uint32), idx=out.idx, lower=out.lower, upper=out.upper,
+                flipped=bool(out.flipped), flip_bit=bool(out.flip_bit), accept=bool(out.accept),
+                phi_trial=out.phi_trial, theta_trial=out.theta_trial, d=out.d, eps=out.eps, mag=out.mag,
+                log_alpha=out.log_alpha, U_cur=out.U_cur, U_trial=out.U_trial, trial_phi=tphi, trial_theta=tth,
+                grow=grow[:out.ngrow])
+
+
+def seed_state(params: EapParams, chain_id: int = 0):
+    """(phi[n], theta[n], rng[4]) of the seeded start of a chain: what every run of the oracle begins from."""
+    n = params.n
+    phi, th = np.empty(n), np.empty(n)
+    words = (C.c_uint32 * 4)()
+    dp = C.POINTER(C.c_double)
+    lib().eap_seed_state(C.byref(params), chain_id, words, phi.ctypes.data_as(dp), th.ctypes.data_as(dp))
+    return phi, th, np.array(words[:], dtype=np.uint32)
+
+
+def adapt(params: EapParams, step: int, phi_step: float, theta_step: float, nacc: int, natt: int):
+    """The step-size adaptation after in-run step `step` (1-based): returns (phi_step, theta_step, nacc, natt)."""
+    a, b = C.c_double(phi_step), C.c_double(theta_step)
+    k, m = C.c_int64(nacc), C.c_int64(natt)
+    lib().eap_adapt(C.byref(params), step, C.byref(a), C.byref(b), C.byref(k), C.byref(m))
+    return a.value, b.value, k.value, m.value

@@ -436,6 +436,51 @@ static int check_params(const eap_params *P) {
   return 0;
 }
 
+/* ------------------------------------------------------------------ one step's proposal
+ * The body of one step up to the Metropolis decision, stated once: the run loops below and the one-step judge
+ * (eap_step_judge, eap_step_judge_cluster) call these same functions. */
+
+typedef struct proposal_t {
+  uint32_t w_idx, w_phi, w_th, w_eps;
+  int64_t idx;
+  int flip_bit;           /* --do-flips: the bit drawn (0 if the option is off) */
+  double phi1, th1;       /* the moved monomer's angles after move!, before any reflection */
+  double eps;
+  /* clustering main */
+  int64_t lower, upper;   /* the cluster, [idx, idx] if none was grown */
+  int flipped;            /* a cluster was reflected */
+  double alpha;
+} proposal_t;
+
+/* growth tests of one cluster_flip!: (draw, link probability, draw - probability) per test, in stream order */
+typedef struct growlog_t { double *rows; int64_t max, count; } growlog_t;
+
+/* acceptance.jl:29-39 on a difference of log-densities */
+static int metropolis_ok(double delta, double eps) { return (delta >= 0.0) || (eps < exp(delta)); }
+
+/* mcmc_eap_chain.jl:277-287: the draws, the trial chain, eps */
+static void propose_single(const eap_params *P, uint32_t rng[5], const chain_t *cur, chain_t *trial,
+                           double phistep, double thstep, proposal_t *pr, const double *moved_to) {
+  pr->w_idx = draw_w(rng); pr->w_phi = draw_w(rng);
+  pr->idx = idx_of(pr->w_idx, P->n);                            /* :277 */
+  double dphi = phistep * sym_of(pr->w_phi);                    /* :278 */
+  double flip = 0.0;
+  pr->flip_bit = 0;
+  if (P->do_flips && (draw_w(rng) >> 31)) {                     /* :279 */
+    flip = M_PI - 2 * cur->th[pr->idx];
+    pr->flip_bit = 1;
+  }
+  pr->w_th = draw_w(rng);
+  double dth = flip + thstep * sym_of(pr->w_th);                /* :280 */
+  if (moved_to) { dphi = moved_to[0] - cur->phi[pr->idx]; dth = moved_to[1] - cur->th[pr->idx]; }   /* judge only */
+  chain_copy(trial, cur);                                       /* :281 */
+  chain_move(P, trial, pr->idx, dphi, dth);                     /* :283 */
+  pr->phi1 = trial->phi[pr->idx]; pr->th1 = trial->th[pr->idx];
+  pr->w_eps = draw_w(rng);
+  pr->eps = eap_eps(P->uniform_bits, pr->w_eps, pr->w_idx, pr->w_phi, pr->w_th);   /* :287 */
+  pr->lower = pr->upper = pr->idx; pr->flipped = 0; pr->alpha = 1.0;
+}
+
 /* ------------------------------------------------------------------ faithful run */
 
 int eap_run_faithful(const eap_params *P, uint64_t chain_id, eap_result *out, eap_trace *tr) {
@@ -459,20 +504,11 @@ int eap_run_faithful(const eap_params *P, uint64_t chain_id, eap_result *out, ea
 
   for (int64_t init = 1; init <= P->num_inits; ++init) {        /* :266 */
     for (int64_t step = 1; step <= P->num_steps; ++step, ++t) { /* :276 */
-      const uint32_t w_idx = draw_w(rng), w_phi = draw_w(rng);
-      int64_t idx = idx_of(w_idx, P->n);                        /* :277 */
-      double dphi = phistep * sym_of(w_phi);                    /* :278 */
-      double flip = 0.0;
-      if (P->do_flips && (draw_w(rng) >> 31))                   /* :279 */
-        flip = M_PI - 2 * cur.th[idx];
-      const uint32_t w_th = draw_w(rng);
-      double dth = flip + thstep * sym_of(w_th);                /* :280 */
-      chain_copy(&trial, &cur);                                 /* :281 */
-      chain_move(P, &trial, idx, dphi, dth);                    /* :283 */
-      double eps = eap_eps(P->uniform_bits, draw_w(rng), w_idx, w_phi, w_th);   /* :287 */
+      proposal_t pr;
+      propose_single(P, rng, &cur, &trial, phistep, thstep, &pr, NULL);   /* :277-287 */
       /* Metropolis functor, acceptance.jl:29-39 */
       double logpi = -trial.U / P->kT + trial.Omega + (wf.on ? weight_eval(&wf, sum_us(&trial)) : 1.0);
-      int ok = (logpi >= logpi_prev) || (eps < exp(logpi - logpi_prev));
+      int ok = metropolis_ok(logpi - logpi_prev, pr.eps);
       if (!isfinite(trial.U)) ++nan_rejects;
       if (ok) {
         logpi_prev = logpi;
@@ -522,8 +558,17 @@ int eap_run_faithful(const eap_params *P, uint64_t chain_id, eap_result *out, ea
 
 /* ------------------------------------------------------------------ clustering main */
 
+static void growlog_add(growlog_t *gl, double u, double p) {
+  if (!gl) return;
+  if (gl->rows && gl->count < gl->max) {
+    double *row = gl->rows + 3 * gl->count;
+    row[0] = u; row[1] = p; row[2] = u - p;
+  }
+  ++gl->count;
+}
+
 /* cluster_flip!, inc/eap_chain.jl:269-333 (flip_f! = refl_n!, pflip = pflip_linear) */
-static double cluster_flip(const eap_params *P, uint32_t rng[5], chain_t *c, int64_t idx) {
+static double cluster_flip(const eap_params *P, uint32_t rng[5], chain_t *c, int64_t idx, proposal_t *pr, growlog_t *glog) {
   if (draw_u(rng) <= P->cluster_prob) return 1.0;                                  /* :276 */
   const int64_t n = c->n;
   double upper_p = 0.0, lower_p = 0.0;
@@ -538,18 +583,23 @@ static double cluster_flip(const eap_params *P, uint32_t rng[5], chain_t *c, int
       double d = c->nh[3 * upper] * c->nh[3 * upper + 3] + c->nh[3 * upper + 1] * c->nh[3 * upper + 4] +
                  c->nh[3 * upper + 2] * c->nh[3 * upper + 5];
       upper_p = (1 + d) / 2;
-      if (draw_u(rng) <= upper_p) { ++upper; if (upper >= n - 1) { upper_p = 0.0; gu = 0; } }
+      const double u = draw_u(rng);
+      growlog_add(glog, u, upper_p);
+      if (u <= upper_p) { ++upper; if (upper >= n - 1) { upper_p = 0.0; gu = 0; } }
       else gu = 0;
     }
     if (gl) {
       double d = c->nh[3 * lower] * c->nh[3 * lower - 3] + c->nh[3 * lower + 1] * c->nh[3 * lower - 2] +
                  c->nh[3 * lower + 2] * c->nh[3 * lower - 1];
       lower_p = (1 + d) / 2;
-      if (draw_u(rng) <= lower_p) { --lower; if (lower <= 0) { lower_p = 0.0; gl = 0; } }
+      const double u = draw_u(rng);
+      growlog_add(glog, u, lower_p);
+      if (u <= lower_p) { --lower; if (lower <= 0) { lower_p = 0.0; gl = 0; } }
       else gl = 0;
     }
   }
   for (int64_t i = lower; i <= upper; ++i) chain_move(P, c, i, 0.0, M_PI - 2 * c->th[i]);  /* refl_n!, :263-265,314-316 */
+  pr->lower = lower; pr->upper = upper; pr->flipped = 1;
   double new_upper_p = 0.0, new_lower_p = 0.0;                                      /* :318-327 */
   if (upper < n - 1)
     new_upper_p = (1 + (c->nh[3 * upper] * c->nh[3 * upper + 3] + c->nh[3 * upper + 1] * c->nh[3 * upper + 4] +
@@ -570,6 +620,24 @@ static void record_extra(double ex[2], const chain_t *c, int umbrella, double w)
   ex[1] += umbrella ? ps / expw : ps;
 }
 
+/* mcmc_clustering_eap_chain.jl:268-273 and the eps draw: the draws, move!, cluster_flip! on the trial chain */
+static void propose_cluster(const eap_params *P, uint32_t rng[5], const chain_t *cur, chain_t *trial,
+                            double phistep, double thstep, proposal_t *pr, growlog_t *gl, const double *moved_to) {
+  pr->w_idx = draw_w(rng); pr->w_phi = draw_w(rng); pr->w_th = draw_w(rng);
+  pr->idx = idx_of(pr->w_idx, P->n);
+  pr->flip_bit = 0;
+  double dphi = phistep * sym_of(pr->w_phi);
+  double dth = thstep * sym_of(pr->w_th);
+  if (moved_to) { dphi = moved_to[0] - cur->phi[pr->idx]; dth = moved_to[1] - cur->th[pr->idx]; }   /* judge only */
+  chain_copy(trial, cur);
+  chain_move(P, trial, pr->idx, dphi, dth);                     /* :272 */
+  pr->phi1 = trial->phi[pr->idx]; pr->th1 = trial->th[pr->idx];
+  pr->lower = pr->upper = pr->idx; pr->flipped = 0;
+  pr->alpha = cluster_flip(P, rng, trial, pr->idx, pr, gl);     /* :273 */
+  pr->w_eps = draw_w(rng);
+  pr->eps = eap_eps(P->uniform_bits, pr->w_eps, pr->w_idx, pr->w_phi, pr->w_th);
+}
+
 /* one call of mcmc(nsteps, pargs, chain), mcmc_clustering_eap_chain.jl:172-352 */
 static void cluster_stage(const eap_params *P, int64_t nsteps, uint32_t rng[5], chain_t *cur, chain_t *trial,
                           averagers_t *A, double extra[2], int64_t *nacc_total_out, double steps_out[2],
@@ -583,17 +651,11 @@ static void cluster_stage(const eap_params *P, int64_t nsteps, uint32_t rng[5], 
   extra[0] = extra[1] = 0.0;
   int64_t nacc = 0, natt = 0, nacc_total = 0;
   for (int64_t step = 1; step <= nsteps; ++step, ++*t) {          /* :268 */
-    const uint32_t w_idx = draw_w(rng), w_phi = draw_w(rng), w_th = draw_w(rng);
-    int64_t idx = idx_of(w_idx, P->n);
-    double dphi = phistep * sym_of(w_phi);
-    double dth = thstep * sym_of(w_th);
-    chain_copy(trial, cur);
-    chain_move(P, trial, idx, dphi, dth);                         /* :272 */
-    double alpha = cluster_flip(P, rng, trial, idx);              /* :273 */
-    double eps = eap_eps(P->uniform_bits, draw_w(rng), w_idx, w_phi, w_th);
+    proposal_t pr;
+    propose_cluster(P, rng, cur, trial, phistep, thstep, &pr, NULL, NULL);   /* :268-273 */
     /* acceptance.jl:29-39 with alpha; the cached value keeps the log(alpha) of the accepted move */
-    double logpi = -trial->U / P->kT + trial->Omega + (wf.on ? weight_eval(&wf, sum_us(trial)) : 1.0) + log(alpha);
-    int ok = (logpi >= logpi_prev) || (eps < exp(logpi - logpi_prev));
+    double logpi = -trial->U / P->kT + trial->Omega + (wf.on ? weight_eval(&wf, sum_us(trial)) : 1.0) + log(pr.alpha);
+    int ok = metropolis_ok(logpi - logpi_prev, pr.eps);
     if (!isfinite(trial->U)) ++*nan_rejects;
     if (ok) {
       logpi_prev = logpi;
@@ -652,6 +714,108 @@ int eap_run_cluster(const eap_params *P0, uint64_t chain_id, eap_result *out, ea
   if (tr && tr->final_theta) memcpy(tr->final_theta, cur.th, sizeof(double) * (size_t)P0->n);
   chain_free(&cur); chain_free(&trial);
   return 0;
+}
+
+/* ------------------------------------------------------------------ one-step judge */
+
+/* |t| over the terms t that d is the signed sum of, for a trial that changed the monomers [lo, hi] */
+static double judge_mag(const eap_params *P, const chain_t *cur, const chain_t *tri, int64_t lo, int64_t hi,
+                        double log_alpha) {
+  const int64_t n = cur->n;
+  const chain_t *side[2] = {cur, tri};
+  double e = 0.0, jac = 0.0;                 /* energy terms (divided by kT below), Jacobian terms */
+  for (int s = 0; s < 2; ++s) {
+    const chain_t *c = side[s];
+    for (int64_t i = lo; i <= hi; ++i) jac += fabs(log(c->sth[i]));
+    if (P->energy_type != EAP_CUTOFF) {      /* UCutoff is the pair sum alone, see chain_U */
+      for (int64_t i = lo; i <= hi; ++i) {
+        e += fabs(-0.5 * P->E0 * c->mus[3 * i + 2]);
+        e += fabs(P->Fx * P->b * c->nh[3 * i]) + fabs(P->Fz * P->b * c->nh[3 * i + 2]);
+      }
+      for (int64_t j = (lo > 0 ? lo - 1 : 0); j <= hi && j + 1 < n; ++j)
+        e += fabs(P->bend_mod / 2 * (c->psis[j] - P->bend_angle) * (c->psis[j] - P->bend_angle));
+    }
+    if (P->energy_type == EAP_ISING) {
+      for (int64_t j = (lo > 0 ? lo - 1 : 0); j <= hi && j + 1 < n; ++j)
+        e += fabs(pair_term(c->xs + 3 * j, c->xs + 3 * (j + 1), c->mus + 3 * j, c->mus + 3 * (j + 1)));
+    } else if (P->energy_type == EAP_INTERACTING || P->energy_type == EAP_CUTOFF) {
+      const double crad2 = (P->cutoff_radius * P->b) * (P->cutoff_radius * P->b);
+      for (int64_t i = 0; i <= hi; ++i)      /* x_j - x_i depends on the monomers i..j only */
+        for (int64_t j = (i + 1 > lo ? i + 1 : lo); j < n; ++j) {
+          const double *xi = c->xs + 3 * i, *xj = c->xs + 3 * j;
+          if (P->energy_type == EAP_CUTOFF) {
+            double rx = xi[0] - xj[0], ry = xi[1] - xj[1], rz = xi[2] - xj[2];
+            if (rx * rx + ry * ry + rz * rz > crad2) continue;
+          }
+          e += fabs(pair_term(xi, xj, c->mus + 3 * i, c->mus + 3 * j));
+        }
+    }
+  }
+  return 1.0 + e / fabs(P->kT) + jac + fabs(log_alpha);
+}
+
+static int step_judge(const eap_params *P, int cluster, const double *phi, const double *theta, const uint32_t rng_in[4],
+                      double phi_step, double theta_step, const double *moved_to, eap_step_out *out, double *trial_phi,
+                      double *trial_theta, double *grow, int64_t max_grow) {
+  if (check_params(P) || P->umbrella || !out) return -1;
+  if (!cluster && P->energy_type == EAP_CUTOFF) return -1;
+  uint32_t rng[5] = {rng_in[0], rng_in[1], rng_in[2], rng_in[3], (uint32_t)P->rng};
+  chain_t cur, tri;
+  if (chain_alloc(&cur, P->n) || chain_alloc(&tri, P->n)) return -2;
+  memcpy(cur.phi, phi, sizeof(double) * (size_t)P->n);
+  memcpy(cur.th, theta, sizeof(double) * (size_t)P->n);
+  chain_derive(P, &cur);
+  proposal_t pr;
+  growlog_t gl = {grow, max_grow, 0};
+  if (cluster) propose_cluster(P, rng, &cur, &tri, phi_step, theta_step, &pr, &gl, moved_to);
+  else propose_single(P, rng, &cur, &tri, phi_step, theta_step, &pr, moved_to);
+  const int64_t lo = pr.lower, hi = pr.upper;
+  double djac = 0.0;
+  for (int64_t i = lo; i <= hi; ++i) djac += log(tri.sth[i]) - log(cur.sth[i]);
+  const double log_alpha = log(pr.alpha);
+  out->d = -(tri.U - cur.U) / P->kT + djac + log_alpha;
+  out->mag = judge_mag(P, &cur, &tri, lo, hi, log_alpha);
+  out->eps = pr.eps;
+  out->log_alpha = log_alpha;
+  out->accept = metropolis_ok(out->d, pr.eps);
+  out->idx = pr.idx; out->lower = lo; out->upper = hi;
+  out->flipped = pr.flipped; out->flip_bit = pr.flip_bit;
+  out->phi_trial = pr.phi1; out->theta_trial = pr.th1;
+  out->ngrow = gl.count;
+  out->U_cur = cur.U; out->U_trial = tri.U;
+  memcpy(out->rng, rng, sizeof out->rng);
+  if (trial_phi) memcpy(trial_phi, tri.phi, sizeof(double) * (size_t)P->n);
+  if (trial_theta) memcpy(trial_theta, tri.th, sizeof(double) * (size_t)P->n);
+  chain_free(&cur); chain_free(&tri);
+  return 0;
+}
+
+int eap_step_judge(const eap_params *P, const double *phi, const double *theta, const uint32_t rng[4],
+                   double phi_step, double theta_step, const double *moved_to, eap_step_out *out, double *trial_phi,
+                   double *trial_theta) {
+  return step_judge(P, 0, phi, theta, rng, phi_step, theta_step, moved_to, out, trial_phi, trial_theta, NULL, 0);
+}
+
+int eap_step_judge_cluster(const eap_params *P, const double *phi, const double *theta, const uint32_t rng[4],
+                           double phi_step, double theta_step, const double *moved_to, eap_step_out *out, double *trial_phi,
+                           double *trial_theta, double *grow, int64_t max_grow) {
+  return step_judge(P, 1, phi, theta, rng, phi_step, theta_step, moved_to, out, trial_phi, trial_theta, grow, max_grow);
+}
+
+void eap_seed_state(const eap_params *P, uint64_t chain_id, uint32_t rng[4], double *phi, double *theta) {
+  uint32_t s[5];
+  seed_chain(P, chain_id, s);
+  chain_t c;
+  if (chain_alloc(&c, P->n)) return;
+  chain_random(P, s, &c);
+  memcpy(phi, c.phi, sizeof(double) * (size_t)P->n);
+  memcpy(theta, c.th, sizeof(double) * (size_t)P->n);
+  memcpy(rng, s, sizeof(uint32_t) * 4);
+  chain_free(&c);
+}
+
+void eap_adapt(const eap_params *P, int64_t step, double *phi_step, double *theta_step, int64_t *nacc, int64_t *natt) {
+  adapt(P, step, phi_step, theta_step, nacc, natt);
 }
 
 /* ------------------------------------------------------------------ incremental run */

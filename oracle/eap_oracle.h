@@ -124,6 +124,45 @@ int eap_run_fast(const eap_params *P, uint64_t chain_id, eap_result *out, eap_tr
  * :365-386).  Energy types: noninteracting, Ising, interacting. */
 int eap_run_cluster(const eap_params *P, uint64_t chain_id, eap_result *out, eap_trace *tr);
 
+/* --- the one-step judge: one step of either main from an explicit state, judged in f64 ---
+ * The run loops above and these entry points share the functions that draw the step's words, build the trial chain
+ * (move!, cluster_flip!) and apply acceptance.jl:29-39; what differs is where the density of the CURRENT chain comes
+ * from: the run loops keep the acceptor's cached value, the judge computes both sides fresh from the angles it is given.
+ * No umbrella sampling (returns -1). */
+typedef struct eap_step_out {
+  uint32_t rng[4];              /* generator words after the step */
+  int64_t idx;                  /* the monomer of the single move */
+  int64_t lower, upper;         /* the monomers whose angles the trial changes: [idx, idx], or the reflected cluster */
+  int32_t flipped;              /* clustering main: a cluster was grown and reflected */
+  int32_t flip_bit;             /* fixed-force main: the --do-flips bit of this step */
+  int32_t accept;               /* d >= 0 || eps < exp(d) */
+  int32_t pad_;
+  int64_t ngrow;                /* growth tests made (rows of `grow`) */
+  double phi_trial, theta_trial;/* the moved monomer after move!, before any reflection */
+  double d;                     /* log pi(trial) - log pi(current) [+ log alpha]: -dU/kT + sum of log sin(theta') - log sin(theta) */
+  double eps;                   /* under P->uniform_bits */
+  double mag;                   /* 1 + sum |t| over the terms t that d is the signed sum of: the field, force and bending terms
+                                   of the changed monomers and every pair term that changes, old and new, over kT;
+                                   |log sin theta| and |log sin theta'| of the changed monomers; |log alpha| */
+  double log_alpha;
+  double U_cur, U_trial;        /* energy.jl:7-23 of both chains */
+} eap_step_out;
+/* phi, theta: [n], radians.  rng: the four state words (the kind is P->rng).  trial_phi / trial_theta: [n] or NULL, every
+ * angle of the trial chain.  grow: [max_grow][3] or NULL -- per growth test the draw, the link probability, draw - probability.
+ * moved_to: NULL, or {phi', theta'} that the single move puts monomer idx at in place of the step's own displacement -- for a
+ * state that lives on a lattice (PSTAT_Q16), whose trial is the lattice point its rounding rule gives; every word is still
+ * drawn, and the cluster grows from the monomer as given. */
+int eap_step_judge(const eap_params *P, const double *phi, const double *theta, const uint32_t rng[4],
+                   double phi_step, double theta_step, const double *moved_to, eap_step_out *out, double *trial_phi,
+                   double *trial_theta);
+int eap_step_judge_cluster(const eap_params *P, const double *phi, const double *theta, const uint32_t rng[4],
+                           double phi_step, double theta_step, const double *moved_to, eap_step_out *out, double *trial_phi,
+                           double *trial_theta, double *grow, int64_t max_grow);
+/* the seeded start of chain `chain_id`: EAPChain(pargs) and the generator words after its draws */
+void eap_seed_state(const eap_params *P, uint64_t chain_id, uint32_t rng[4], double *phi, double *theta);
+/* the step-size adaptation of mcmc_eap_chain.jl:301-322 as the run loops apply it after in-run step `step` (1-based) */
+void eap_adapt(const eap_params *P, int64_t step, double *phi_step, double *theta_step, int64_t *nacc, int64_t *natt);
+
 /* Many independent chains (chain ids id0 .. id0+nchains-1), one per worker
  * thread at a time, mirroring the reference's pmap process farm. mode: 0 faithful, 1 fast. */
 int eap_run_many(const eap_params *P, uint64_t id0, int64_t nchains, int nthreads,
