@@ -685,7 +685,10 @@ __device__ __forceinline__ void run_segment(const SweepArgs &A, const DevState &
       R dw = 0;
       if constexpr (RARE) dw = du * wscale;   // change of the umbrella weight function (0 if off)
       if constexpr (sizeof(R) == 8) {
-        ok = metropolis_f64(dU, kT, ninv_kT, st1, st0, dw - lag, A.wide_eps != 0, d.weps, d.w0, d.wphi, d.wth);
+        // (cells in memory: the straight common path.  The LDS home keeps the plain form: with the literal block
+        // behind its 2-step loop it issued 14 instructions more per update and ran 3 % slower,
+        // profiles/r06/experiments/ab_straight_path.txt)
+        ok = metropolis_f64<GM>(dU, kT, ninv_kT, st1, st0, dw - lag, A.wide_eps != 0, d.weps, d.w0, d.wphi, d.wth);
       } else {
         // same test with the logarithm folded away: eps * sin(th0) < sin(th1) * exp(-dU/kT + dw - lag)
         R e;

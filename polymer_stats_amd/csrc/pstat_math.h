@@ -146,7 +146,14 @@ __device__ __forceinline__ double eps_uniform(const bool wide, const uint32_t we
 // underflow to 0 and eps = 0 all land in the literal branch or on the side the literal test takes.
 // x = everything in delta except the logarithm of the ratio num / den (sweep: num / den = sin(theta') / sin(theta); clustering
 // main: times the Hastings ratio alpha); literal() = the reference's expression, evaluated only in the rare branch.
-template <typename Literal>
+// STRAIGHT (the step loop of the f64 sweep with its cells in memory): the same filter and the same verdicts,
+// with the rare branch shaped for a lone wave's straight-line common path.  "Some lane undecided" is formed from the two
+// compares' own lane masks on the scalar side -- (acc | rej) != exec: one s_or, one s_cmp, a branch on scc -- instead of
+// a ballot of the combined predicate, which compiles to a select and a third vector compare (two vector instructions
+// per step) and a branch on a VALU-written vcc; and the branch is marked unlikely, so block placement moves the literal
+// evaluation (and the reloads of the scalars spilled around it) behind the loop: the common path falls through a
+// not-taken branch.  (The expectation has to stand in the `if` itself.)
+template <bool STRAIGHT = false, typename Literal>
 __device__ __forceinline__ bool metropolis_filter(const double x, const double num, const double den, const uint32_t weps,
                                                   Literal &&literal) {
   const float t = (float)x;
@@ -162,16 +169,20 @@ __device__ __forceinline__ bool metropolis_filter(const double x, const double n
   const bool acc = __builtin_fmaf(lhs_hi, m, lhs_hi) < rhs, rej = lhs > __builtin_fmaf(rhs, m, rhs);
 #endif
   bool ok = acc;
-  if (__builtin_amdgcn_ballot_w64(!(acc || rej)) != 0) {        // some lane is too close to call (or not finite)
+  const bool undecided = STRAIGHT ? (__builtin_amdgcn_ballot_w64(acc) | __builtin_amdgcn_ballot_w64(rej)) !=
+                                        __builtin_amdgcn_ballot_w64(true)
+                                  : __builtin_amdgcn_ballot_w64(!(acc || rej)) != 0;
+  if (STRAIGHT ? __builtin_expect(undecided, false) : undecided) {   // some lane is too close to call (or not finite)
     const bool lit = literal();
     ok = (acc || rej) ? acc : lit;
   }
   return ok;
 }
+template <bool STRAIGHT = false>
 __device__ __forceinline__ bool metropolis_f64(const double dU, const double kT, const double ninv_kT, const double st1,
                                                const double st0, const double extra, const bool wide, const uint32_t weps,
                                                const uint32_t w0, const uint32_t wphi, const uint32_t wth) {
-  return metropolis_filter(dU * ninv_kT + extra, st1, st0, weps, [&]() -> bool {
+  return metropolis_filter<STRAIGHT>(dU * ninv_kT + extra, st1, st0, weps, [&]() -> bool {
     const double delta = -dU / kT + log_f64(st1 / st0) + extra;
     const double eps = eps_uniform(wide, weps, w0, wphi, wth);
     return (delta >= 0) || (eps < exp_f64(delta));
