@@ -291,7 +291,7 @@ int pstat_microstate(pstat_handle *h, int64_t chain, double out[7]);
 
 /* The quantities printed at mcmc_eap_chain.jl:365,386-395.  Synchronises.  Like every accessor that
  * synchronises (pstat_sync, pstat_reduce_host, pstat_rolling, pstat_microstate, pstat_chain_state,
- * pstat_chain_extras, pstat_checkpoint, pstat_corr_read, pstat_corr_rows, pstat_series_read, pstat_series_error_bars, pstat_hist_read) it fails with PSTAT_ERR_HIP if a launch since the last successful
+ * pstat_chain_extras, pstat_checkpoint, pstat_corr_read, pstat_corr_rows, pstat_shape_read, pstat_shape_rows, pstat_series_read, pstat_series_error_bars, pstat_hist_read) it fails with PSTAT_ERR_HIP if a launch since the last successful
  * call did not run to completion (a job of the persistent kernels timed out waiting for its predecessor):
  * the handle's averages are then not the averages of the steps it was asked for. */
 int pstat_summary_get(pstat_handle *h, int32_t icase, pstat_summary *out);
@@ -534,6 +534,58 @@ int pstat_corr_read(pstat_handle *h, pstat_corr *g, double *sum /* [ncases][ncol
 int pstat_corr_rows(pstat_handle *h, pstat_corr *g, const double **dev_rows /* DEVICE memory */, int64_t *nrows, int64_t *stride);
 int pstat_corr_clear(pstat_handle *h, pstat_corr *g);
 void pstat_corr_close(pstat_handle *h, pstat_corr *g);
+
+/* Chain shape on the device: per-case gyration tensor and form factor S(q) of the monomers' positions.  The correlations above
+ * read the bond directions; this reads where the monomers are: the size and shape of the coil and what it scatters.  The
+ * reference keeps the positions (chain.xs, inc/eap_chain.jl:49-51) only to feed its pair energies.  A shape object is a sibling of
+ * a correlation object: it belongs to the handle it was opened on, one record is a pair of launches on the handle's stream that
+ * reads the stored angles of EVERY chain where they sit and writes the object's own buffers only.
+ * The contract (DESIGN.md 3.16 states it in full; polymer_stats_amd/csrc/pstat_shape.hip is the device's statement).  All in f64
+ * from the doubles pstat_chain_state returns for the angles, whatever the handle's precision:
+ *   unit vectors    as for the correlations; a planar handle's n_i = (cos phi_i, sin phi_i) sits in the x and z slots, y = 0.
+ *   positions       x_i = b (sum_{j <= i} n_j - n_i / 2), i = 0 .. n - 1: the monomers' centres, with the case's own b.
+ *   gyration block  PSTAT_SHAPE_GYR = 8 columns per chain, in this order: gxx, gyy, gzz, gxy, gxz, gyz, rg2, trg2.
+ *                   xbar = (1 / n) sum_i x_i;  G_ab = (1 / n) sum_i (x_i - xbar)_a (x_i - xbar)_b, centred first;
+ *                   rg2 = G_xx + G_yy + G_zz;  trg2 = sum_ab G_ab^2, the off-diagonals counted twice.
+ *                   A planar handle's gyy, gxy and gyz are exactly 0.
+ *   form factor     nq >= 0 columns follow, one per wave-vector of the table q[nq][3] (absolute units; a planar handle
+ *                   ignores q[.][1]):  S(c, q) = (1 / n) [(sum_i cos(q . x_i))^2 + (sum_i sin(q . x_i))^2]; q = 0 gives exactly n.
+ *   columns         ncols = PSTAT_SHAPE_GYR + nq.
+ *   totals          per case and column one record adds the sum over the case's chains of the per-chain value to `sum` and the
+ *                   sum of its square to `sumsq`; both are additive across handles.  After ONE record the pooled mean
+ *                   sum / num_chains has the across-chain standard error sqrt((sumsq / N - mean^2) / (N - 1)), N = num_chains.
+ *                   Over many records the mean is sum / (records * num_chains) and its error bar comes from the rows through
+ *                   pstat_blocking_device.
+ *   reproducible    no floating-point atomics; the order of every addition, the prefix sum that makes the positions included,
+ *                   depends on (ncases, num_chains, n, nq) only: two identical runs give bit-identical totals.
+ *
+ *   pstat_shape_open    q: host memory, copied.  capacity_rows = 0 keeps the totals only; > 0 also keeps one row per record.
+ *                       Before the device is touched, with a message naming the argument, PSTAT_ERR_INVALID_ARG: null
+ *                       arguments; nq < 0; a null q with nq > 0; a q component that is not finite; capacity_rows < 0; a
+ *                       wave-vector and case with (|q_x| + |q_y| + |q_z|) b n >= 1e5 (below that the device's sincos is its
+ *                       < 1 ulp routine; |q_y| does not count for a planar handle).  PSTAT_ERR_UNSUPPORTED: nq >
+ *                       PSTAT_SHAPE_MAX_Q = 512; an umbrella-sampling handle (its samples carry per-chain weights whose gauge
+ *                       the sums do not hold); a chain whose positions do not fit the 60 KiB of LDS a workgroup keeps them in:
+ *                       n > 2560 (planar handles: n > 3840).  PSTAT_ERR_NOMEM: the device allocation fails.
+ *   pstat_shape_record, pstat_advance_shape, pstat_shape_read, pstat_shape_rows, pstat_shape_clear, pstat_shape_close
+ *                       what the pstat_corr_* call of the same name does for a correlation object: PSTAT_ERR_TOO_SMALL before
+ *                       anything is enqueued when the rows would not fit; _read and _rows synchronise and fail like every
+ *                       accessor that does after an incomplete launch; the rows are a DEVICE matrix [*nrows][*stride = ncases *
+ *                       ncols] that pstat_blocking_device accepts; pstat_destroy closes the objects still open; a shape object
+ *                       is not part of a checkpoint.
+ *   An object of another handle (or a closed one) is PSTAT_ERR_INVALID_ARG.  Every home, every precision and planar handles
+ *   are accepted. */
+#define PSTAT_SHAPE_GYR 8
+#define PSTAT_SHAPE_MAX_Q 512
+typedef struct pstat_shape pstat_shape;
+int pstat_shape_open(pstat_handle *h, const double *q /* host [nq][3] */, int32_t nq, int64_t capacity_rows, pstat_shape **out);
+int pstat_shape_record(pstat_handle *h, pstat_shape *g);
+int pstat_advance_shape(pstat_handle *h, pstat_shape *g, int64_t nsteps, int64_t stepout);
+int pstat_shape_read(pstat_handle *h, pstat_shape *g, double *sum /* [ncases][ncols] */, double *sumsq /* [ncases][ncols] */,
+                     int64_t *records);
+int pstat_shape_rows(pstat_handle *h, pstat_shape *g, const double **dev_rows /* DEVICE memory */, int64_t *nrows, int64_t *stride);
+int pstat_shape_clear(pstat_handle *h, pstat_shape *g);
+void pstat_shape_close(pstat_handle *h, pstat_shape *g);
 
 /* Per-chain accessors for tests and tooling (host buffers).  angles: theta[n] then phi[n] as
  * doubles, radians; sums: the 16 per-chain running sums in rolling.csv order;

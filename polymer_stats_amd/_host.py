@@ -323,6 +323,43 @@ def check_corr(pargs: dict, spec, write_csv: bool = False, devices: int | None =
                               "for float64 runs only")
 
 
+def parse_shape(text: str):
+    """--shape [AXIS:QMAX:NQ[,AXIS:QMAX:NQ...]] of tools/run_sweep.py -> ("shape", [[qx, qy, qz], ...]): every entry gives NQ
+    wave-vectors QMAX (1 .. NQ) / NQ along AXIS (x, y or z); an empty text: no wave-vector, the gyration block only."""
+    q = []
+    for entry in [t for t in str(text or "").split(",") if t.strip() != ""]:
+        parts = entry.strip().split(":")
+        try:
+            axis, qmax, nq = "xyz".index(parts[0].strip().lower()) if len(parts[0].strip()) == 1 else -1, float(parts[1]), int(parts[2])
+            if len(parts) != 3 or axis < 0 or nq < 1 or not np.isfinite(qmax) or qmax <= 0.0:
+                raise ValueError
+        except (ValueError, IndexError):
+            raise ReferenceError_(f"--shape '{text}' not understood: AXIS:QMAX:NQ[,AXIS:QMAX:NQ...] with AXIS one of x, y, z, "
+                                  "QMAX > 0 and NQ >= 1")
+        for j in range(1, nq + 1):
+            v = [0.0, 0.0, 0.0]
+            v[axis] = qmax * j / nq
+            q.append(v)
+    if len(q) > _lib.SHAPE_MAX_Q:
+        raise ReferenceError_(f"--shape '{text}': {len(q)} wave-vectors, at most {_lib.SHAPE_MAX_Q}")
+    return "shape", q
+
+
+def check_shape(pargs: dict, spec, write_csv: bool = False, devices: int | None = None, error_bars: int = 0, hist=None, corr=None):
+    """What --shape (tools/run_sweep.py; run_cases(..., shape=parse_shape(...))) cannot be combined with, refused before any GPU
+    work: what --corr cannot, for the same reasons (check_corr), --corr itself, and a wave-vector whose phase the library refuses."""
+    if corr:
+        raise ReferenceError_("--shape cannot be combined with --corr: each records the production run in its own way")
+    try:
+        check_corr(pargs, (0, ("nn",)), write_csv, devices=devices, error_bars=error_bars, hist=hist)
+    except ReferenceError_ as e:
+        raise ReferenceError_(str(e).replace("--corr", "--shape").replace("as correlations", "as shape columns"))
+    reach = float(pargs["mlen"]) * int(pargs["num-monomers"])
+    for v in spec[1]:
+        if sum(abs(c) for c in v) * reach >= 1.0e5:
+            raise ReferenceError_(f"--shape: |q| b n = {sum(abs(c) for c in v) * reach:g} for q = {v} is not below 1e5")
+
+
 def burn_ladder(pargs: dict) -> list[float]:
     """--burn-schedule of the two clustering mains: a Julia vector literal of kT multipliers."""
     try:
@@ -569,6 +606,23 @@ class _Pool:
         self.advance(nsteps)
         return res
 
+    def shapes(self, nsteps, stepout, spec):
+        """advance(nsteps) with one record of the gyration block and of S at the wave-vectors of `spec` = parse_shape(...) after
+        every `stepout`-th step, rows kept -> (ShapeResult, ErrorBars of the rows).  Made TWICE from the same state like
+        correlations, and for the same reason."""
+        check_shape(self.plist[0], spec, devices=len(self.parts))
+        e = self.parts[0]
+        image = e.checkpoint()
+        g = e.open_shape(spec[1], capacity_rows=nsteps // stepout)
+        try:
+            e.advance_shape(g, (nsteps // stepout) * stepout, stepout)      # (the remainder would be lost with the restore anyway)
+            res = g.read(), g.error_bars(min_blocks=CORR_MIN_RECORDS)
+        finally:
+            g.close()
+            e.restore(image)      # also when the recorded run failed: the handle is never left mid-run
+        self.advance(nsteps)
+        return res
+
     def chain0(self, k=0):
         return self.parts[0].chain_state(k * self.counts[0])      # the first chain of case k
 
@@ -661,7 +715,7 @@ class CsvFiles:
 
 
 def recorded_stage(pool, nsteps, write: bool, traj_header, roll_header, rows, angles=False, runs=(None,), report=None,
-                   error_bars: int = 0, hist=None, corr=None):
+                   error_bars: int = 0, hist=None, corr=None, shape=None):
     """One recorded run of `nsteps` for every case of the pool, the body of the reference's mcmc(nsteps, pargs[, chain]):
     with `write` the two CSV files of every case (headers `traj_header(pargs)` and `roll_header`, a row per --stepout
     steps: `rows(pargs, step, micro, ang, summary)` -> the case's (trajectory row, rolling row)), then the summaries, the
@@ -671,7 +725,8 @@ def recorded_stage(pool, nsteps, write: bool, traj_header, roll_header, rows, an
     gets their blocked standard errors under "error_bars".  `hist` = [(channel, lo, hi, nbins), ...] (without `write`): every
     chain is histogrammed every --stepout steps of the run (_Pool.histograms) and `info` gets the HistResult under "hist".  `corr` = (max_lag, channels)
     (without `write`): the lag correlations are recorded every --stepout steps (_Pool.correlations) and `info` gets the
-    (CorrResult, ErrorBars) under "corr"."""
+    (CorrResult, ErrorBars) under "corr".  `shape` = parse_shape(...) (without `write`): likewise the gyration block and the form
+    factor (_Pool.shapes), `info` gets the (ShapeResult, ErrorBars) under "shape"."""
     plist = pool.plist
     pargs = plist[0]
     stepout = int(pargs["stepout"]) if write else 0
@@ -703,6 +758,11 @@ def recorded_stage(pool, nsteps, write: bool, traj_header, roll_header, rows, an
                 res = pool.correlations(nsteps, int(pargs["stepout"]), corr)
                 if pool.info is not None:
                     pool.info["corr"] = res
+                continue
+            if shape:
+                res = pool.shapes(nsteps, int(pargs["stepout"]), shape)
+                if pool.info is not None:
+                    pool.info["shape"] = res
                 continue
             for step, micro, ang, sums in pool.recorded(nsteps, stepout, angles=angles, tick=tick):
                 for k in range(len(files)):
@@ -761,6 +821,18 @@ def corr_lines(res, eb, k: int) -> list[str]:
     for lag in range(w):
         out.append(f"{lag}," + ",".join(f"{float(res.mean[ch][k, lag])!r},{float(eb.stderr[k, i * w + lag])!r}"
                                         for i, ch in enumerate(res.channels)))
+    return out
+
+
+def shape_lines(res, eb, k: int) -> list[str]:
+    """`<case>.shape`: CSV `name,qx,qy,qz,value,stderr`: the eight gyration rows (no wave-vector), then a row `sq` per
+    wave-vector: the mean over records and chains and its blocked standard error from the records' rows."""
+    out = ["name,qx,qy,qz,value,stderr"]
+    for i, name in enumerate(_lib.SHAPE_NAMES):
+        out.append(f"{name},,,,{float(res.mean[k, i])!r},{float(eb.stderr[k, i])!r}")
+    for j, v in enumerate(res.q):
+        i = len(_lib.SHAPE_NAMES) + j
+        out.append(f"sq,{float(v[0])!r},{float(v[1])!r},{float(v[2])!r},{float(res.mean[k, i])!r},{float(eb.stderr[k, i])!r}")
     return out
 
 

@@ -38,6 +38,9 @@ HIST_MAX_BINS = 8192
 HIST_MAX_SPECS = 16
 # correlation channels (pstat_corr_*): bit i of the PSTAT_CORR_* mask is CORR_NAMES[i]; columns come in this order
 CORR_NAMES = ("nn", "zz", "mm")
+# the gyration block of a shape object (pstat_shape_*): its first PSTAT_SHAPE_GYR columns, in this order; S(q) columns follow
+SHAPE_NAMES = ("gxx", "gyy", "gzz", "gxy", "gxz", "gyz", "rg2", "trg2")
+SHAPE_MAX_Q = 512
 
 # every symbol include/pstat.h declares (tests check the built library exports all of them)
 SYMBOLS = [
@@ -53,6 +56,8 @@ SYMBOLS = [
     "pstat_histogram_device",
     "pstat_corr_open", "pstat_corr_record", "pstat_advance_corr", "pstat_corr_read", "pstat_corr_rows", "pstat_corr_clear",
     "pstat_corr_close",
+    "pstat_shape_open", "pstat_shape_record", "pstat_advance_shape", "pstat_shape_read", "pstat_shape_rows", "pstat_shape_clear",
+    "pstat_shape_close",
 ]
 ABI_VERSION = 6
 
@@ -180,6 +185,14 @@ def load():
     L.pstat_corr_clear.argtypes = [vp, vp]
     L.pstat_corr_close.argtypes = [vp, vp]
     L.pstat_corr_close.restype = None
+    L.pstat_shape_open.argtypes = [vp, dp, i32, i64, C.POINTER(vp)]
+    L.pstat_shape_record.argtypes = [vp, vp]
+    L.pstat_advance_shape.argtypes = [vp, vp, i64, i64]
+    L.pstat_shape_read.argtypes = [vp, vp, dp, dp, ip]
+    L.pstat_shape_rows.argtypes = [vp, vp, C.POINTER(vp), ip, ip]
+    L.pstat_shape_clear.argtypes = [vp, vp]
+    L.pstat_shape_close.argtypes = [vp, vp]
+    L.pstat_shape_close.restype = None
     if L.pstat_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI version {L.pstat_abi_version()}, this binding needs {ABI_VERSION}: "
                           "rebuild it with `make -C polymer_stats_amd/csrc`")

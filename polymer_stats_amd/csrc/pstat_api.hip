@@ -114,6 +114,7 @@ struct pstat_handle {
   std::vector<pstat_tempering *> tempering;   // tempering objects still open (likewise)
   std::vector<pstat_hist *> hists;      // histograms still open (likewise)
   std::vector<pstat_corr *> corrs;      // correlation objects still open (likewise)
+  std::vector<pstat_shape *> shapes;    // shape objects still open (likewise)
 };
 
 // The stepout time series of one handle: rows recorded on the device by launch_record, read back in bulk.
@@ -151,6 +152,17 @@ struct pstat_corr {
   int64_t capacity = 0, rows = 0;   // rows kept (0: totals only) and taken
   double *d_totals = nullptr;       // [2][ncases][ncols]: sum, sumsq
   double *d_partial = nullptr;      // corr_partial_doubles(args): the tiles' partial sums of one record
+  double *d_rows = nullptr;         // [capacity][ncases][ncols]
+};
+
+// Per-case gyration tensor and form factor of one handle (pstat_shape.hip).
+struct pstat_shape {
+  ShapeArgs args{};
+  int64_t records = 0;              // records enqueued since open / the last clear (known when a record is enqueued)
+  int64_t capacity = 0, rows = 0;   // rows kept (0: totals only) and taken
+  double *d_q = nullptr;            // [nq][3]: the wave-vectors
+  double *d_totals = nullptr;       // [2][ncases][ncols]: sum, sumsq
+  double *d_partial = nullptr;      // shape_partial_doubles(args): the tiles' partial sums of one record
   double *d_rows = nullptr;         // [capacity][ncases][ncols]
 };
 
@@ -679,6 +691,20 @@ void free_corr(pstat_corr *g) {
   delete g;
 }
 
+pstat_shape *own_shape(pstat_handle *h, pstat_shape *g) {
+  for (pstat_shape *mine : h->shapes)
+    if (mine == g) return g;
+  return nullptr;
+}
+
+void free_shape(pstat_shape *g) {
+  (void)hipFree(g->d_q);
+  (void)hipFree(g->d_totals);
+  (void)hipFree(g->d_partial);
+  (void)hipFree(g->d_rows);
+  delete g;
+}
+
 HistArgs hist_args(const pstat_handle *h, const pstat_hist *g) {
   return HistArgs{h->base.num_chains, h->ncases, h->S.C, 1, g->nspecs, g->total_bins, g->per_case, 0};
 }
@@ -928,6 +954,7 @@ void pstat_destroy(pstat_handle *h) {
   for (pstat_tempering *t : h->tempering) free_tempering(t);
   for (pstat_hist *g : h->hists) free_hist(g);
   for (pstat_corr *g : h->corrs) free_corr(g);
+  for (pstat_shape *g : h->shapes) free_shape(g);
   if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }
@@ -1477,6 +1504,150 @@ void pstat_corr_close(pstat_handle *h, pstat_corr *g) {
   for (size_t i = 0; i < h->corrs.size(); ++i)
     if (h->corrs[i] == g) { h->corrs.erase(h->corrs.begin() + (long)i); break; }
   free_corr(g);
+}
+
+int pstat_shape_open(pstat_handle *h, const double *q, int32_t nq, int64_t capacity_rows, pstat_shape **out) {
+  if (!h || !out) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
+  *out = nullptr;
+  const int64_t n = h->base.n;
+  const bool planar = h->cfg.planar;
+  if (nq < 0) return fail(PSTAT_ERR_INVALID_ARG, "nq must be >= 0, not %d", nq);
+  if (nq > PSTAT_SHAPE_MAX_Q)
+    return fail(PSTAT_ERR_UNSUPPORTED, "nq = %d: at most PSTAT_SHAPE_MAX_Q = %d wave-vectors per shape object", nq, PSTAT_SHAPE_MAX_Q);
+  if (nq > 0 && !q) return fail(PSTAT_ERR_INVALID_ARG, "q is null with nq = %d", nq);
+  for (int32_t k = 0; k < 3 * nq; ++k)
+    if (!std::isfinite(q[k])) return fail(PSTAT_ERR_INVALID_ARG, "q[%d][%d] is not finite", k / 3, k % 3);
+  if (capacity_rows < 0) return fail(PSTAT_ERR_INVALID_ARG, "capacity_rows must be >= 0, not %lld", (long long)capacity_rows);
+  for (int32_t k = 0; k < nq; ++k) {
+    const double q1 = std::fabs(q[3 * k]) + (planar ? 0.0 : std::fabs(q[3 * k + 1])) + std::fabs(q[3 * k + 2]);
+    for (int c = 0; c < h->ncases; ++c)
+      if (!(q1 * std::fabs(h->cases[(size_t)c].b) * (double)n < 1.0e5))
+        return fail(PSTAT_ERR_INVALID_ARG, "q[%d] = (%g, %g, %g) with case %d (b = %g, n = %lld): (|q_x| + |q_y| + |q_z|) b n must stay "
+                    "below 1e5, where the device's sincos is its < 1 ulp routine", k, q[3 * k], q[3 * k + 1], q[3 * k + 2], c,
+                    h->cases[(size_t)c].b, (long long)n);
+  }
+  if (h->cfg.umbrella)
+    return fail(PSTAT_ERR_UNSUPPORTED, "chain shape under --umbrella-sampling: the samples carry per-chain weights whose gauge "
+                "the sums do not hold");
+  if (n > corr_max_n(h->cfg.planar))
+    return fail(PSTAT_ERR_UNSUPPORTED, "n = %lld: a chain's positions must fit the LDS of a workgroup, n <= %lld for a %s handle",
+                (long long)n, (long long)corr_max_n(h->cfg.planar), planar ? "planar" : "3D");
+  const int32_t ncols = PSTAT_SHAPE_GYR + nq;
+  const size_t stride = (size_t)h->ncases * (size_t)ncols;
+  if (capacity_rows > 0 && (uint64_t)capacity_rows > (SIZE_MAX / sizeof(double)) / stride)
+    return fail(PSTAT_ERR_NOMEM, "%lld rows of shape columns do not fit the address space", (long long)capacity_rows);
+  PSTAT_TRY(set_device(h));
+  pstat_shape *g = new (std::nothrow) pstat_shape;
+  if (!g) return fail(PSTAT_ERR_NOMEM, "host allocation failed");
+  ShapeArgs &a = g->args;
+  a.per = h->base.num_chains; a.ncases = h->ncases; a.n = n;
+  a.nq = nq; a.ncols = ncols;
+  a.elem = (int32_t)h->elem; a.planar = planar ? 1 : 0;
+  shape_layout(a);
+  g->capacity = capacity_rows;
+  hipError_t e = hipMalloc((void **)&g->d_totals, 2 * stride * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc((void **)&g->d_partial, shape_partial_doubles(a) * sizeof(double));
+  if (e == hipSuccess && nq > 0) e = hipMalloc((void **)&g->d_q, 3 * (size_t)nq * sizeof(double));
+  if (e == hipSuccess && capacity_rows > 0) e = hipMalloc((void **)&g->d_rows, (size_t)capacity_rows * stride * sizeof(double));
+  if (e != hipSuccess) {
+    free_shape(g);
+    return fail(PSTAT_ERR_NOMEM, "shape object of %zu columns, %lld rows: %s", stride, (long long)capacity_rows, hipGetErrorString(e));
+  }
+  e = hipMemsetAsync(g->d_totals, 0, 2 * stride * sizeof(double), h->stream);   // ahead of the first record
+  if (e == hipSuccess && nq > 0) e = hipMemcpy(g->d_q, q, 3 * (size_t)nq * sizeof(double), hipMemcpyHostToDevice);   // the caller's table may go
+  if (e != hipSuccess) {
+    free_shape(g);
+    return fail(PSTAT_ERR_HIP, "shape totals: %s", hipGetErrorString(e));
+  }
+  try {
+    h->shapes.push_back(g);
+  } catch (const std::bad_alloc &) {
+    free_shape(g);
+    return fail(PSTAT_ERR_NOMEM, "host allocation failed");
+  }
+  *out = g;
+  return PSTAT_OK;
+}
+
+// one record, enqueued; the caller has checked that a row is free
+static int enqueue_shape(pstat_handle *h, pstat_shape *g) {
+  const size_t stride = (size_t)h->ncases * (size_t)g->args.ncols;
+  HIP_TRY(launch_shape(g->args, h->S.ang, h->d_cases, g->d_q, g->d_partial, g->d_totals,
+                       g->capacity > 0 ? g->d_rows + (size_t)g->rows * stride : nullptr, h->stream));
+  g->records += 1;
+  if (g->capacity > 0) g->rows += 1;
+  return PSTAT_OK;
+}
+
+int pstat_shape_record(pstat_handle *h, pstat_shape *g) {
+  if (!h || !g) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
+  if (!own_shape(h, g)) return fail(PSTAT_ERR_INVALID_ARG, "the shape object is not an open one of this handle");
+  if (g->capacity > 0 && g->rows >= g->capacity)
+    return fail(PSTAT_ERR_TOO_SMALL, "the shape object has 0 of %lld rows free", (long long)g->capacity);
+  PSTAT_TRY(set_device(h));
+  if (h->failed_job) return report_failed_job(h);
+  return enqueue_shape(h, g);
+}
+
+int pstat_advance_shape(pstat_handle *h, pstat_shape *g, int64_t nsteps, int64_t stepout) {
+  if (!h || !g) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
+  if (!own_shape(h, g)) return fail(PSTAT_ERR_INVALID_ARG, "the shape object is not an open one of this handle");
+  if (nsteps < 0) return fail(PSTAT_ERR_INVALID_ARG, "nsteps must be >= 0");
+  if (stepout < 1) return fail(PSTAT_ERR_INVALID_ARG, "stepout must be >= 1");
+  const int64_t nrec = nsteps / stepout;
+  if (g->capacity > 0 && nrec > g->capacity - g->rows)
+    return fail(PSTAT_ERR_TOO_SMALL, "the shape object has %lld of %lld rows free, this call would record %lld",
+                (long long)(g->capacity - g->rows), (long long)g->capacity, (long long)nrec);
+  PSTAT_TRY(set_device(h));
+  if (h->failed_job) return report_failed_job(h);
+  for (int64_t i = 0; i < nrec; ++i) {
+    PSTAT_TRY(enqueue_steps(h, stepout));
+    PSTAT_TRY(enqueue_shape(h, g));
+  }
+  return enqueue_steps(h, nsteps - nrec * stepout);
+}
+
+int pstat_shape_read(pstat_handle *h, pstat_shape *g, double *sum, double *sumsq, int64_t *records) {
+  if (!h || !g) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
+  if (!own_shape(h, g)) return fail(PSTAT_ERR_INVALID_ARG, "the shape object is not an open one of this handle");
+  PSTAT_TRY(set_device(h));
+  PSTAT_TRY(sync_checked(h));
+  const size_t stride = (size_t)h->ncases * (size_t)g->args.ncols;
+  if (sum) HIP_TRY(hipMemcpy(sum, g->d_totals, stride * sizeof(double), hipMemcpyDeviceToHost));
+  if (sumsq) HIP_TRY(hipMemcpy(sumsq, g->d_totals + stride, stride * sizeof(double), hipMemcpyDeviceToHost));
+  if (records) *records = g->records;
+  return PSTAT_OK;
+}
+
+int pstat_shape_rows(pstat_handle *h, pstat_shape *g, const double **dev_rows, int64_t *nrows, int64_t *stride) {
+  if (!h || !g || !dev_rows || !nrows || !stride) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
+  if (!own_shape(h, g)) return fail(PSTAT_ERR_INVALID_ARG, "the shape object is not an open one of this handle");
+  PSTAT_TRY(set_device(h));
+  PSTAT_TRY(sync_checked(h));
+  *dev_rows = g->d_rows;
+  *nrows = g->rows;
+  *stride = (int64_t)h->ncases * g->args.ncols;
+  return PSTAT_OK;
+}
+
+int pstat_shape_clear(pstat_handle *h, pstat_shape *g) {
+  if (!h || !g) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
+  if (!own_shape(h, g)) return fail(PSTAT_ERR_INVALID_ARG, "the shape object is not an open one of this handle");
+  PSTAT_TRY(set_device(h));
+  const size_t stride = (size_t)h->ncases * (size_t)g->args.ncols;
+  HIP_TRY(hipMemsetAsync(g->d_totals, 0, 2 * stride * sizeof(double), h->stream));   // behind the records already enqueued
+  g->records = 0;
+  g->rows = 0;
+  return PSTAT_OK;
+}
+
+void pstat_shape_close(pstat_handle *h, pstat_shape *g) {
+  if (!h || !g || !own_shape(h, g)) return;
+  (void)hipSetDevice(h->device);
+  (void)hipStreamSynchronize(h->stream);   // a record may still be in flight
+  for (size_t i = 0; i < h->shapes.size(); ++i)
+    if (h->shapes[i] == g) { h->shapes.erase(h->shapes.begin() + (long)i); break; }
+  free_shape(g);
 }
 
 int pstat_sync(pstat_handle *h) {

@@ -148,7 +148,9 @@ __global__ __launch_bounds__(CTHREADS) void corr_stage1(const CorrArgs a, const 
   }
 }
 
-// wave w of the grid takes (case, column) w
+}  // namespace
+
+// wave w of the grid takes (case, column) w (declared in pstat_device.h: the shape recorder's fold is this kernel too)
 __global__ __launch_bounds__(CTHREADS) void corr_stage2(const CorrArgs a, const double *__restrict__ partial,
                                                         double *__restrict__ totals, double *__restrict__ row) {
   const int lane = threadIdx.x & 63;
@@ -170,8 +172,6 @@ __global__ __launch_bounds__(CTHREADS) void corr_stage2(const CorrArgs a, const 
     if (row) row[w] = r1 / (double)a.per;
   }
 }
-
-}  // namespace
 
 int64_t corr_max_n(int planar) { return (int64_t)((CORR_LDS - CORR_SCRATCH) / ((planar ? 2 : 3) * sizeof(double))); }
 

@@ -419,5 +419,29 @@ size_t corr_partial_doubles(const CorrArgs &a);
 // one record: totals[2][ncases][ncols] (sum, then sumsq) += this record's, row[ncases][ncols] (unless null) = the cases' means
 hipError_t launch_corr(const CorrArgs &a, const void *ang, const CaseConst *cases, double *partial, double *totals, double *row,
                        hipStream_t stream);
+// the fold over the tiles of one record (defined in pstat_corr.hip; pstat_shape.hip launches it too): one wavefront per
+// (case, column) in workgroups of 256 threads.  It reads a.ncases, a.ncols, a.tiles and a.per only; partial is
+// [ncases][tiles][sum | sumsq][ncols].
+__global__ void corr_stage2(const CorrArgs a, const double *__restrict__ partial, double *__restrict__ totals,
+                            double *__restrict__ row);
+
+// Per-case gyration tensor and form factor of the chains' current positions (pstat_shape.hip states the contract).
+struct ShapeArgs {
+  int64_t per, ncases, n;      // chains per case, cases, monomers
+  int64_t tiles;               // workgroups per case: ceil(per / tile_chains)
+  int32_t nq;                  // wave-vectors
+  int32_t ncols;               // PSTAT_SHAPE_GYR + nq
+  int32_t elem;                // bytes per stored angle of DevState::ang
+  int32_t planar;
+  int32_t tile_chains;         // chains per workgroup
+  int32_t lpc, groups, nslots; // threads per group, groups per workgroup (lpc * groups = 256), wave-vectors per thread
+};
+// fills tiles, tile_chains, lpc, groups, nslots from the other fields: the shape of the reduction, which is part of the result
+void shape_layout(ShapeArgs &a);
+size_t shape_partial_doubles(const ShapeArgs &a);
+// one record: totals[2][ncases][ncols] (sum, then sumsq) += this record's, row[ncases][ncols] (unless null) = the cases' means;
+// q = the wave-vectors [nq][3] in device memory (may be null when nq = 0)
+hipError_t launch_shape(const ShapeArgs &a, const void *ang, const CaseConst *cases, const double *q, double *partial,
+                        double *totals, double *row, hipStream_t stream);
 
 }  // namespace pstat

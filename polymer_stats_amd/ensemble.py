@@ -150,6 +150,21 @@ class Ensemble:
         """advance(nsteps) with a record into `corr` after every `stepout`-th step (asynchronous)."""
         check(self._L.pstat_advance_corr(self._h, corr._g, int(nsteps), int(stepout)))
 
+    # --- per-case gyration tensor and form factor of the monomers' positions (pstat_shape_*; DESIGN.md 3.16)
+    def open_shape(self, q=None, capacity_rows: int = 0) -> "Shape":
+        """`q`: wave-vectors in absolute units, array-like [nq, 3] (a planar handle also takes [nq, 2], mapped to the x and z
+        slots); None or empty: the gyration block only.  `capacity_rows` > 0 also keeps one row of case means per record, for
+        Shape.error_bars."""
+        qa = _shape_q(q, self.planar)
+        g = C.c_void_p()
+        check(self._L.pstat_shape_open(self._h, qa.ctypes.data_as(C.POINTER(C.c_double)) if len(qa) else None, len(qa),
+                                       int(capacity_rows), C.byref(g)))
+        return Shape(self, g, qa)
+
+    def advance_shape(self, shape: "Shape", nsteps: int, stepout: int):
+        """advance(nsteps) with a record into `shape` after every `stepout`-th step (asynchronous)."""
+        check(self._L.pstat_advance_shape(self._h, shape._g, int(nsteps), int(stepout)))
+
     # --- read-outs
     def reduce_into(self, dev_ptr: int, icase: int = -1):
         """Device-side reduction into a caller-owned device buffer of NRED doubles (async)."""
@@ -420,6 +435,102 @@ class Corr:
     def close(self):
         if self._g and self._e._h:      # (closing the ensemble closes its correlation objects)
             self._e._L.pstat_corr_close(self._e._h, self._g)
+        self._g = None
+
+
+def _shape_q(q, planar: bool) -> np.ndarray:
+    """The wave-vector table as the library takes it: float64 [nq, 3], C order."""
+    if q is None:
+        return np.zeros((0, 3))
+    a = np.asarray(q, dtype=np.float64)
+    if a.size == 0:
+        return np.zeros((0, 3))
+    if a.ndim != 2 or a.shape[1] not in ((2, 3) if planar else (3,)):
+        raise ValueError(f"q must be [nq, 3]{' or [nq, 2]' if planar else ''}, not {a.shape}")
+    if a.shape[1] == 2:                 # a planar handle's (x, z)
+        a = np.stack([a[:, 0], np.zeros(len(a)), a[:, 1]], axis=1)
+    return np.ascontiguousarray(a)
+
+
+class ShapeResult:
+    """What Shape.read returns.  `sum`, `sumsq`: the raw totals, float64 [ncases, 8 + nq], the columns SHAPE_NAMES and then one
+    per wave-vector of `q` ([nq, 3]); `records`; `mean`: sum / (records * chains per case); `chain_stderr`: the across-chain
+    standard error of that mean, defined after exactly one record (chains are independent, records of one chain are not) and
+    NaN otherwise; `gyration`: the mean tensor [ncases, 3, 3]; `rg2`: [ncases]; `sq`: the mean form factor [ncases, nq]."""
+
+    def __init__(self, q: np.ndarray, num_chains: int, planar: bool, sum_: np.ndarray, sumsq: np.ndarray, records: int):
+        self.q, self.num_chains, self.planar, self.records, self.sum, self.sumsq = q, num_chains, planar, records, sum_, sumsq
+        N = num_chains
+        with np.errstate(invalid="ignore", divide="ignore"):
+            self.mean = sum_ / (records * N) if records > 0 else np.full(sum_.shape, np.nan)
+            if records == 1 and N > 1:
+                self.chain_stderr = np.sqrt(np.maximum(sumsq / N - (sum_ / N) ** 2, 0.0) / (N - 1))
+            else:
+                self.chain_stderr = np.full(sum_.shape, np.nan)
+        m = self.mean
+        self.gyration = np.stack([np.stack([m[:, 0], m[:, 3], m[:, 4]], axis=-1), np.stack([m[:, 3], m[:, 1], m[:, 5]], axis=-1),
+                                  np.stack([m[:, 4], m[:, 5], m[:, 2]], axis=-1)], axis=1)
+        self.rg2 = m[:, 6]
+        self.sq = m[:, len(_lib.SHAPE_NAMES):]
+
+
+def shape_anisotropy(result: ShapeResult) -> np.ndarray:
+    """The relative shape anisotropy of every case as a ratio of averages, [ncases]: (3 <trg2> - <rg2^2>) / (2 <rg2^2>) for a 3D
+    handle, (2 <trg2> - <rg2^2>) / <rg2^2> for a planar one, with <rg2^2> = sumsq / (records * chains per case) of the rg2
+    column.  0 for a sphere (disc), 1 for a rod."""
+    i_rg2, i_trg2 = _lib.SHAPE_NAMES.index("rg2"), _lib.SHAPE_NAMES.index("trg2")
+    with np.errstate(invalid="ignore", divide="ignore"):
+        rg4 = result.sumsq[:, i_rg2] / (result.records * result.num_chains)
+        trg2 = result.mean[:, i_trg2]
+        return (2.0 * trg2 - rg4) / rg4 if result.planar else (3.0 * trg2 - rg4) / (2.0 * rg4)
+
+
+class Shape:
+    """Gyration tensor and form factor recorded on the device (Ensemble.open_shape, pstat_shape_*)."""
+
+    def __init__(self, ensemble: Ensemble, g, q: np.ndarray):
+        self._e, self._g, self.q = ensemble, g, q
+        self.ncols = len(_lib.SHAPE_NAMES) + len(q)
+
+    def record(self):
+        """One record of the current configuration of every chain (asynchronous)."""
+        check(self._e._L.pstat_shape_record(self._e._h, self._g))
+
+    def read(self) -> ShapeResult:
+        """Synchronises."""
+        e = self._e
+        s = np.zeros((e.ncases, self.ncols))
+        q = np.zeros((e.ncases, self.ncols))
+        records = C.c_int64(0)
+        dp = C.POINTER(C.c_double)
+        check(e._L.pstat_shape_read(e._h, self._g, s.ctypes.data_as(dp), q.ctypes.data_as(dp), C.byref(records)))
+        return ShapeResult(self.q, e.num_chains, e.planar, s, q, int(records.value))
+
+    def rows(self):
+        """(device pointer, rows, stride) of the per-record case means, a float64 matrix [rows][ncases * ncols] in device
+        memory (pstat_shape_rows).  Synchronises."""
+        e = self._e
+        ptr, nrows, stride = C.c_void_p(), C.c_int64(0), C.c_int64(0)
+        check(e._L.pstat_shape_rows(e._h, self._g, C.byref(ptr), C.byref(nrows), C.byref(stride)))
+        return ptr.value or 0, int(nrows.value), int(stride.value)
+
+    def error_bars(self, min_blocks: int = 32, levels: bool = False, device: int | None = None) -> "ErrorBars":
+        """Blocked standard errors of the recorded rows' columns (pstat_blocking_device on pstat_shape_rows): arrays of shape
+        [ncases, ncols].  Needs capacity_rows > 0 at open_shape and at least `min_blocks` records.  Synchronises."""
+        e = self._e
+        ptr, nrows, stride = self.rows()
+        dev = int(e.cases[0].device) if device is None else int(device)
+        eb = blocking_device(ptr, nrows, stride, stride, min_blocks=min_blocks, levels=levels, device=dev)
+        out = np.stack([eb.mean, eb.stderr, eb.stderr_err, eb.inefficiency, eb.level.astype(float), eb.converged.astype(float)], axis=-1)
+        lev = eb.levels.reshape(e.ncases, self.ncols, -1) if levels else None
+        return ErrorBars(out.reshape(e.ncases, self.ncols, -1), nrows, lev)
+
+    def clear(self):
+        check(self._e._L.pstat_shape_clear(self._e._h, self._g))
+
+    def close(self):
+        if self._g and self._e._h:      # (closing the ensemble closes its shape objects)
+            self._e._L.pstat_shape_close(self._e._h, self._g)
         self._g = None
 
 

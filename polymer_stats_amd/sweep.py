@@ -45,6 +45,7 @@ from ._host import ReferenceError_, arith, error_lines, fresh_seed, number
 from ._host import check_error_bars as _host_check_error_bars
 from ._host import check_hist as _host_check_hist, hist_lines, parse_hist
 from ._host import check_corr as _host_check_corr, corr_lines, parse_corr
+from ._host import check_shape as _host_check_shape, parse_shape, shape_lines
 
 # (the planar main: 2D/run/Ising_2024-11-06.jl and its siblings launch 2D/mcmc_clustering_eap_chain.jl the same way)
 MAINS = {"mcmc_eap_chain": fixed_main, "mcmc_clustering_eap_chain": cluster_main, "mcmc_clustering_eap_chain_2d": planar_main}
@@ -231,6 +232,25 @@ def check_corr(main_name: str, fixed_argv: list[str], corr: str, cases: list[dic
     return spec
 
 
+def check_shape(main_name: str, fixed_argv: list[str], shape: str, cases: list[dict], write_csv: bool = False, world: int = 1,
+                error_bars: int = 0, hist=None, corr=None):
+    """--shape of tools/run_sweep.py: parses it and refuses what it cannot be combined with (_host.check_shape, and more than one
+    rank), judged from the options every case shares and from every chain and monomer length among the cases; no GPU is touched.
+    Returns parse_shape's spec."""
+    spec = parse_shape(shape)
+    if world > 1:
+        raise ReferenceError_(f"--shape needs one device, not --gpus {world}")
+    main = MAINS[main_name]
+    if main is planar_main and any(v[1] != 0.0 for v in spec[1]):
+        raise ReferenceError_("--shape: the planar main's chains lie in the x-z plane: no wave-vectors along y")
+    sizes = {}
+    for case in cases or [{}]:
+        sizes.setdefault(repr((case.get("n", case.get("num-monomers")), case.get("b", case.get("mlen")))), case)
+    for case in sizes.values():
+        _host_check_shape(main.parse_args(list(fixed_argv) + case_argv(case)), spec, write_csv, error_bars=error_bars, hist=hist, corr=corr)
+    return spec
+
+
 def _signature(pargs: dict):
     return tuple(sorted((k, repr(v)) for k, v in pargs.items() if k not in PER_CASE and not k.startswith("_")))
 
@@ -238,7 +258,7 @@ def _signature(pargs: dict):
 def run_sweep(main_name: str, fixed_argv: list[str], cases: list[dict], workdir: str, *, name=None, num_chains: int = 64,
               seed: int | None = None, precision: str | None = None, rng: str | None = None, rank: int = 0, world: int = 1,
               device: int = 0, overwrite: bool = False, write_csv: bool = False, max_chains: int = 262144, log=None,
-              error_bars: int = 0, hist=None, corr=None) -> dict:
+              error_bars: int = 0, hist=None, corr=None, shape=None) -> dict:
     """Runs the cases whose `.out` does not exist yet (run/interacting_dielectric_study.jl:39) and that fall to this rank
     (position in the full case list modulo `world`).  `write_csv` also writes every case's two time-series files (rows
     recorded on the device for the whole ensemble, _Pool.recorded).  `error_bars` = N: the production run is recorded as N batches
@@ -246,19 +266,24 @@ def run_sweep(main_name: str, fixed_argv: list[str], cases: list[dict], workdir:
     .out files are those of a run without it, and a case whose .err is missing is run again.  `hist` = ["CHANNEL:LO:HI:NBINS", ...]:
     every chain is histogrammed every --stepout steps of the production run and every `<case>.out` gets a `<case>.hist` beside it
     (_host.hist_lines), under the same two rules.  `corr` = "MAXLAG[:nn,zz,mm]": the lag correlations are recorded every --stepout
-    steps of the production run and every `<case>.out` gets a `<case>.corr` beside it (_host.corr_lines), likewise.  Returns {"ran": [...], "skipped": [...], "launches": k}."""
+    steps of the production run and every `<case>.out` gets a `<case>.corr` beside it (_host.corr_lines), likewise.  `shape` = "[AXIS:QMAX:NQ,...]"
+    ("" for the gyration block alone; None: no shape): the gyration tensor and the form factor at those wave-vectors, recorded the
+    same way, in a `<case>.shape` (_host.shape_lines).  Returns {"ran": [...], "skipped": [...], "launches": k}."""
     main = MAINS[main_name]
     if error_bars:
         check_error_bars(main_name, fixed_argv, error_bars, write_csv=write_csv, world=world)
     specs = check_hist(main_name, fixed_argv, list(hist), write_csv=write_csv, world=world, error_bars=error_bars) if hist else None
     cspec = check_corr(main_name, fixed_argv, corr, cases, write_csv=write_csv, world=world, error_bars=error_bars, hist=hist) if corr else None
+    sspec = check_shape(main_name, fixed_argv, shape, cases, write_csv=write_csv, world=world, error_bars=error_bars, hist=hist,
+                        corr=corr) if shape is not None else None
     os.makedirs(workdir, exist_ok=True)
     todo_all = plan(main_name, fixed_argv, cases, workdir, name=name, num_chains=num_chains, seed=seed, precision=precision,
                     rng=rng, device=device)
     # with error bars a case is complete when its .err is there too (a directory first swept without them: run again)
     beside = lambda p, ext: p["_out"][:-len(".out")] + ext
     done = lambda p: (os.path.isfile(p["_out"]) and (not error_bars or os.path.isfile(beside(p, ".err")))
-                      and (not specs or os.path.isfile(beside(p, ".hist"))) and (not cspec or os.path.isfile(beside(p, ".corr"))))
+                      and (not specs or os.path.isfile(beside(p, ".hist"))) and (not cspec or os.path.isfile(beside(p, ".corr")))
+                      and (not sspec or os.path.isfile(beside(p, ".shape"))))
     skipped = [p["_name"] for p in todo_all if done(p) and not overwrite]
     todo = [p for p in todo_all if overwrite or not done(p)]
     mine = [p for p in todo if p["_index"] % world == rank]     # by position in the full list: ranks need not agree on what is done
@@ -274,7 +299,8 @@ def run_sweep(main_name: str, fixed_argv: list[str], cases: list[dict], workdir:
             info = {}
             # the main's own protocol, every case of the ensemble at once
             res = main.run_cases(plist, write_csv=write_csv, info=info, **({"error_bars": error_bars} if error_bars else {}),
-                                 **({"hist": specs} if specs else {}), **({"corr": cspec} if cspec else {}))
+                                 **({"hist": specs} if specs else {}), **({"corr": cspec} if cspec else {}),
+                                 **({"shape": sspec} if sspec else {}))
             for k, (p, (sas, vas, ar)) in enumerate(zip(plist, res)):
                 texts = [(p["_out"], main.summary_lines(sas, vas, ar, p))]      # println x 10 (12)
                 if error_bars:      # (first: a case whose .out is there is complete)
@@ -283,6 +309,8 @@ def run_sweep(main_name: str, fixed_argv: list[str], cases: list[dict], workdir:
                     texts.insert(0, (beside(p, ".hist"), hist_lines(info["hist"], specs, k, int(num_chains))))
                 if cspec:
                     texts.insert(0, (beside(p, ".corr"), corr_lines(*info["corr"], k)))
+                if sspec:
+                    texts.insert(0, (beside(p, ".shape"), shape_lines(*info["shape"], k)))
                 for path, lines in texts:           # complete or absent: an interrupted sweep re-runs the case
                     tmp = path + f".tmp{os.getpid()}"
                     with open(tmp, "w") as f:

@@ -75,6 +75,13 @@ def main():
                          "<case>.out a <case>.corr: CSV k,<ch>,<ch>_stderr,... with the blocked standard errors of the records (at least "
                          "32 records).  Default channel: nn.  Refused where --hist is, with it and with --error-bars; the .out files stay "
                          "byte for byte a plain run's, at the same doubled production time")
+    ap.add_argument("--shape", nargs="?", const="", default=None, metavar="AXIS:QMAX:NQ[,AXIS:QMAX:NQ...]",
+                    help="record the gyration tensor of EVERY chain (gxx gyy gzz gxy gxz gyz rg2 trg2) and its form factor S(q) at NQ "
+                         "wave-vectors QMAX (1 .. NQ) / NQ along AXIS (x, y or z) per entry, every --stepout steps of the production "
+                         "run, on the device, and write next to every <case>.out a <case>.shape: CSV name,qx,qy,qz,value,stderr with "
+                         "the blocked standard errors of the records (at least 32 records).  A bare --shape records the gyration "
+                         "block only.  Refused where --corr is, and with it; the .out files stay byte for byte a plain run's, at the "
+                         "same doubled production time")
     ap.add_argument("--max-chains", type=int, default=262144, help="chains per launch (cases per ensemble = this / num-chains)")
     ap.add_argument("--dry-run", action="store_true", help="print the plan (cases, file names, ensembles) and stop: no GPU needed")
     ap.add_argument("--aggregate", default="", help="afterwards write scripts/aggregate_mcmc.jl's CSV of the whole directory here")
@@ -108,6 +115,12 @@ def main():
         try:
             sw.check_corr(args.main, fixed, args.corr, cases, write_csv=args.csv, world=args.gpus, error_bars=args.error_bars,
                           hist=args.hist)
+        except sw.ReferenceError_ as e:
+            raise SystemExit(str(e))
+    if args.shape is not None:
+        try:
+            sw.check_shape(args.main, fixed, args.shape, cases, write_csv=args.csv, world=args.gpus, error_bars=args.error_bars,
+                           hist=args.hist, corr=args.corr)
         except sw.ReferenceError_ as e:
             raise SystemExit(str(e))
     if args.dry_run:
@@ -168,7 +181,7 @@ def main():
     res = sw.run_sweep(args.main, fixed, cases, args.workdir, name=args.name or None, num_chains=args.num_chains, seed=args.seed,
                        precision=args.precision, rng=args.rng, rank=rank, world=world, device=local % ndev,
                        overwrite=args.overwrite, write_csv=args.csv, max_chains=args.max_chains, error_bars=args.error_bars, **({"hist": args.hist} if args.hist else {}),
-                       **({"corr": args.corr} if args.corr else {}),
+                       **({"corr": args.corr} if args.corr else {}), **({"shape": args.shape} if args.shape is not None else {}),
                        log=lambda m: print("# " + m, file=sys.stderr, flush=True))
     print(f"# rank {rank} of {world}: {len(res['ran'])} cases run in {res['launches']} ensembles, {len(res['skipped'])} already "
           f"there; {time.time() - t0:.2f} s", file=sys.stderr, flush=True)
