@@ -239,11 +239,43 @@ def parse_hist(text: str):
     return parts[0], lo, hi, nbins
 
 
+# What --hist, --corr and --shape record, in the words of their refusals: (the production run is recorded as ..., the devices
+# do not merge their ..., a re-initialisation falls between ..., the weights' gauge is not held by the ..., why float64 only)
+_RECORDER_WORDS = {
+    "--hist": ("histograms", "histograms", "samples", "counts", "the samples are the device's Float64 microstates"),
+    "--corr": ("correlations", "sums", "records", "sums", "like --hist it is offered for float64 runs only"),
+    "--shape": ("shape columns", "sums", "records", "sums", "like --hist it is offered for float64 runs only"),
+}
+
+
+def _check_recorder(flag: str, pargs: dict, write_csv: bool, devices: int | None, rivals: dict):
+    """The combinations that --hist, --corr and --shape (`flag`) all refuse, for the reasons --error-bars has
+    (check_error_bars): first the `rivals`, {flag: whether it is given}, that record the production run themselves."""
+    recorded_as, merged, between, held_by, float64_only = _RECORDER_WORDS[flag]
+    if devices is None:
+        devices = len([d for d in str(pargs["devices"]).split(",") if d != ""][:max(1, int(pargs["num-chains"]))])
+    for rival, given in rivals.items():
+        if given:
+            raise ReferenceError_(f"{flag} cannot be combined with {rival}: each records the production run in its own way")
+    if write_csv:
+        raise ReferenceError_(f"{flag} cannot be combined with --csv: the production run is recorded as {recorded_as}, not as "
+                              "--stepout rows")
+    if devices > 1:
+        raise ReferenceError_(f"{flag} needs one device, not {devices}: the devices hold different chains of a case and "
+                              f"their {merged} are not merged")
+    if int(pargs.get("num-inits", 1)) != 1:
+        raise ReferenceError_(f"{flag} cannot be combined with --num-inits {pargs['num-inits']}: a re-initialisation "
+                              f"between {between} is not a stationary series")
+    if pargs["umbrella-sampling"]:
+        raise ReferenceError_(f"{flag} cannot be combined with --umbrella-sampling: the samples carry per-chain weights whose "
+                              f"gauge the {held_by} do not hold")
+    if pargs["numeric-type"] != "float64":
+        raise ReferenceError_(f"{flag} cannot be combined with --numeric-type {pargs['numeric-type']}: {float64_only}")
+
+
 def check_hist(pargs: dict, specs, write_csv: bool = False, devices: int | None = None, error_bars: int = 0):
     """What --hist (tools/run_sweep.py; run_cases(..., hist=[...])) cannot be combined with, refused before any GPU work: what
     --error-bars cannot, for the same reasons (check_error_bars), and --error-bars itself."""
-    if devices is None:
-        devices = len([d for d in str(pargs["devices"]).split(",") if d != ""][:max(1, int(pargs["num-chains"]))])
     if not 1 <= len(specs) <= _lib.HIST_MAX_SPECS:
         raise ReferenceError_(f"--hist: between 1 and {_lib.HIST_MAX_SPECS} histograms, not {len(specs)}")
     if sum(s[3] for s in specs) > _lib.HIST_MAX_BINS:
@@ -252,23 +284,7 @@ def check_hist(pargs: dict, specs, write_csv: bool = False, devices: int | None 
     if not 1 <= stepout <= int(pargs["num-steps"]):
         raise ReferenceError_(f"--hist samples every --stepout steps of the production run: --stepout {stepout} must be in 1 .. "
                               f"--num-steps {pargs['num-steps']}")
-    if error_bars:
-        raise ReferenceError_("--hist cannot be combined with --error-bars: each records the production run in its own way")
-    if write_csv:
-        raise ReferenceError_("--hist cannot be combined with --csv: the production run is recorded as histograms, not as "
-                              "--stepout rows")
-    if devices > 1:
-        raise ReferenceError_(f"--hist needs one device, not {devices}: the devices hold different chains of a case and "
-                              "their histograms are not merged")
-    if int(pargs.get("num-inits", 1)) != 1:
-        raise ReferenceError_(f"--hist cannot be combined with --num-inits {pargs['num-inits']}: a re-initialisation "
-                              "between samples is not a stationary series")
-    if pargs["umbrella-sampling"]:
-        raise ReferenceError_("--hist cannot be combined with --umbrella-sampling: the samples carry per-chain weights whose "
-                              "gauge the counts do not hold")
-    if pargs["numeric-type"] != "float64":
-        raise ReferenceError_(f"--hist cannot be combined with --numeric-type {pargs['numeric-type']}: the samples are the "
-                              "device's Float64 microstates")
+    _check_recorder("--hist", pargs, write_csv, devices, {"--error-bars": error_bars})
 
 
 CORR_MIN_RECORDS = 32      # the blocking transform's default min_blocks: a .corr's standard errors need that many records
@@ -293,34 +309,19 @@ def check_corr(pargs: dict, spec, write_csv: bool = False, devices: int | None =
     work: what --hist cannot, for the same reasons (check_hist), --hist itself, a lag beyond n - 1 and a run of fewer records
     than the blocked standard errors need."""
     max_lag = spec[0]
-    if devices is None:
-        devices = len([d for d in str(pargs["devices"]).split(",") if d != ""][:max(1, int(pargs["num-chains"]))])
     if max_lag > int(pargs["num-monomers"]) - 1:
         raise ReferenceError_(f"--corr: lag {max_lag} is beyond n - 1 = {int(pargs['num-monomers']) - 1}")
+    _check_records("--corr", pargs)
+    _check_recorder("--corr", pargs, write_csv, devices, {"--error-bars": error_bars, "--hist": hist})
+
+
+def _check_records(flag: str, pargs: dict):
+    """--corr and --shape (`flag`) keep a row per record: the run must give the blocking transform enough of them."""
     stepout = int(pargs["stepout"])
     if not 1 <= stepout <= int(pargs["num-steps"]) or int(pargs["num-steps"]) // stepout < CORR_MIN_RECORDS:
-        raise ReferenceError_(f"--corr takes a record every --stepout steps of the production run and its standard errors from "
+        raise ReferenceError_(f"{flag} takes a record every --stepout steps of the production run and its standard errors from "
                               f"at least {CORR_MIN_RECORDS} of them: --stepout {stepout} must be in 1 .. --num-steps "
                               f"{pargs['num-steps']} / {CORR_MIN_RECORDS}")
-    if error_bars:
-        raise ReferenceError_("--corr cannot be combined with --error-bars: each records the production run in its own way")
-    if hist:
-        raise ReferenceError_("--corr cannot be combined with --hist: each records the production run in its own way")
-    if write_csv:
-        raise ReferenceError_("--corr cannot be combined with --csv: the production run is recorded as correlations, not as "
-                              "--stepout rows")
-    if devices > 1:
-        raise ReferenceError_(f"--corr needs one device, not {devices}: the devices hold different chains of a case and "
-                              "their sums are not merged")
-    if int(pargs.get("num-inits", 1)) != 1:
-        raise ReferenceError_(f"--corr cannot be combined with --num-inits {pargs['num-inits']}: a re-initialisation "
-                              "between records is not a stationary series")
-    if pargs["umbrella-sampling"]:
-        raise ReferenceError_("--corr cannot be combined with --umbrella-sampling: the samples carry per-chain weights whose "
-                              "gauge the sums do not hold")
-    if pargs["numeric-type"] != "float64":
-        raise ReferenceError_(f"--corr cannot be combined with --numeric-type {pargs['numeric-type']}: like --hist it is offered "
-                              "for float64 runs only")
 
 
 def parse_shape(text: str):
@@ -350,10 +351,8 @@ def check_shape(pargs: dict, spec, write_csv: bool = False, devices: int | None 
     work: what --corr cannot, for the same reasons (check_corr), --corr itself, and a wave-vector whose phase the library refuses."""
     if corr:
         raise ReferenceError_("--shape cannot be combined with --corr: each records the production run in its own way")
-    try:
-        check_corr(pargs, (0, ("nn",)), write_csv, devices=devices, error_bars=error_bars, hist=hist)
-    except ReferenceError_ as e:
-        raise ReferenceError_(str(e).replace("--corr", "--shape").replace("as correlations", "as shape columns"))
+    _check_records("--shape", pargs)
+    _check_recorder("--shape", pargs, write_csv, devices, {"--error-bars": error_bars, "--hist": hist})
     reach = float(pargs["mlen"]) * int(pargs["num-monomers"])
     for v in spec[1]:
         if sum(abs(c) for c in v) * reach >= 1.0e5:
@@ -423,6 +422,11 @@ def _averagers(s):
 
 
 # ---------------------------------------------------------------------------------------------- the pool
+def _totals_and_error_bars(g):
+    """What a Corr or a Shape with kept rows gives at the end of a recorded run."""
+    return g.read(), g.error_bars(min_blocks=CORR_MIN_RECORDS)
+
+
 class _Pool:
     """The cases of one ensemble -- one for the command line, many for a sweep (polymer_stats_amd/sweep.py; they differ only
     in their physics scalars, pstat_create) --, every case's chains sharded over one or more devices in this process;
@@ -558,70 +562,58 @@ class _Pool:
         a run without error bars does.  (Recording leaves trajectories alone, but N launches add the running sums in another
         order than one launch: the step kernels fold them in blocks that start at a launch's first step.)"""
         check_error_bars(self.plist[0], nbatches, devices=len(self.parts))
+        return self._recorded_twice(nsteps, nbatches, nsteps // nbatches, lambda e: e.open_series(nbatches), Ensemble.advance_series,
+                                    lambda series: series.error_bars(), restore_after_failure=False)
+
+    def _recorded_twice(self, nsteps, nrec, stepout, open_, advance, read, restore_after_failure=True):
+        """advance(nsteps), made TWICE from the same state, as error_bars explains: first `nrec` records `stepout` steps apart
+        (the remainder would be lost with the restore anyway) into the recorder that `open_(ensemble)` opens, by
+        `advance(ensemble, recorder, nsteps, stepout)`; then, from a checkpoint taken before it, as the one launch of
+        advance(nsteps).  Returns `read(recorder)`.  The recorder is closed whatever happens; the checkpoint is put back also when
+        the recorded run failed, so that the handle is never left mid-run (error_bars alone leaves a failed run where it stopped)."""
         e = self.parts[0]
         image = e.checkpoint()
-        series = e.open_series(nbatches)
+        recorder = open_(e)
+        done = False
         try:
-            q = nsteps // nbatches
-            e.advance_series(series, nbatches * q, q)      # (the remainder would be lost with the restore anyway)
-            eb = series.error_bars()
+            advance(e, recorder, nrec * stepout, stepout)
+            res = read(recorder)
+            done = True
         finally:
-            series.close()
-        e.restore(image)
+            recorder.close()
+            if done or restore_after_failure:
+                e.restore(image)
         self.advance(nsteps)
-        return eb
+        return res
 
     def histograms(self, nsteps, stepout, specs):
         """advance(nsteps) with every chain's configuration added, after every `stepout`-th step, to the histograms `specs`
         ((channel name, lo, hi, nbins), shared by all cases) on the device -> HistResult.  Made TWICE from the same state like
-        error_bars, and for the same reason: recorded, then, from a checkpoint taken before it, as the one launch of
-        advance(nsteps), so that the averages the caller prints are exactly those of a run without histograms."""
+        error_bars, and for the same reason, so that the averages the caller prints are exactly those of a run without
+        histograms."""
         check_hist(self.plist[0], specs, devices=len(self.parts))
-        e = self.parts[0]
-        image = e.checkpoint()
-        h = e.open_hist([_lib.hist_spec(channel, nbins, lo, hi) for channel, lo, hi, nbins in specs])
-        try:
-            e.advance_hist(h, (nsteps // stepout) * stepout, stepout)      # (the remainder would be lost with the restore anyway)
-            res = h.read()
-        finally:
-            h.close()
-            e.restore(image)      # also when the recorded run failed: the handle is never left mid-run
-        self.advance(nsteps)
-        return res
+        return self._recorded_twice(
+            nsteps, nsteps // stepout, stepout,
+            lambda e: e.open_hist([_lib.hist_spec(channel, nbins, lo, hi) for channel, lo, hi, nbins in specs]),
+            Ensemble.advance_hist, lambda h: h.read())
 
     def correlations(self, nsteps, stepout, spec):
         """advance(nsteps) with one record of the lag correlations `spec` = (max_lag, channel names) after every `stepout`-th
         step, rows kept -> (CorrResult, ErrorBars of the rows).  Made TWICE from the same state like histograms, and for the
         same reason."""
         check_corr(self.plist[0], spec, devices=len(self.parts))
-        e = self.parts[0]
-        image = e.checkpoint()
-        g = e.open_corr(spec[1], spec[0], capacity_rows=nsteps // stepout)
-        try:
-            e.advance_corr(g, (nsteps // stepout) * stepout, stepout)      # (the remainder would be lost with the restore anyway)
-            res = g.read(), g.error_bars(min_blocks=CORR_MIN_RECORDS)
-        finally:
-            g.close()
-            e.restore(image)      # also when the recorded run failed: the handle is never left mid-run
-        self.advance(nsteps)
-        return res
+        nrec = nsteps // stepout
+        return self._recorded_twice(nsteps, nrec, stepout, lambda e: e.open_corr(spec[1], spec[0], capacity_rows=nrec),
+                                    Ensemble.advance_corr, _totals_and_error_bars)
 
     def shapes(self, nsteps, stepout, spec):
         """advance(nsteps) with one record of the gyration block and of S at the wave-vectors of `spec` = parse_shape(...) after
         every `stepout`-th step, rows kept -> (ShapeResult, ErrorBars of the rows).  Made TWICE from the same state like
         correlations, and for the same reason."""
         check_shape(self.plist[0], spec, devices=len(self.parts))
-        e = self.parts[0]
-        image = e.checkpoint()
-        g = e.open_shape(spec[1], capacity_rows=nsteps // stepout)
-        try:
-            e.advance_shape(g, (nsteps // stepout) * stepout, stepout)      # (the remainder would be lost with the restore anyway)
-            res = g.read(), g.error_bars(min_blocks=CORR_MIN_RECORDS)
-        finally:
-            g.close()
-            e.restore(image)      # also when the recorded run failed: the handle is never left mid-run
-        self.advance(nsteps)
-        return res
+        nrec = nsteps // stepout
+        return self._recorded_twice(nsteps, nrec, stepout, lambda e: e.open_shape(spec[1], capacity_rows=nrec),
+                                    Ensemble.advance_shape, _totals_and_error_bars)
 
     def chain0(self, k=0):
         return self.parts[0].chain_state(k * self.counts[0])      # the first chain of case k

@@ -85,7 +85,27 @@ Overrides read_overrides() {
   return o;
 }
 
+// Device memory that goes with its owner: the scratch of one call, or a member of a recorder object.
+template <class T>
+struct DeviceMem {
+  T *p = nullptr;
+  DeviceMem() = default;
+  DeviceMem(const DeviceMem &) = delete;
+  DeviceMem &operator=(const DeviceMem &) = delete;
+  ~DeviceMem() { (void)hipFree(p); }
+  hipError_t malloc(size_t count) { return hipMalloc((void **)&p, count * sizeof(T)); }
+  int alloc(size_t count) {
+    hipError_t e = malloc(count);
+    if (e != hipSuccess) return fail(PSTAT_ERR_NOMEM, "hipMalloc(%zu) failed: %s", count * sizeof(T), hipGetErrorString(e));
+    return PSTAT_OK;
+  }
+};
+using DeviceDoubles = DeviceMem<double>;
+
 }  // namespace
+
+template <class T>
+using OpenList = std::vector<std::unique_ptr<T>>;   // deleting the handle, or erasing an entry, frees the object
 
 struct pstat_handle {
   pstat_params base{};              // case 0's parameters (shared, non-physics fields)
@@ -110,19 +130,21 @@ struct pstat_handle {
   int64_t step_in_init = 0;         // the reference's loop variable `step` (mcmc_eap_chain.jl:276)
   size_t elem = 4;                  // sizeof(R)
   int failed_job = 0;               // sticky: 1 + the job of a persistent launch that timed out (0 = none)
-  std::vector<pstat_series *> series;   // series still open (pstat_destroy closes them)
-  std::vector<pstat_tempering *> tempering;   // tempering objects still open (likewise)
-  std::vector<pstat_hist *> hists;      // histograms still open (likewise)
-  std::vector<pstat_corr *> corrs;      // correlation objects still open (likewise)
-  std::vector<pstat_shape *> shapes;    // shape objects still open (likewise)
+  OpenList<pstat_series> series;        // the recorder objects still open
+  OpenList<pstat_tempering> tempering;
+  OpenList<pstat_hist> hists;
+  OpenList<pstat_corr> corrs;
+  OpenList<pstat_shape> shapes;
 };
+
+// ---- the recorder objects of a handle.  Each owns its device memory; the handle owns those that are open.
 
 // The stepout time series of one handle: rows recorded on the device by launch_record, read back in bulk.
 struct pstat_series {
   int64_t capacity = 0, rows = 0;
-  double *d_red = nullptr;          // [capacity][ncases][PSTAT_NRED]
-  double *d_micro = nullptr;        // [capacity][ncases][7]
-  double *d_angles = nullptr;       // [capacity][ncases][2n], PSTAT_SERIES_ANGLES only
+  DeviceDoubles d_red;              // [capacity][ncases][PSTAT_NRED]
+  DeviceDoubles d_micro;            // [capacity][ncases][7]
+  DeviceDoubles d_angles;           // [capacity][ncases][2n], PSTAT_SERIES_ANGLES only
   std::vector<int64_t> steps;       // [capacity]: the handle's steps_recorded at each row (known when the row is enqueued)
 };
 
@@ -131,39 +153,40 @@ struct pstat_tempering {
   uint64_t seed = 0;
   uint64_t round = 0;               // the next round's t; 32 bits on the device
   int64_t npairs[2] = {0, 0};       // pairs of the even and of the odd rounds
-  int32_t *d_pairs[2] = {nullptr, nullptr};   // [npairs][2] = (lower, upper rung's case)
-  unsigned char *d_flags = nullptr; // [max npairs * chains per case]
-  int64_t *d_counts = nullptr;      // [2][ncases]: attempted, accepted, on the lower rung's case
+  DeviceMem<int32_t> d_pairs[2];    // [npairs][2] = (lower, upper rung's case)
+  DeviceMem<unsigned char> d_flags; // [max npairs * chains per case]
+  DeviceMem<int64_t> d_counts;      // [2][ncases]: attempted, accepted, on the lower rung's case
 };
 
 // Per-case histograms of one handle (pstat_hist.hip).
 struct pstat_hist {
   int32_t nspecs = 0, total_bins = 0, per_case = 0;
   int64_t records = 0;              // records enqueued since open / the last clear (known when a record is enqueued)
-  HistSpec *d_specs = nullptr;      // [ncases][nspecs] if per_case, else [nspecs]
-  int64_t *d_counts = nullptr;      // [ncases][total_bins], then tails [ncases][nspecs][3]
+  DeviceMem<HistSpec> d_specs;      // [ncases][nspecs] if per_case, else [nspecs]
+  DeviceMem<int64_t> d_counts;      // [ncases][total_bins], then tails [ncases][nspecs][3]
   size_t slots = 0;                 // int64 words of d_counts
 };
 
-// Per-case lag correlations of one handle (pstat_corr.hip; DESIGN.md 3.15).
-struct pstat_corr {
-  CorrArgs args{};
+// What the correlation and the shape recorder share: per-case column totals, summed over the chains of every record.
+struct ColumnTotals {
+  size_t stride = 0;                // ncases * ncols: doubles of one row
   int64_t records = 0;              // records enqueued since open / the last clear (known when a record is enqueued)
   int64_t capacity = 0, rows = 0;   // rows kept (0: totals only) and taken
-  double *d_totals = nullptr;       // [2][ncases][ncols]: sum, sumsq
-  double *d_partial = nullptr;      // corr_partial_doubles(args): the tiles' partial sums of one record
-  double *d_rows = nullptr;         // [capacity][ncases][ncols]
+  DeviceDoubles d_totals;           // [2][ncases][ncols]: sum, sumsq
+  DeviceDoubles d_partial;          // the tiles' partial sums of one record
+  DeviceDoubles d_rows;             // [capacity][ncases][ncols]
+  double *next_row() const { return capacity > 0 ? d_rows.p + (size_t)rows * stride : nullptr; }
+};
+
+// Per-case lag correlations of one handle (pstat_corr.hip; DESIGN.md 3.15).
+struct pstat_corr : ColumnTotals {
+  CorrArgs args{};
 };
 
 // Per-case gyration tensor and form factor of one handle (pstat_shape.hip).
-struct pstat_shape {
+struct pstat_shape : ColumnTotals {
   ShapeArgs args{};
-  int64_t records = 0;              // records enqueued since open / the last clear (known when a record is enqueued)
-  int64_t capacity = 0, rows = 0;   // rows kept (0: totals only) and taken
-  double *d_q = nullptr;            // [nq][3]: the wave-vectors
-  double *d_totals = nullptr;       // [2][ncases][ncols]: sum, sumsq
-  double *d_partial = nullptr;      // shape_partial_doubles(args): the tiles' partial sums of one record
-  double *d_rows = nullptr;         // [capacity][ncases][ncols]
+  DeviceDoubles d_q;                // [nq][3]: the wave-vectors
 };
 
 namespace {
@@ -595,44 +618,83 @@ int enqueue_steps(pstat_handle *h, int64_t nsteps) {
   return PSTAT_OK;
 }
 
-// the series if it is one of the handle's open ones
-pstat_series *own_series(pstat_handle *h, pstat_series *s) {
-  for (pstat_series *mine : h->series)
-    if (mine == s) return s;
-  return nullptr;
+// ---- the recorder lifecycle: the rules every kind of recorder object follows, each stated here once
+
+template <class T>
+bool owns(const OpenList<T> &list, const T *p) {
+  for (const auto &mine : list)
+    if (mine.get() == p) return true;
+  return false;
 }
 
-void free_series(pstat_series *s) {
-  (void)hipFree(s->d_red);
-  (void)hipFree(s->d_micro);
-  (void)hipFree(s->d_angles);
-  delete s;
+// What every entry point that takes an object tests first: the arguments (`others`: its further pointers that must not be
+// null), then that `p` is one of the handle's open objects; `not_open` is the kind's message.  Touches no device.
+template <class T>
+int check_open(pstat_handle *h, OpenList<T> pstat_handle::*list, const T *p, bool others, const char *not_open) {
+  if (!h || !p || !others) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
+  if (!owns(h->*list, p)) return fail(PSTAT_ERR_INVALID_ARG, "%s", not_open);
+  return PSTAT_OK;
 }
 
-pstat_tempering *own_tempering(pstat_handle *h, pstat_tempering *t) {
-  for (pstat_tempering *mine : h->tempering)
-    if (mine == t) return t;
-  return nullptr;
+int open_series(pstat_handle *h, const pstat_series *s, bool others = true) {
+  return check_open(h, &pstat_handle::series, s, others, "the series is not an open series of this handle");
+}
+int open_tempering(pstat_handle *h, const pstat_tempering *t) {
+  return check_open(h, &pstat_handle::tempering, t, true, "the tempering object is not an open one of this handle");
+}
+int open_hist(pstat_handle *h, const pstat_hist *g) {
+  return check_open(h, &pstat_handle::hists, g, true, "the histogram is not an open histogram of this handle");
+}
+int open_corr(pstat_handle *h, const pstat_corr *g, bool others = true) {
+  return check_open(h, &pstat_handle::corrs, g, others, "the correlation object is not an open one of this handle");
+}
+int open_shape(pstat_handle *h, const pstat_shape *g, bool others = true) {
+  return check_open(h, &pstat_handle::shapes, g, others, "the shape object is not an open one of this handle");
 }
 
-void free_tempering(pstat_tempering *t) {
-  (void)hipFree(t->d_pairs[0]);
-  (void)hipFree(t->d_pairs[1]);
-  (void)hipFree(t->d_flags);
-  (void)hipFree(t->d_counts);
-  delete t;
+// The end of every pstat_X_open: the handle takes the finished object and the caller gets its address.
+template <class T>
+int adopt(OpenList<T> &list, std::unique_ptr<T> &p, T **out) {
+  T *const raw = p.get();
+  try {
+    list.push_back(std::move(p));   // (a push_back that throws leaves p alone, and the caller's return frees the object)
+  } catch (const std::bad_alloc &) {
+    return fail(PSTAT_ERR_NOMEM, "host allocation failed");
+  }
+  *out = raw;
+  return PSTAT_OK;
 }
 
-pstat_hist *own_hist(pstat_handle *h, pstat_hist *g) {
-  for (pstat_hist *mine : h->hists)
-    if (mine == g) return g;
-  return nullptr;
+// Every pstat_X_close: an object that is not one of the handle's open ones is left alone.
+template <class T>
+void close_object(pstat_handle *h, OpenList<T> pstat_handle::*list, const T *p) {
+  if (!h || !p || !owns(h->*list, p)) return;
+  (void)hipSetDevice(h->device);
+  (void)hipStreamSynchronize(h->stream);   // a record (row, round) may still be in flight
+  OpenList<T> &open = h->*list;
+  for (size_t i = 0; i < open.size(); ++i)
+    if (open[i].get() == p) { open.erase(open.begin() + (long)i); break; }
 }
 
-void free_hist(pstat_hist *g) {
-  (void)hipFree(g->d_specs);
-  (void)hipFree(g->d_counts);
-  delete g;
+// Every pstat_advance_X: advance(nsteps) with one record after every `stepout`-th step; the remainder is advanced without
+// one.  `capacity` > 0: the object keeps a row per record and has `rows` of them taken; a call that would overflow is refused
+// before anything is enqueued.  `record` enqueues one record and returns a status.
+template <class Record>
+int advance_recording(pstat_handle *h, int64_t nsteps, int64_t stepout, int64_t capacity, int64_t rows, const char *noun,
+                      Record record) {
+  if (nsteps < 0) return fail(PSTAT_ERR_INVALID_ARG, "nsteps must be >= 0");
+  if (stepout < 1) return fail(PSTAT_ERR_INVALID_ARG, "stepout must be >= 1");
+  const int64_t nrec = nsteps / stepout;
+  if (capacity > 0 && nrec > capacity - rows)
+    return fail(PSTAT_ERR_TOO_SMALL, "the %s has %lld of %lld rows free, this call would record %lld", noun,
+                (long long)(capacity - rows), (long long)capacity, (long long)nrec);
+  PSTAT_TRY(set_device(h));
+  if (h->failed_job) return report_failed_job(h);
+  for (int64_t i = 0; i < nrec; ++i) {
+    PSTAT_TRY(enqueue_steps(h, stepout));
+    PSTAT_TRY(record());
+  }
+  return enqueue_steps(h, nsteps - nrec * stepout);
 }
 
 // Checks specs[rows][nspecs] (rows = 1, or the cases of a per-case table) and states them as the device reads them; touches no
@@ -678,47 +740,99 @@ int hist_specs(const pstat_hist_spec *specs, int32_t nspecs, int64_t rows, int64
   return PSTAT_OK;
 }
 
-pstat_corr *own_corr(pstat_handle *h, pstat_corr *g) {
-  for (pstat_corr *mine : h->corrs)
-    if (mine == g) return g;
-  return nullptr;
+// one histogram record, enqueued
+int enqueue_hist(pstat_handle *h, pstat_hist *g) {
+  const HistArgs a{h->base.num_chains, h->ncases, h->S.C, 1, g->nspecs, g->total_bins, g->per_case, 0};
+  HIP_TRY(launch_hist(a, h->S.obs, g->d_specs.p, g->d_counts.p, g->d_counts.p + (size_t)h->ncases * (size_t)g->total_bins, h->stream));
+  g->records += 1;
+  return PSTAT_OK;
 }
 
-void free_corr(pstat_corr *g) {
-  (void)hipFree(g->d_totals);
-  (void)hipFree(g->d_partial);
-  (void)hipFree(g->d_rows);
-  delete g;
-}
-
-pstat_shape *own_shape(pstat_handle *h, pstat_shape *g) {
-  for (pstat_shape *mine : h->shapes)
-    if (mine == g) return g;
-  return nullptr;
-}
-
-void free_shape(pstat_shape *g) {
-  (void)hipFree(g->d_q);
-  (void)hipFree(g->d_totals);
-  (void)hipFree(g->d_partial);
-  (void)hipFree(g->d_rows);
-  delete g;
-}
-
-HistArgs hist_args(const pstat_handle *h, const pstat_hist *g) {
-  return HistArgs{h->base.num_chains, h->ncases, h->S.C, 1, g->nspecs, g->total_bins, g->per_case, 0};
-}
-
-// device scratch of one call
-struct DeviceDoubles {
-  double *p = nullptr;
-  int alloc(size_t doubles) {
-    hipError_t e = hipMalloc((void **)&p, doubles * sizeof(double));
-    if (e != hipSuccess) return fail(PSTAT_ERR_NOMEM, "hipMalloc(%zu) failed: %s", doubles * sizeof(double), hipGetErrorString(e));
-    return PSTAT_OK;
-  }
-  ~DeviceDoubles() { (void)hipFree(p); }
+// ---- the correlation and the shape recorder: what they do with their ColumnTotals, given the kind's words
+struct TotalsText {
+  const char *object;     // "the <object> has ... rows free"
+  const char *no_room;    // capacity_rows overflows the address space (%lld rows)
+  const char *nomem;      // a hipMalloc failed (%zu columns, %lld rows, %s)
+  const char *hip;        // another HIP call of the open failed (%s)
 };
+constexpr TotalsText kCorrText{"correlation object", "%lld rows of correlations do not fit the address space",
+                               "correlations of %zu columns, %lld rows: %s", "correlation totals: %s"};
+constexpr TotalsText kShapeText{"shape object", "%lld rows of shape columns do not fit the address space",
+                                "shape object of %zu columns, %lld rows: %s", "shape totals: %s"};
+
+// The allocation tail of pstat_corr_open / pstat_shape_open, after the kind's own argument checks: a new object g with zeroed
+// totals of ncols columns per case, `partial` doubles of scratch and capacity_rows kept rows.
+template <class T>
+int new_totals(pstat_handle *h, int32_t ncols, int64_t capacity_rows, size_t partial, const TotalsText &text, std::unique_ptr<T> &g) {
+  const size_t stride = (size_t)h->ncases * (size_t)ncols;
+  if (capacity_rows > 0 && (uint64_t)capacity_rows > (SIZE_MAX / sizeof(double)) / stride)
+    return fail(PSTAT_ERR_NOMEM, text.no_room, (long long)capacity_rows);
+  PSTAT_TRY(set_device(h));
+  g.reset(new (std::nothrow) T);
+  if (!g) return fail(PSTAT_ERR_NOMEM, "host allocation failed");
+  g->stride = stride;
+  g->capacity = capacity_rows;
+  hipError_t e = g->d_totals.malloc(2 * stride);
+  if (e == hipSuccess) e = g->d_partial.malloc(partial);
+  if (e == hipSuccess && capacity_rows > 0) e = g->d_rows.malloc((size_t)capacity_rows * stride);
+  if (e != hipSuccess) return fail(PSTAT_ERR_NOMEM, text.nomem, stride, (long long)capacity_rows, hipGetErrorString(e));
+  e = hipMemsetAsync(g->d_totals.p, 0, 2 * stride * sizeof(double), h->stream);   // ahead of the first record
+  if (e != hipSuccess) return fail(PSTAT_ERR_HIP, text.hip, hipGetErrorString(e));
+  return PSTAT_OK;
+}
+
+// pstat_X_record: one record outside an advance; `enqueue` launches it
+template <class Enqueue>
+int totals_record(pstat_handle *h, const ColumnTotals *g, const TotalsText &text, Enqueue enqueue) {
+  if (g->capacity > 0 && g->rows >= g->capacity)
+    return fail(PSTAT_ERR_TOO_SMALL, "the %s has 0 of %lld rows free", text.object, (long long)g->capacity);
+  PSTAT_TRY(set_device(h));
+  if (h->failed_job) return report_failed_job(h);
+  return enqueue();
+}
+
+// what a record leaves on the host side once its launch is enqueued; the caller has checked that a row is free
+int recorded(ColumnTotals *g) {
+  g->records += 1;
+  if (g->capacity > 0) g->rows += 1;
+  return PSTAT_OK;
+}
+
+int totals_read(pstat_handle *h, const ColumnTotals *g, double *sum, double *sumsq, int64_t *records) {
+  PSTAT_TRY(set_device(h));
+  PSTAT_TRY(sync_checked(h));
+  if (sum) HIP_TRY(hipMemcpy(sum, g->d_totals.p, g->stride * sizeof(double), hipMemcpyDeviceToHost));
+  if (sumsq) HIP_TRY(hipMemcpy(sumsq, g->d_totals.p + g->stride, g->stride * sizeof(double), hipMemcpyDeviceToHost));
+  if (records) *records = g->records;
+  return PSTAT_OK;
+}
+
+int totals_rows(pstat_handle *h, const ColumnTotals *g, const double **dev_rows, int64_t *nrows, int64_t *stride) {
+  PSTAT_TRY(set_device(h));
+  PSTAT_TRY(sync_checked(h));
+  *dev_rows = g->d_rows.p;
+  *nrows = g->rows;
+  *stride = (int64_t)g->stride;
+  return PSTAT_OK;
+}
+
+int totals_clear(pstat_handle *h, ColumnTotals *g) {
+  PSTAT_TRY(set_device(h));
+  HIP_TRY(hipMemsetAsync(g->d_totals.p, 0, 2 * g->stride * sizeof(double), h->stream));   // behind the records already enqueued
+  g->records = 0;
+  g->rows = 0;
+  return PSTAT_OK;
+}
+
+int enqueue_corr(pstat_handle *h, pstat_corr *g) {
+  HIP_TRY(launch_corr(g->args, h->S.ang, h->d_cases, g->d_partial.p, g->d_totals.p, g->next_row(), h->stream));
+  return recorded(g);
+}
+
+int enqueue_shape(pstat_handle *h, pstat_shape *g) {
+  HIP_TRY(launch_shape(g->args, h->S.ang, h->d_cases, g->d_q.p, g->d_partial.p, g->d_totals.p, g->next_row(), h->stream));
+  return recorded(g);
+}
 
 // the blocking transform of x[nbatches][stride] (device) on `stream`, results to host memory; waits for the stream
 int blocking_to_host(const double *x, int64_t nbatches, int64_t ncols, int64_t stride, int min_blocks, hipStream_t stream,
@@ -950,13 +1064,8 @@ void pstat_destroy(pstat_handle *h) {
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   for (auto &b : h->bufs) (void)hipFree(b.ptr);
-  for (pstat_series *s : h->series) free_series(s);
-  for (pstat_tempering *t : h->tempering) free_tempering(t);
-  for (pstat_hist *g : h->hists) free_hist(g);
-  for (pstat_corr *g : h->corrs) free_corr(g);
-  for (pstat_shape *g : h->shapes) free_shape(g);
   if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
+  delete h;   // with the recorder objects still open: nothing of theirs is in flight behind the synchronise above
 }
 
 int pstat_advance(pstat_handle *h, int64_t nsteps) {
@@ -979,95 +1088,62 @@ int pstat_series_open(pstat_handle *h, int64_t capacity_rows, int32_t flags, pst
   if ((uint64_t)capacity_rows > (SIZE_MAX / sizeof(double)) / row_doubles)
     return fail(PSTAT_ERR_NOMEM, "a series of %lld rows does not fit the address space", (long long)capacity_rows);
   PSTAT_TRY(set_device(h));
-  pstat_series *s = new (std::nothrow) pstat_series;
+  std::unique_ptr<pstat_series> s(new (std::nothrow) pstat_series);
   if (!s) return fail(PSTAT_ERR_NOMEM, "host allocation failed");
   const size_t rows = (size_t)capacity_rows;
-  const struct { double **p; size_t doubles; } parts[] = {
-      {&s->d_red, rows * cases * PSTAT_NRED},
-      {&s->d_micro, rows * cases * 7},
-      {&s->d_angles, (flags & PSTAT_SERIES_ANGLES) ? rows * cases * n2 : 0},
-  };
-  for (const auto &b : parts) {
-    if (!b.doubles) continue;
-    hipError_t e = hipMalloc((void **)b.p, b.doubles * sizeof(double));
-    if (e != hipSuccess) {
-      free_series(s);
-      return fail(PSTAT_ERR_NOMEM, "hipMalloc(%zu) failed: %s", b.doubles * sizeof(double), hipGetErrorString(e));
-    }
-  }
+  PSTAT_TRY(s->d_red.alloc(rows * cases * PSTAT_NRED));
+  PSTAT_TRY(s->d_micro.alloc(rows * cases * 7));
+  if (flags & PSTAT_SERIES_ANGLES) PSTAT_TRY(s->d_angles.alloc(rows * cases * n2));
   try {
     s->steps.resize(rows);
-    h->series.push_back(s);
   } catch (const std::bad_alloc &) {
-    free_series(s);
     return fail(PSTAT_ERR_NOMEM, "host allocation failed");
   }
   s->capacity = capacity_rows;
-  *out = s;
-  return PSTAT_OK;
+  return adopt(h->series, s, out);
 }
 
 int pstat_advance_series(pstat_handle *h, pstat_series *s, int64_t nsteps, int64_t stepout) {
-  if (!h || !s) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
-  if (!own_series(h, s)) return fail(PSTAT_ERR_INVALID_ARG, "the series is not an open series of this handle");
-  if (nsteps < 0) return fail(PSTAT_ERR_INVALID_ARG, "nsteps must be >= 0");
-  if (stepout < 1) return fail(PSTAT_ERR_INVALID_ARG, "stepout must be >= 1");
-  const int64_t nrows = nsteps / stepout;
-  if (nrows > s->capacity - s->rows)
-    return fail(PSTAT_ERR_TOO_SMALL, "the series has %lld of %lld rows free, this call would record %lld",
-                (long long)(s->capacity - s->rows), (long long)s->capacity, (long long)nrows);
-  PSTAT_TRY(set_device(h));
-  if (h->failed_job) return report_failed_job(h);
+  PSTAT_TRY(open_series(h, s));
   const size_t cases = (size_t)h->ncases, n2 = 2 * (size_t)h->base.n;
-  for (int64_t i = 0; i < nrows; ++i) {
-    PSTAT_TRY(enqueue_steps(h, stepout));
+  return advance_recording(h, nsteps, stepout, s->capacity, s->rows, "series", [&]() -> int {
     const size_t row = (size_t)s->rows;
-    HIP_TRY(launch_record(h->cfg, h->args, h->S, h->d_cases, h->steps_recorded, s->d_red + row * cases * PSTAT_NRED,
-                          s->d_micro + row * cases * 7, s->d_angles ? s->d_angles + row * cases * n2 : nullptr, h->stream));
+    HIP_TRY(launch_record(h->cfg, h->args, h->S, h->d_cases, h->steps_recorded, s->d_red.p + row * cases * PSTAT_NRED,
+                          s->d_micro.p + row * cases * 7, s->d_angles.p ? s->d_angles.p + row * cases * n2 : nullptr, h->stream));
     s->steps[row] = h->steps_recorded;
     s->rows += 1;
-  }
-  return enqueue_steps(h, nsteps - nrows * stepout);
+    return PSTAT_OK;
+  });
 }
 
 int pstat_series_read(pstat_handle *h, pstat_series *s, int64_t nrows, int64_t *steps_recorded, double *red, double *micro,
                       double *angles) {
-  if (!h || !s) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
-  if (!own_series(h, s)) return fail(PSTAT_ERR_INVALID_ARG, "the series is not an open series of this handle");
+  PSTAT_TRY(open_series(h, s));
   if (nrows < 0 || nrows > s->rows)
     return fail(PSTAT_ERR_INVALID_ARG, "%lld rows asked for, %lld recorded", (long long)nrows, (long long)s->rows);
-  if (angles && !s->d_angles) return fail(PSTAT_ERR_INVALID_ARG, "the series was opened without PSTAT_SERIES_ANGLES");
+  if (angles && !s->d_angles.p) return fail(PSTAT_ERR_INVALID_ARG, "the series was opened without PSTAT_SERIES_ANGLES");
   PSTAT_TRY(set_device(h));
   PSTAT_TRY(sync_checked(h));
   const size_t rows = (size_t)nrows, cases = (size_t)h->ncases, n2 = 2 * (size_t)h->base.n;
   if (!rows) return PSTAT_OK;
   if (steps_recorded) std::memcpy(steps_recorded, s->steps.data(), rows * sizeof(int64_t));
-  if (red) HIP_TRY(hipMemcpy(red, s->d_red, rows * cases * PSTAT_NRED * sizeof(double), hipMemcpyDeviceToHost));
-  if (micro) HIP_TRY(hipMemcpy(micro, s->d_micro, rows * cases * 7 * sizeof(double), hipMemcpyDeviceToHost));
-  if (angles) HIP_TRY(hipMemcpy(angles, s->d_angles, rows * cases * n2 * sizeof(double), hipMemcpyDeviceToHost));
+  if (red) HIP_TRY(hipMemcpy(red, s->d_red.p, rows * cases * PSTAT_NRED * sizeof(double), hipMemcpyDeviceToHost));
+  if (micro) HIP_TRY(hipMemcpy(micro, s->d_micro.p, rows * cases * 7 * sizeof(double), hipMemcpyDeviceToHost));
+  if (angles) HIP_TRY(hipMemcpy(angles, s->d_angles.p, rows * cases * n2 * sizeof(double), hipMemcpyDeviceToHost));
   return PSTAT_OK;
 }
 
 int pstat_series_clear(pstat_handle *h, pstat_series *s) {
-  if (!h || !s) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
-  if (!own_series(h, s)) return fail(PSTAT_ERR_INVALID_ARG, "the series is not an open series of this handle");
+  PSTAT_TRY(open_series(h, s));
   s->rows = 0;   // later rows are enqueued behind whatever still writes the old ones
   return PSTAT_OK;
 }
 
-void pstat_series_close(pstat_handle *h, pstat_series *s) {
-  if (!h || !s || !own_series(h, s)) return;
-  (void)hipSetDevice(h->device);
-  (void)hipStreamSynchronize(h->stream);   // rows may still be in flight
-  for (size_t i = 0; i < h->series.size(); ++i)
-    if (h->series[i] == s) { h->series.erase(h->series.begin() + (long)i); break; }
-  free_series(s);
-}
+void pstat_series_close(pstat_handle *h, pstat_series *s) { close_object(h, &pstat_handle::series, s); }
 
 int pstat_series_error_bars(pstat_handle *h, pstat_series *s, int64_t first_row, int64_t nrows, int32_t min_blocks,
                             int64_t *nbatches, double *out, double *levels) {
-  if (!h || !s || !out) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
-  if (!own_series(h, s)) return fail(PSTAT_ERR_INVALID_ARG, "the series is not an open series of this handle");
+  PSTAT_TRY(open_series(h, s, out != nullptr));
   if (h->cfg.umbrella)
     return fail(PSTAT_ERR_UNSUPPORTED, "error bars under --umbrella-sampling: the recorded means are ratios with per-chain "
                 "normalizers that the rows do not hold");
@@ -1099,7 +1175,7 @@ int pstat_series_error_bars(pstat_handle *h, pstat_series *s, int64_t first_row,
   DeviceDoubles x;
   PSTAT_TRY(x.alloc((size_t)nb * (size_t)ncols));
   const int64_t row0 = first_row + (zero_base ? 0 : 1);
-  HIP_TRY(launch_series_batches(s->d_red, row0, nb, h->ncases, s->steps[(size_t)row0], d, zero_base ? 1 : 0, x.p, h->stream));
+  HIP_TRY(launch_series_batches(s->d_red.p, row0, nb, h->ncases, s->steps[(size_t)row0], d, zero_base ? 1 : 0, x.p, h->stream));
   return blocking_to_host(x.p, nb, ncols, ncols, min_blocks, h->stream, out, levels);
 }
 
@@ -1132,7 +1208,6 @@ int pstat_tempering_open(pstat_handle *h, const int32_t *ladder, uint64_t seed, 
   if (h->cfg.umbrella)
     return fail(PSTAT_ERR_UNSUPPORTED, "replica exchange under --umbrella-sampling: the weights and their reference energy are "
                 "per chain, relative to the chain's first configuration");
-  pstat_tempering *t = nullptr;
   try {
     // a ladder's cases agree with its first one in every physics scalar but kT
     std::vector<int> first((size_t)nc, -1), order;
@@ -1170,7 +1245,7 @@ int pstat_tempering_open(pstat_handle *h, const int32_t *ladder, uint64_t seed, 
         }
     }
     PSTAT_TRY(set_device(h));
-    t = new (std::nothrow) pstat_tempering;
+    std::unique_ptr<pstat_tempering> t(new (std::nothrow) pstat_tempering);
     if (!t) return fail(PSTAT_ERR_NOMEM, "host allocation failed");
     t->seed = seed;
     const size_t per = (size_t)h->base.num_chains;
@@ -1180,29 +1255,23 @@ int pstat_tempering_open(pstat_handle *h, const int32_t *ladder, uint64_t seed, 
       t->npairs[parity] = (int64_t)(pairs[parity].size() / 2);
       most = pairs[parity].size() / 2 > most ? pairs[parity].size() / 2 : most;
       if (pairs[parity].empty()) continue;
-      e = hipMalloc((void **)&t->d_pairs[parity], pairs[parity].size() * sizeof(int32_t));
+      e = t->d_pairs[parity].malloc(pairs[parity].size());
       if (e == hipSuccess)
-        e = hipMemcpy(t->d_pairs[parity], pairs[parity].data(), pairs[parity].size() * sizeof(int32_t), hipMemcpyHostToDevice);
+        e = hipMemcpy(t->d_pairs[parity].p, pairs[parity].data(), pairs[parity].size() * sizeof(int32_t), hipMemcpyHostToDevice);
     }
-    if (e == hipSuccess && most) e = hipMalloc((void **)&t->d_flags, most * per);
-    if (e == hipSuccess) e = hipMalloc((void **)&t->d_counts, 2 * (size_t)nc * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMemsetAsync(t->d_counts, 0, 2 * (size_t)nc * sizeof(int64_t), h->stream);   // ahead of the first round
-    if (e != hipSuccess) {
-      free_tempering(t);
+    if (e == hipSuccess && most) e = t->d_flags.malloc(most * per);
+    if (e == hipSuccess) e = t->d_counts.malloc(2 * (size_t)nc);
+    if (e == hipSuccess) e = hipMemsetAsync(t->d_counts.p, 0, 2 * (size_t)nc * sizeof(int64_t), h->stream);   // ahead of the first round
+    if (e != hipSuccess)
       return fail(e == hipErrorOutOfMemory ? PSTAT_ERR_NOMEM : PSTAT_ERR_HIP, "tempering tables: %s", hipGetErrorString(e));
-    }
-    h->tempering.push_back(t);
+    return adopt(h->tempering, t, out);
   } catch (const std::bad_alloc &) {
-    if (t) free_tempering(t);
     return fail(PSTAT_ERR_NOMEM, "host allocation failed");
   }
-  *out = t;
-  return PSTAT_OK;
 }
 
 int pstat_tempering_exchange(pstat_handle *h, pstat_tempering *t) {
-  if (!h || !t) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
-  if (!own_tempering(h, t)) return fail(PSTAT_ERR_INVALID_ARG, "the tempering object is not an open one of this handle");
+  PSTAT_TRY(open_tempering(h, t));
   if (t->round > 0xffffffffull)
     return fail(PSTAT_ERR_INVALID_ARG, "the 32-bit round counter of this tempering object is used up (2^32 rounds)");
   PSTAT_TRY(set_device(h));
@@ -1210,37 +1279,28 @@ int pstat_tempering_exchange(pstat_handle *h, pstat_tempering *t) {
   const int parity = (int)(t->round & 1);
   const ExchangeArgs a{h->base.num_chains, h->S.C, h->base.n, t->npairs[parity], (uint32_t)t->round,
                        (uint32_t)t->seed, (uint32_t)(t->seed >> 32), 0u};
-  HIP_TRY(launch_exchange(a, h->S, h->d_cases, t->d_pairs[parity], t->d_flags, t->d_counts, t->d_counts + h->ncases, h->elem,
-                          h->stream));
+  HIP_TRY(launch_exchange(a, h->S, h->d_cases, t->d_pairs[parity].p, t->d_flags.p, t->d_counts.p, t->d_counts.p + h->ncases,
+                          h->elem, h->stream));
   t->round += 1;
   return PSTAT_OK;
 }
 
 int pstat_tempering_stats(pstat_handle *h, pstat_tempering *t, int64_t *attempted, int64_t *accepted, int64_t *rounds) {
-  if (!h || !t) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
-  if (!own_tempering(h, t)) return fail(PSTAT_ERR_INVALID_ARG, "the tempering object is not an open one of this handle");
+  PSTAT_TRY(open_tempering(h, t));
   PSTAT_TRY(set_device(h));
   PSTAT_TRY(sync_checked(h));
   const size_t bytes = (size_t)h->ncases * sizeof(int64_t);
-  if (attempted) HIP_TRY(hipMemcpy(attempted, t->d_counts, bytes, hipMemcpyDeviceToHost));
-  if (accepted) HIP_TRY(hipMemcpy(accepted, t->d_counts + h->ncases, bytes, hipMemcpyDeviceToHost));
+  if (attempted) HIP_TRY(hipMemcpy(attempted, t->d_counts.p, bytes, hipMemcpyDeviceToHost));
+  if (accepted) HIP_TRY(hipMemcpy(accepted, t->d_counts.p + h->ncases, bytes, hipMemcpyDeviceToHost));
   if (rounds) *rounds = (int64_t)t->round;
   return PSTAT_OK;
 }
 
-void pstat_tempering_close(pstat_handle *h, pstat_tempering *t) {
-  if (!h || !t || !own_tempering(h, t)) return;
-  (void)hipSetDevice(h->device);
-  (void)hipStreamSynchronize(h->stream);   // a round may still be in flight
-  for (size_t i = 0; i < h->tempering.size(); ++i)
-    if (h->tempering[i] == t) { h->tempering.erase(h->tempering.begin() + (long)i); break; }
-  free_tempering(t);
-}
+void pstat_tempering_close(pstat_handle *h, pstat_tempering *t) { close_object(h, &pstat_handle::tempering, t); }
 
 int pstat_hist_open(pstat_handle *h, const pstat_hist_spec *specs, int32_t nspecs, int32_t per_case, pstat_hist **out) {
   if (!h || !specs || !out) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
   *out = nullptr;
-  pstat_hist *g = nullptr;
   try {
     std::vector<HistSpec> dev;
     int32_t total_bins = 0;
@@ -1249,89 +1309,56 @@ int pstat_hist_open(pstat_handle *h, const pstat_hist_spec *specs, int32_t nspec
       return fail(PSTAT_ERR_UNSUPPORTED, "histograms under --umbrella-sampling: the samples carry per-chain weights whose gauge "
                   "the counts do not hold");
     PSTAT_TRY(set_device(h));
-    g = new (std::nothrow) pstat_hist;
+    std::unique_ptr<pstat_hist> g(new (std::nothrow) pstat_hist);
     if (!g) return fail(PSTAT_ERR_NOMEM, "host allocation failed");
     g->nspecs = nspecs;
     g->total_bins = total_bins;
     g->per_case = per_case ? 1 : 0;
     g->slots = (size_t)h->ncases * ((size_t)total_bins + 3 * (size_t)nspecs);
-    hipError_t e = hipMalloc((void **)&g->d_specs, dev.size() * sizeof(HistSpec));
-    if (e == hipSuccess) e = hipMalloc((void **)&g->d_counts, g->slots * sizeof(int64_t));
-    if (e != hipSuccess) {
-      const size_t slots = g->slots;
-      free_hist(g);
-      return fail(PSTAT_ERR_NOMEM, "histogram of %zu counters: %s", slots, hipGetErrorString(e));
-    }
-    e = hipMemcpy(g->d_specs, dev.data(), dev.size() * sizeof(HistSpec), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemsetAsync(g->d_counts, 0, g->slots * sizeof(int64_t), h->stream);   // ahead of the first record
-    if (e != hipSuccess) {
-      free_hist(g);
-      return fail(PSTAT_ERR_HIP, "histogram tables: %s", hipGetErrorString(e));
-    }
-    h->hists.push_back(g);
+    hipError_t e = g->d_specs.malloc(dev.size());
+    if (e == hipSuccess) e = g->d_counts.malloc(g->slots);
+    if (e != hipSuccess) return fail(PSTAT_ERR_NOMEM, "histogram of %zu counters: %s", g->slots, hipGetErrorString(e));
+    e = hipMemcpy(g->d_specs.p, dev.data(), dev.size() * sizeof(HistSpec), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemsetAsync(g->d_counts.p, 0, g->slots * sizeof(int64_t), h->stream);   // ahead of the first record
+    if (e != hipSuccess) return fail(PSTAT_ERR_HIP, "histogram tables: %s", hipGetErrorString(e));
+    return adopt(h->hists, g, out);
   } catch (const std::bad_alloc &) {
-    if (g) free_hist(g);
     return fail(PSTAT_ERR_NOMEM, "host allocation failed");
   }
-  *out = g;
-  return PSTAT_OK;
 }
 
 int pstat_hist_record(pstat_handle *h, pstat_hist *g) {
-  if (!h || !g) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
-  if (!own_hist(h, g)) return fail(PSTAT_ERR_INVALID_ARG, "the histogram is not an open histogram of this handle");
+  PSTAT_TRY(open_hist(h, g));
   PSTAT_TRY(set_device(h));
   if (h->failed_job) return report_failed_job(h);
-  HIP_TRY(launch_hist(hist_args(h, g), h->S.obs, g->d_specs, g->d_counts, g->d_counts + (size_t)h->ncases * (size_t)g->total_bins,
-                      h->stream));
-  g->records += 1;
-  return PSTAT_OK;
+  return enqueue_hist(h, g);
 }
 
 int pstat_advance_hist(pstat_handle *h, pstat_hist *g, int64_t nsteps, int64_t stepout) {
-  if (!h || !g) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
-  if (!own_hist(h, g)) return fail(PSTAT_ERR_INVALID_ARG, "the histogram is not an open histogram of this handle");
-  if (nsteps < 0) return fail(PSTAT_ERR_INVALID_ARG, "nsteps must be >= 0");
-  if (stepout < 1) return fail(PSTAT_ERR_INVALID_ARG, "stepout must be >= 1");
-  PSTAT_TRY(set_device(h));
-  if (h->failed_job) return report_failed_job(h);
-  const int64_t nrec = nsteps / stepout;
-  for (int64_t i = 0; i < nrec; ++i) {
-    PSTAT_TRY(enqueue_steps(h, stepout));
-    PSTAT_TRY(pstat_hist_record(h, g));
-  }
-  return enqueue_steps(h, nsteps - nrec * stepout);
+  PSTAT_TRY(open_hist(h, g));
+  return advance_recording(h, nsteps, stepout, 0, 0, "histogram", [&] { return enqueue_hist(h, g); });
 }
 
 int pstat_hist_read(pstat_handle *h, pstat_hist *g, int64_t *counts, int64_t *tails, int64_t *records) {
-  if (!h || !g) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
-  if (!own_hist(h, g)) return fail(PSTAT_ERR_INVALID_ARG, "the histogram is not an open histogram of this handle");
+  PSTAT_TRY(open_hist(h, g));
   PSTAT_TRY(set_device(h));
   PSTAT_TRY(sync_checked(h));
   const size_t nbins = (size_t)h->ncases * (size_t)g->total_bins;
-  if (counts) HIP_TRY(hipMemcpy(counts, g->d_counts, nbins * sizeof(int64_t), hipMemcpyDeviceToHost));
-  if (tails) HIP_TRY(hipMemcpy(tails, g->d_counts + nbins, (g->slots - nbins) * sizeof(int64_t), hipMemcpyDeviceToHost));
+  if (counts) HIP_TRY(hipMemcpy(counts, g->d_counts.p, nbins * sizeof(int64_t), hipMemcpyDeviceToHost));
+  if (tails) HIP_TRY(hipMemcpy(tails, g->d_counts.p + nbins, (g->slots - nbins) * sizeof(int64_t), hipMemcpyDeviceToHost));
   if (records) *records = g->records;
   return PSTAT_OK;
 }
 
 int pstat_hist_clear(pstat_handle *h, pstat_hist *g) {
-  if (!h || !g) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
-  if (!own_hist(h, g)) return fail(PSTAT_ERR_INVALID_ARG, "the histogram is not an open histogram of this handle");
+  PSTAT_TRY(open_hist(h, g));
   PSTAT_TRY(set_device(h));
-  HIP_TRY(hipMemsetAsync(g->d_counts, 0, g->slots * sizeof(int64_t), h->stream));   // behind the records already enqueued
+  HIP_TRY(hipMemsetAsync(g->d_counts.p, 0, g->slots * sizeof(int64_t), h->stream));   // behind the records already enqueued
   g->records = 0;
   return PSTAT_OK;
 }
 
-void pstat_hist_close(pstat_handle *h, pstat_hist *g) {
-  if (!h || !g || !own_hist(h, g)) return;
-  (void)hipSetDevice(h->device);
-  (void)hipStreamSynchronize(h->stream);   // a record may still be in flight
-  for (size_t i = 0; i < h->hists.size(); ++i)
-    if (h->hists[i] == g) { h->hists.erase(h->hists.begin() + (long)i); break; }
-  free_hist(g);
-}
+void pstat_hist_close(pstat_handle *h, pstat_hist *g) { close_object(h, &pstat_handle::hists, g); }
 
 int pstat_histogram_device(const double *x, int64_t nrows, int64_t stride, const pstat_hist_spec *specs, int32_t nspecs,
                            int32_t device, void *stream, int64_t *counts, int64_t *tails) {
@@ -1391,120 +1418,43 @@ int pstat_corr_open(pstat_handle *h, int32_t channels, int32_t max_lag, int64_t 
                 (long long)n, (long long)corr_max_n(h->cfg.planar), h->cfg.planar ? "planar" : "3D");
   if (max_lag < 0) max_lag = (int32_t)(n - 1);
   const int nch = (channels & 1) + ((channels >> 1) & 1) + ((channels >> 2) & 1);
-  const size_t stride = (size_t)h->ncases * (size_t)nch * (size_t)(max_lag + 1);
-  if (capacity_rows > 0 && (uint64_t)capacity_rows > (SIZE_MAX / sizeof(double)) / stride)
-    return fail(PSTAT_ERR_NOMEM, "%lld rows of correlations do not fit the address space", (long long)capacity_rows);
-  PSTAT_TRY(set_device(h));
-  pstat_corr *g = new (std::nothrow) pstat_corr;
-  if (!g) return fail(PSTAT_ERR_NOMEM, "host allocation failed");
-  CorrArgs &a = g->args;
+  CorrArgs a{};
   a.per = h->base.num_chains; a.ncases = h->ncases; a.n = n;
   a.channels = channels; a.max_lag = max_lag; a.ncols = nch * (max_lag + 1);
   a.elem = (int32_t)h->elem; a.planar = h->cfg.planar ? 1 : 0; a.polar = h->cfg.chain_type == PSTAT_POLAR ? 1 : 0;
   corr_shape(a);
-  g->capacity = capacity_rows;
-  hipError_t e = hipMalloc((void **)&g->d_totals, 2 * stride * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc((void **)&g->d_partial, corr_partial_doubles(a) * sizeof(double));
-  if (e == hipSuccess && capacity_rows > 0) e = hipMalloc((void **)&g->d_rows, (size_t)capacity_rows * stride * sizeof(double));
-  if (e != hipSuccess) {
-    free_corr(g);
-    return fail(PSTAT_ERR_NOMEM, "correlations of %zu columns, %lld rows: %s", stride, (long long)capacity_rows, hipGetErrorString(e));
-  }
-  e = hipMemsetAsync(g->d_totals, 0, 2 * stride * sizeof(double), h->stream);   // ahead of the first record
-  if (e != hipSuccess) {
-    free_corr(g);
-    return fail(PSTAT_ERR_HIP, "correlation totals: %s", hipGetErrorString(e));
-  }
-  try {
-    h->corrs.push_back(g);
-  } catch (const std::bad_alloc &) {
-    free_corr(g);
-    return fail(PSTAT_ERR_NOMEM, "host allocation failed");
-  }
-  *out = g;
-  return PSTAT_OK;
-}
-
-// one record, enqueued; the caller has checked that a row is free
-static int enqueue_corr(pstat_handle *h, pstat_corr *g) {
-  const size_t stride = (size_t)h->ncases * (size_t)g->args.ncols;
-  HIP_TRY(launch_corr(g->args, h->S.ang, h->d_cases, g->d_partial, g->d_totals,
-                      g->capacity > 0 ? g->d_rows + (size_t)g->rows * stride : nullptr, h->stream));
-  g->records += 1;
-  if (g->capacity > 0) g->rows += 1;
-  return PSTAT_OK;
+  std::unique_ptr<pstat_corr> g;
+  PSTAT_TRY(new_totals(h, a.ncols, capacity_rows, corr_partial_doubles(a), kCorrText, g));
+  g->args = a;
+  return adopt(h->corrs, g, out);
 }
 
 int pstat_corr_record(pstat_handle *h, pstat_corr *g) {
-  if (!h || !g) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
-  if (!own_corr(h, g)) return fail(PSTAT_ERR_INVALID_ARG, "the correlation object is not an open one of this handle");
-  if (g->capacity > 0 && g->rows >= g->capacity)
-    return fail(PSTAT_ERR_TOO_SMALL, "the correlation object has 0 of %lld rows free", (long long)g->capacity);
-  PSTAT_TRY(set_device(h));
-  if (h->failed_job) return report_failed_job(h);
-  return enqueue_corr(h, g);
+  PSTAT_TRY(open_corr(h, g));
+  return totals_record(h, g, kCorrText, [&] { return enqueue_corr(h, g); });
 }
 
 int pstat_advance_corr(pstat_handle *h, pstat_corr *g, int64_t nsteps, int64_t stepout) {
-  if (!h || !g) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
-  if (!own_corr(h, g)) return fail(PSTAT_ERR_INVALID_ARG, "the correlation object is not an open one of this handle");
-  if (nsteps < 0) return fail(PSTAT_ERR_INVALID_ARG, "nsteps must be >= 0");
-  if (stepout < 1) return fail(PSTAT_ERR_INVALID_ARG, "stepout must be >= 1");
-  const int64_t nrec = nsteps / stepout;
-  if (g->capacity > 0 && nrec > g->capacity - g->rows)
-    return fail(PSTAT_ERR_TOO_SMALL, "the correlation object has %lld of %lld rows free, this call would record %lld",
-                (long long)(g->capacity - g->rows), (long long)g->capacity, (long long)nrec);
-  PSTAT_TRY(set_device(h));
-  if (h->failed_job) return report_failed_job(h);
-  for (int64_t i = 0; i < nrec; ++i) {
-    PSTAT_TRY(enqueue_steps(h, stepout));
-    PSTAT_TRY(enqueue_corr(h, g));
-  }
-  return enqueue_steps(h, nsteps - nrec * stepout);
+  PSTAT_TRY(open_corr(h, g));
+  return advance_recording(h, nsteps, stepout, g->capacity, g->rows, kCorrText.object, [&] { return enqueue_corr(h, g); });
 }
 
 int pstat_corr_read(pstat_handle *h, pstat_corr *g, double *sum, double *sumsq, int64_t *records) {
-  if (!h || !g) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
-  if (!own_corr(h, g)) return fail(PSTAT_ERR_INVALID_ARG, "the correlation object is not an open one of this handle");
-  PSTAT_TRY(set_device(h));
-  PSTAT_TRY(sync_checked(h));
-  const size_t stride = (size_t)h->ncases * (size_t)g->args.ncols;
-  if (sum) HIP_TRY(hipMemcpy(sum, g->d_totals, stride * sizeof(double), hipMemcpyDeviceToHost));
-  if (sumsq) HIP_TRY(hipMemcpy(sumsq, g->d_totals + stride, stride * sizeof(double), hipMemcpyDeviceToHost));
-  if (records) *records = g->records;
-  return PSTAT_OK;
+  PSTAT_TRY(open_corr(h, g));
+  return totals_read(h, g, sum, sumsq, records);
 }
 
 int pstat_corr_rows(pstat_handle *h, pstat_corr *g, const double **dev_rows, int64_t *nrows, int64_t *stride) {
-  if (!h || !g || !dev_rows || !nrows || !stride) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
-  if (!own_corr(h, g)) return fail(PSTAT_ERR_INVALID_ARG, "the correlation object is not an open one of this handle");
-  PSTAT_TRY(set_device(h));
-  PSTAT_TRY(sync_checked(h));
-  *dev_rows = g->d_rows;
-  *nrows = g->rows;
-  *stride = (int64_t)h->ncases * g->args.ncols;
-  return PSTAT_OK;
+  PSTAT_TRY(open_corr(h, g, dev_rows && nrows && stride));
+  return totals_rows(h, g, dev_rows, nrows, stride);
 }
 
 int pstat_corr_clear(pstat_handle *h, pstat_corr *g) {
-  if (!h || !g) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
-  if (!own_corr(h, g)) return fail(PSTAT_ERR_INVALID_ARG, "the correlation object is not an open one of this handle");
-  PSTAT_TRY(set_device(h));
-  const size_t stride = (size_t)h->ncases * (size_t)g->args.ncols;
-  HIP_TRY(hipMemsetAsync(g->d_totals, 0, 2 * stride * sizeof(double), h->stream));   // behind the records already enqueued
-  g->records = 0;
-  g->rows = 0;
-  return PSTAT_OK;
+  PSTAT_TRY(open_corr(h, g));
+  return totals_clear(h, g);
 }
 
-void pstat_corr_close(pstat_handle *h, pstat_corr *g) {
-  if (!h || !g || !own_corr(h, g)) return;
-  (void)hipSetDevice(h->device);
-  (void)hipStreamSynchronize(h->stream);   // a record may still be in flight
-  for (size_t i = 0; i < h->corrs.size(); ++i)
-    if (h->corrs[i] == g) { h->corrs.erase(h->corrs.begin() + (long)i); break; }
-  free_corr(g);
-}
+void pstat_corr_close(pstat_handle *h, pstat_corr *g) { close_object(h, &pstat_handle::corrs, g); }
 
 int pstat_shape_open(pstat_handle *h, const double *q, int32_t nq, int64_t capacity_rows, pstat_shape **out) {
   if (!h || !out) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
@@ -1532,123 +1482,49 @@ int pstat_shape_open(pstat_handle *h, const double *q, int32_t nq, int64_t capac
   if (n > corr_max_n(h->cfg.planar))
     return fail(PSTAT_ERR_UNSUPPORTED, "n = %lld: a chain's positions must fit the LDS of a workgroup, n <= %lld for a %s handle",
                 (long long)n, (long long)corr_max_n(h->cfg.planar), planar ? "planar" : "3D");
-  const int32_t ncols = PSTAT_SHAPE_GYR + nq;
-  const size_t stride = (size_t)h->ncases * (size_t)ncols;
-  if (capacity_rows > 0 && (uint64_t)capacity_rows > (SIZE_MAX / sizeof(double)) / stride)
-    return fail(PSTAT_ERR_NOMEM, "%lld rows of shape columns do not fit the address space", (long long)capacity_rows);
-  PSTAT_TRY(set_device(h));
-  pstat_shape *g = new (std::nothrow) pstat_shape;
-  if (!g) return fail(PSTAT_ERR_NOMEM, "host allocation failed");
-  ShapeArgs &a = g->args;
+  ShapeArgs a{};
   a.per = h->base.num_chains; a.ncases = h->ncases; a.n = n;
-  a.nq = nq; a.ncols = ncols;
+  a.nq = nq; a.ncols = PSTAT_SHAPE_GYR + nq;
   a.elem = (int32_t)h->elem; a.planar = planar ? 1 : 0;
   shape_layout(a);
-  g->capacity = capacity_rows;
-  hipError_t e = hipMalloc((void **)&g->d_totals, 2 * stride * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc((void **)&g->d_partial, shape_partial_doubles(a) * sizeof(double));
-  if (e == hipSuccess && nq > 0) e = hipMalloc((void **)&g->d_q, 3 * (size_t)nq * sizeof(double));
-  if (e == hipSuccess && capacity_rows > 0) e = hipMalloc((void **)&g->d_rows, (size_t)capacity_rows * stride * sizeof(double));
-  if (e != hipSuccess) {
-    free_shape(g);
-    return fail(PSTAT_ERR_NOMEM, "shape object of %zu columns, %lld rows: %s", stride, (long long)capacity_rows, hipGetErrorString(e));
+  std::unique_ptr<pstat_shape> g;
+  PSTAT_TRY(new_totals(h, a.ncols, capacity_rows, shape_partial_doubles(a), kShapeText, g));
+  g->args = a;
+  if (nq > 0) {   // the wave-vectors: a copy, the caller's table may go
+    hipError_t e = g->d_q.malloc(3 * (size_t)nq);
+    if (e != hipSuccess) return fail(PSTAT_ERR_NOMEM, kShapeText.nomem, g->stride, (long long)capacity_rows, hipGetErrorString(e));
+    e = hipMemcpy(g->d_q.p, q, 3 * (size_t)nq * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(PSTAT_ERR_HIP, kShapeText.hip, hipGetErrorString(e));
   }
-  e = hipMemsetAsync(g->d_totals, 0, 2 * stride * sizeof(double), h->stream);   // ahead of the first record
-  if (e == hipSuccess && nq > 0) e = hipMemcpy(g->d_q, q, 3 * (size_t)nq * sizeof(double), hipMemcpyHostToDevice);   // the caller's table may go
-  if (e != hipSuccess) {
-    free_shape(g);
-    return fail(PSTAT_ERR_HIP, "shape totals: %s", hipGetErrorString(e));
-  }
-  try {
-    h->shapes.push_back(g);
-  } catch (const std::bad_alloc &) {
-    free_shape(g);
-    return fail(PSTAT_ERR_NOMEM, "host allocation failed");
-  }
-  *out = g;
-  return PSTAT_OK;
-}
-
-// one record, enqueued; the caller has checked that a row is free
-static int enqueue_shape(pstat_handle *h, pstat_shape *g) {
-  const size_t stride = (size_t)h->ncases * (size_t)g->args.ncols;
-  HIP_TRY(launch_shape(g->args, h->S.ang, h->d_cases, g->d_q, g->d_partial, g->d_totals,
-                       g->capacity > 0 ? g->d_rows + (size_t)g->rows * stride : nullptr, h->stream));
-  g->records += 1;
-  if (g->capacity > 0) g->rows += 1;
-  return PSTAT_OK;
+  return adopt(h->shapes, g, out);
 }
 
 int pstat_shape_record(pstat_handle *h, pstat_shape *g) {
-  if (!h || !g) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
-  if (!own_shape(h, g)) return fail(PSTAT_ERR_INVALID_ARG, "the shape object is not an open one of this handle");
-  if (g->capacity > 0 && g->rows >= g->capacity)
-    return fail(PSTAT_ERR_TOO_SMALL, "the shape object has 0 of %lld rows free", (long long)g->capacity);
-  PSTAT_TRY(set_device(h));
-  if (h->failed_job) return report_failed_job(h);
-  return enqueue_shape(h, g);
+  PSTAT_TRY(open_shape(h, g));
+  return totals_record(h, g, kShapeText, [&] { return enqueue_shape(h, g); });
 }
 
 int pstat_advance_shape(pstat_handle *h, pstat_shape *g, int64_t nsteps, int64_t stepout) {
-  if (!h || !g) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
-  if (!own_shape(h, g)) return fail(PSTAT_ERR_INVALID_ARG, "the shape object is not an open one of this handle");
-  if (nsteps < 0) return fail(PSTAT_ERR_INVALID_ARG, "nsteps must be >= 0");
-  if (stepout < 1) return fail(PSTAT_ERR_INVALID_ARG, "stepout must be >= 1");
-  const int64_t nrec = nsteps / stepout;
-  if (g->capacity > 0 && nrec > g->capacity - g->rows)
-    return fail(PSTAT_ERR_TOO_SMALL, "the shape object has %lld of %lld rows free, this call would record %lld",
-                (long long)(g->capacity - g->rows), (long long)g->capacity, (long long)nrec);
-  PSTAT_TRY(set_device(h));
-  if (h->failed_job) return report_failed_job(h);
-  for (int64_t i = 0; i < nrec; ++i) {
-    PSTAT_TRY(enqueue_steps(h, stepout));
-    PSTAT_TRY(enqueue_shape(h, g));
-  }
-  return enqueue_steps(h, nsteps - nrec * stepout);
+  PSTAT_TRY(open_shape(h, g));
+  return advance_recording(h, nsteps, stepout, g->capacity, g->rows, kShapeText.object, [&] { return enqueue_shape(h, g); });
 }
 
 int pstat_shape_read(pstat_handle *h, pstat_shape *g, double *sum, double *sumsq, int64_t *records) {
-  if (!h || !g) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
-  if (!own_shape(h, g)) return fail(PSTAT_ERR_INVALID_ARG, "the shape object is not an open one of this handle");
-  PSTAT_TRY(set_device(h));
-  PSTAT_TRY(sync_checked(h));
-  const size_t stride = (size_t)h->ncases * (size_t)g->args.ncols;
-  if (sum) HIP_TRY(hipMemcpy(sum, g->d_totals, stride * sizeof(double), hipMemcpyDeviceToHost));
-  if (sumsq) HIP_TRY(hipMemcpy(sumsq, g->d_totals + stride, stride * sizeof(double), hipMemcpyDeviceToHost));
-  if (records) *records = g->records;
-  return PSTAT_OK;
+  PSTAT_TRY(open_shape(h, g));
+  return totals_read(h, g, sum, sumsq, records);
 }
 
 int pstat_shape_rows(pstat_handle *h, pstat_shape *g, const double **dev_rows, int64_t *nrows, int64_t *stride) {
-  if (!h || !g || !dev_rows || !nrows || !stride) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
-  if (!own_shape(h, g)) return fail(PSTAT_ERR_INVALID_ARG, "the shape object is not an open one of this handle");
-  PSTAT_TRY(set_device(h));
-  PSTAT_TRY(sync_checked(h));
-  *dev_rows = g->d_rows;
-  *nrows = g->rows;
-  *stride = (int64_t)h->ncases * g->args.ncols;
-  return PSTAT_OK;
+  PSTAT_TRY(open_shape(h, g, dev_rows && nrows && stride));
+  return totals_rows(h, g, dev_rows, nrows, stride);
 }
 
 int pstat_shape_clear(pstat_handle *h, pstat_shape *g) {
-  if (!h || !g) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
-  if (!own_shape(h, g)) return fail(PSTAT_ERR_INVALID_ARG, "the shape object is not an open one of this handle");
-  PSTAT_TRY(set_device(h));
-  const size_t stride = (size_t)h->ncases * (size_t)g->args.ncols;
-  HIP_TRY(hipMemsetAsync(g->d_totals, 0, 2 * stride * sizeof(double), h->stream));   // behind the records already enqueued
-  g->records = 0;
-  g->rows = 0;
-  return PSTAT_OK;
+  PSTAT_TRY(open_shape(h, g));
+  return totals_clear(h, g);
 }
 
-void pstat_shape_close(pstat_handle *h, pstat_shape *g) {
-  if (!h || !g || !own_shape(h, g)) return;
-  (void)hipSetDevice(h->device);
-  (void)hipStreamSynchronize(h->stream);   // a record may still be in flight
-  for (size_t i = 0; i < h->shapes.size(); ++i)
-    if (h->shapes[i] == g) { h->shapes.erase(h->shapes.begin() + (long)i); break; }
-  free_shape(g);
-}
+void pstat_shape_close(pstat_handle *h, pstat_shape *g) { close_object(h, &pstat_handle::shapes, g); }
 
 int pstat_sync(pstat_handle *h) {
   if (!h) return fail(PSTAT_ERR_INVALID_ARG, "null handle");

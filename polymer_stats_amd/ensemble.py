@@ -238,11 +238,32 @@ class Ensemble:
         return info
 
 
-class Series:
+class _Recorder:
+    """An object that a handle keeps open for its Ensemble (pstat_<_kind>_*): `_g` is its address, None once closed."""
+
+    _kind = ""
+
+    def __init__(self, ensemble: Ensemble, g):
+        self._e, self._g = ensemble, g
+
+    def _fn(self, name: str):
+        return getattr(self._e._L, f"pstat_{self._kind}_{name}")
+
+    def close(self):
+        if self._g and self._e._h:      # (closing the ensemble closes its objects)
+            self._fn("close")(self._e._h, self._g)
+        self._g = None
+
+
+class Series(_Recorder):
     """Rows recorded by Ensemble.advance_series (pstat_series_*); `rows` counts them."""
 
+    _kind = "series"
+    _s = property(lambda self: self._g)
+
     def __init__(self, ensemble: Ensemble, s, angles: bool):
-        self._e, self._s, self.angles, self.rows = ensemble, s, angles, 0
+        super().__init__(ensemble, s)
+        self.angles, self.rows = angles, 0
 
     def read(self, nrows: int | None = None):
         """(steps[rows], red[rows, ncases, NRED], micro[rows, ncases, 7], angles[rows, ncases, 2n] or None) of the first
@@ -275,17 +296,12 @@ class Series:
         check(self._e._L.pstat_series_clear(self._e._h, self._s))
         self.rows = 0
 
-    def close(self):
-        if self._s and self._e._h:      # (closing the ensemble closes its series)
-            self._e._L.pstat_series_close(self._e._h, self._s)
-        self._s = None
 
-
-class Tempering:
+class Tempering(_Recorder):
     """Replica exchange between the cases of an Ensemble (Ensemble.open_tempering)."""
 
-    def __init__(self, ensemble: Ensemble, t):
-        self._e, self._t = ensemble, t
+    _kind = "tempering"
+    _t = property(lambda self: self._g)
 
     def exchange(self):
         """One round: even rounds pair rungs (0, 1), (2, 3), ..., odd rounds (1, 2), (3, 4), ... (asynchronous)."""
@@ -301,11 +317,6 @@ class Tempering:
         ip = C.POINTER(C.c_int64)
         check(e._L.pstat_tempering_stats(e._h, self._t, att.ctypes.data_as(ip), acc.ctypes.data_as(ip), C.byref(rounds)))
         return att, acc, int(rounds.value)
-
-    def close(self):
-        if self._t and self._e._h:      # (closing the ensemble closes its tempering objects)
-            self._e._L.pstat_tempering_close(self._e._h, self._t)
-        self._t = None
 
 
 def _edges(spec) -> np.ndarray:
@@ -337,11 +348,14 @@ class HistResult:
         return self.counts[i][case] / (max(self.samples, 1) * (sp.hi - sp.lo) / sp.nbins)
 
 
-class Hist:
+class Hist(_Recorder):
     """Histograms recorded on the device (Ensemble.open_hist, pstat_hist_*)."""
 
+    _kind = "hist"
+
     def __init__(self, ensemble: Ensemble, g, specs):
-        self._e, self._g, self.specs = ensemble, g, specs
+        super().__init__(ensemble, g)
+        self.specs = specs
 
     def record(self):
         """Adds the current configuration of every chain (asynchronous)."""
@@ -363,10 +377,15 @@ class Hist:
     def clear(self):
         check(self._e._L.pstat_hist_clear(self._e._h, self._g))
 
-    def close(self):
-        if self._g and self._e._h:      # (closing the ensemble closes its histograms)
-            self._e._L.pstat_hist_close(self._e._h, self._g)
-        self._g = None
+
+def _mean_and_chain_stderr(sum_: np.ndarray, sumsq: np.ndarray, records: int, N: int):
+    """Of column totals over `records` records of N chains: sum / (records * N), and the across-chain standard error of that
+    mean, defined after exactly one record (chains are independent, records of one chain are not) and NaN otherwise."""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = sum_ / (records * N) if records > 0 else np.full(sum_.shape, np.nan)
+        if records == 1 and N > 1:
+            return mean, np.sqrt(np.maximum(sumsq / N - (sum_ / N) ** 2, 0.0) / (N - 1))
+        return mean, np.full(sum_.shape, np.nan)
 
 
 class CorrResult:
@@ -377,50 +396,46 @@ class CorrResult:
 
     def __init__(self, channels, max_lag: int, num_chains: int, sum_: np.ndarray, sumsq: np.ndarray, records: int):
         self.channels, self.max_lag, self.records, self.sum, self.sumsq = channels, max_lag, records, sum_, sumsq
-        w, N = max_lag + 1, num_chains
-        self.mean, self.chain_stderr = {}, {}
-        for i, ch in enumerate(channels):
-            s, q = sum_[:, i * w:(i + 1) * w], sumsq[:, i * w:(i + 1) * w]
-            with np.errstate(invalid="ignore", divide="ignore"):
-                self.mean[ch] = s / (records * N) if records > 0 else np.full(s.shape, np.nan)
-                if records == 1 and N > 1:
-                    self.chain_stderr[ch] = np.sqrt(np.maximum(q / N - (s / N) ** 2, 0.0) / (N - 1))
-                else:
-                    self.chain_stderr[ch] = np.full(s.shape, np.nan)
+        w = max_lag + 1
+        mean, stderr = _mean_and_chain_stderr(sum_, sumsq, records, num_chains)
+        self.mean = {ch: mean[:, i * w:(i + 1) * w] for i, ch in enumerate(channels)}
+        self.chain_stderr = {ch: stderr[:, i * w:(i + 1) * w] for i, ch in enumerate(channels)}
 
 
-class Corr:
-    """Lag correlations recorded on the device (Ensemble.open_corr, pstat_corr_*)."""
+class _Totals(_Recorder):
+    """What Corr and Shape share: per-case totals of `ncols` columns and, with capacity_rows > 0 at the open, one row of case
+    means per record."""
 
-    def __init__(self, ensemble: Ensemble, g, channels, max_lag: int):
-        self._e, self._g, self.channels, self.max_lag = ensemble, g, channels, max_lag
-        self.ncols = len(channels) * (max_lag + 1)
+    def __init__(self, ensemble: Ensemble, g, ncols: int):
+        super().__init__(ensemble, g)
+        self.ncols = ncols
+        self._record = self._fn("record")
 
     def record(self):
         """One record of the current configuration of every chain (asynchronous)."""
-        check(self._e._L.pstat_corr_record(self._e._h, self._g))
+        check(self._record(self._e._h, self._g))
 
-    def read(self) -> CorrResult:
-        """Synchronises."""
+    def _read(self):
+        """(sum, sumsq, records) as the library keeps them.  Synchronises."""
         e = self._e
         s = np.zeros((e.ncases, self.ncols))
         q = np.zeros((e.ncases, self.ncols))
         records = C.c_int64(0)
         dp = C.POINTER(C.c_double)
-        check(e._L.pstat_corr_read(e._h, self._g, s.ctypes.data_as(dp), q.ctypes.data_as(dp), C.byref(records)))
-        return CorrResult(self.channels, self.max_lag, e.num_chains, s, q, int(records.value))
+        check(self._fn("read")(e._h, self._g, s.ctypes.data_as(dp), q.ctypes.data_as(dp), C.byref(records)))
+        return s, q, int(records.value)
 
     def rows(self):
         """(device pointer, rows, stride) of the per-record case means, a float64 matrix [rows][ncases * ncols] in device
-        memory (pstat_corr_rows).  Synchronises."""
+        memory (pstat_corr_rows, pstat_shape_rows).  Synchronises."""
         e = self._e
         ptr, nrows, stride = C.c_void_p(), C.c_int64(0), C.c_int64(0)
-        check(e._L.pstat_corr_rows(e._h, self._g, C.byref(ptr), C.byref(nrows), C.byref(stride)))
+        check(self._fn("rows")(e._h, self._g, C.byref(ptr), C.byref(nrows), C.byref(stride)))
         return ptr.value or 0, int(nrows.value), int(stride.value)
 
     def error_bars(self, min_blocks: int = 32, levels: bool = False, device: int | None = None) -> "ErrorBars":
-        """Blocked standard errors of the recorded rows' columns (pstat_blocking_device on pstat_corr_rows): arrays of shape
-        [ncases, ncols].  Needs capacity_rows > 0 at open_corr and at least `min_blocks` records.  Synchronises."""
+        """Blocked standard errors of the recorded rows' columns (pstat_blocking_device on rows()): arrays of shape
+        [ncases, ncols].  Needs capacity_rows > 0 at open_corr / open_shape and at least `min_blocks` records.  Synchronises."""
         e = self._e
         ptr, nrows, stride = self.rows()
         dev = int(e.cases[0].device) if device is None else int(device)
@@ -430,12 +445,21 @@ class Corr:
         return ErrorBars(out.reshape(e.ncases, self.ncols, -1), nrows, lev)
 
     def clear(self):
-        check(self._e._L.pstat_corr_clear(self._e._h, self._g))
+        check(self._fn("clear")(self._e._h, self._g))
 
-    def close(self):
-        if self._g and self._e._h:      # (closing the ensemble closes its correlation objects)
-            self._e._L.pstat_corr_close(self._e._h, self._g)
-        self._g = None
+
+class Corr(_Totals):
+    """Lag correlations recorded on the device (Ensemble.open_corr, pstat_corr_*)."""
+
+    _kind = "corr"
+
+    def __init__(self, ensemble: Ensemble, g, channels, max_lag: int):
+        super().__init__(ensemble, g, len(channels) * (max_lag + 1))
+        self.channels, self.max_lag = channels, max_lag
+
+    def read(self) -> CorrResult:
+        """Synchronises."""
+        return CorrResult(self.channels, self.max_lag, self._e.num_chains, *self._read())
 
 
 def _shape_q(q, planar: bool) -> np.ndarray:
@@ -460,14 +484,8 @@ class ShapeResult:
 
     def __init__(self, q: np.ndarray, num_chains: int, planar: bool, sum_: np.ndarray, sumsq: np.ndarray, records: int):
         self.q, self.num_chains, self.planar, self.records, self.sum, self.sumsq = q, num_chains, planar, records, sum_, sumsq
-        N = num_chains
-        with np.errstate(invalid="ignore", divide="ignore"):
-            self.mean = sum_ / (records * N) if records > 0 else np.full(sum_.shape, np.nan)
-            if records == 1 and N > 1:
-                self.chain_stderr = np.sqrt(np.maximum(sumsq / N - (sum_ / N) ** 2, 0.0) / (N - 1))
-            else:
-                self.chain_stderr = np.full(sum_.shape, np.nan)
-        m = self.mean
+        m, self.chain_stderr = _mean_and_chain_stderr(sum_, sumsq, records, num_chains)
+        self.mean = m
         self.gyration = np.stack([np.stack([m[:, 0], m[:, 3], m[:, 4]], axis=-1), np.stack([m[:, 3], m[:, 1], m[:, 5]], axis=-1),
                                   np.stack([m[:, 4], m[:, 5], m[:, 2]], axis=-1)], axis=1)
         self.rg2 = m[:, 6]
@@ -485,53 +503,18 @@ def shape_anisotropy(result: ShapeResult) -> np.ndarray:
         return (2.0 * trg2 - rg4) / rg4 if result.planar else (3.0 * trg2 - rg4) / (2.0 * rg4)
 
 
-class Shape:
+class Shape(_Totals):
     """Gyration tensor and form factor recorded on the device (Ensemble.open_shape, pstat_shape_*)."""
 
-    def __init__(self, ensemble: Ensemble, g, q: np.ndarray):
-        self._e, self._g, self.q = ensemble, g, q
-        self.ncols = len(_lib.SHAPE_NAMES) + len(q)
+    _kind = "shape"
 
-    def record(self):
-        """One record of the current configuration of every chain (asynchronous)."""
-        check(self._e._L.pstat_shape_record(self._e._h, self._g))
+    def __init__(self, ensemble: Ensemble, g, q: np.ndarray):
+        super().__init__(ensemble, g, len(_lib.SHAPE_NAMES) + len(q))
+        self.q = q
 
     def read(self) -> ShapeResult:
         """Synchronises."""
-        e = self._e
-        s = np.zeros((e.ncases, self.ncols))
-        q = np.zeros((e.ncases, self.ncols))
-        records = C.c_int64(0)
-        dp = C.POINTER(C.c_double)
-        check(e._L.pstat_shape_read(e._h, self._g, s.ctypes.data_as(dp), q.ctypes.data_as(dp), C.byref(records)))
-        return ShapeResult(self.q, e.num_chains, e.planar, s, q, int(records.value))
-
-    def rows(self):
-        """(device pointer, rows, stride) of the per-record case means, a float64 matrix [rows][ncases * ncols] in device
-        memory (pstat_shape_rows).  Synchronises."""
-        e = self._e
-        ptr, nrows, stride = C.c_void_p(), C.c_int64(0), C.c_int64(0)
-        check(e._L.pstat_shape_rows(e._h, self._g, C.byref(ptr), C.byref(nrows), C.byref(stride)))
-        return ptr.value or 0, int(nrows.value), int(stride.value)
-
-    def error_bars(self, min_blocks: int = 32, levels: bool = False, device: int | None = None) -> "ErrorBars":
-        """Blocked standard errors of the recorded rows' columns (pstat_blocking_device on pstat_shape_rows): arrays of shape
-        [ncases, ncols].  Needs capacity_rows > 0 at open_shape and at least `min_blocks` records.  Synchronises."""
-        e = self._e
-        ptr, nrows, stride = self.rows()
-        dev = int(e.cases[0].device) if device is None else int(device)
-        eb = blocking_device(ptr, nrows, stride, stride, min_blocks=min_blocks, levels=levels, device=dev)
-        out = np.stack([eb.mean, eb.stderr, eb.stderr_err, eb.inefficiency, eb.level.astype(float), eb.converged.astype(float)], axis=-1)
-        lev = eb.levels.reshape(e.ncases, self.ncols, -1) if levels else None
-        return ErrorBars(out.reshape(e.ncases, self.ncols, -1), nrows, lev)
-
-    def clear(self):
-        check(self._e._L.pstat_shape_clear(self._e._h, self._g))
-
-    def close(self):
-        if self._g and self._e._h:      # (closing the ensemble closes its shape objects)
-            self._e._L.pstat_shape_close(self._e._h, self._g)
-        self._g = None
+        return ShapeResult(self.q, self._e.num_chains, self._e.planar, *self._read())
 
 
 def histogram_device(ptr: int, nrows: int, stride: int, specs, device: int = 0, stream: int | None = None):
