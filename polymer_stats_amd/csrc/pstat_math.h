@@ -25,7 +25,7 @@ template <> struct K<double> {
 // versions cost several times that).  Classic forms: exp by x = k ln2 + r, |r| <= ln2/2, a degree-13
 // polynomial and one v_ldexp; log by x = 2^k (1 + f), sqrt(1/2) < 1 + f < sqrt(2), s = f / (2 + f) and the
 // fdlibm minimax polynomial in s^2 (the reciprocal is v_rcp_f64 + two Newton steps).  Both within 2 ulp
-// (tools/mathcheck); the test they feed compares against a 23-bit uniform.  exp(-inf) = 0, log(0) = -inf,
+// (tests/test_gpu_math.py: 0.95 and 0.88 ulp measured); the test they feed compares against a 23-bit uniform.  exp(-inf) = 0, log(0) = -inf,
 // NaN in => NaN out, as the reject-on-NaN logic of the callers needs.
 __device__ __forceinline__ double exp_f64(const double x) {
   const double k = rint(x * 1.44269504088896338700e+00);
@@ -139,8 +139,21 @@ __device__ __forceinline__ double eps_uniform(const bool wide, const uint32_t we
 // is  eps * st0 < st1 * exp(-dU/kT + extra)  wherever that product is finite, and an f32 evaluation of the two sides
 // (v_exp_f32, three conversions) decides it whenever they differ by more than the f32 error bound m: only draws
 // within a relative 1e-5 of the threshold -- one wave-step in ~1500 -- run the literal double expression, whose
-// verdict is then taken unchanged.  The decision is therefore ALWAYS the literal one (the bit-parity tests against
-// the oracle hold); the filter only spares its evaluation.  The filter sees the top 23 bits u of eps only, i.e. eps in
+// verdict is then taken unchanged.  The decision is therefore the literal one (the bit-parity tests against
+// the oracle hold); the filter only spares its evaluation.
+// DOMAIN of that promise (tests/test_gpu_math.py asserts it over the whole domain and at its boundary): num and den each
+// exactly 0 or in [2^-96, 16]; any x, +-inf and NaN included; any draw.  There every f32 quantity the two compares see is a
+// normal float, 0 or inf, which is what m bounds the error of: den >= 2^-96 and u >= 2^-23 keep lhs above 2^-119, and where
+// v_exp_f32 underflows (x < -87.3: it returns 0 for every subnormal result) the true rhs is below 16 * 2^-126, so the
+// rejection is the literal one.  BELOW 2^-96 the promise does not hold: the conversions of num and den, or their products
+// with u and e, are subnormal floats whose rounding error exceeds m, and the filter decided up to one near-threshold draw
+// in seven against the literal test (the recorded family of the test; profiles/math/math_probe.txt).  No step of the sweep
+// leaves the domain: num and den are sin(theta') and sin(theta), theta in [0, pi].  A clamped theta is exactly 0 or fl(pi),
+// whose sines are 0 and 1.2246e-16 = 2^-52.9.  Any other theta' = fl(theta + d) comes from a displacement d = step (k 2^-22 - 1)
+// that is 0 or at least step 2^-22 in magnitude: the sum is a multiple of the spacing of doubles at |d| / 2, so a positive
+// theta' is >= step 2^-76 (and pi - theta' >= 2^-51), and its sine is inside the domain for every step size >= 2^-19 rad.
+// The clustering mains multiply in the Hastings ratio, a product of link probabilities: they stay inside while it does.
+// The filter sees the top 23 bits u of eps only, i.e. eps in
 // [u, u + 2^-23) under either contract: it accepts on the upper end of that interval and rejects on the lower, so a draw
 // whose low bits could matter (u * den within 2^-23 den of the threshold) goes to the literal branch too.  NaN, +-inf,
 // underflow to 0 and eps = 0 all land in the literal branch or on the side the literal test takes.
@@ -178,15 +191,31 @@ __device__ __forceinline__ bool metropolis_filter(const double x, const double n
   }
   return ok;
 }
+// the reference's expression itself (what the filter's rare branch evaluates; tests/test_gpu_math.py holds it to a
+// 200-bit evaluation of the same expression).  MetropolisLiteral is the closure that metropolis_f64 hands to the filter,
+// written out -- references to the caller's variables in the order of their use, so that every kernel compiles to the
+// code it had when this was an unnamed lambda; metropolis_literal evaluates it.
+struct MetropolisLiteral {
+  const double &dU, &kT, &st1, &st0, &extra;
+  const bool &wide;
+  const uint32_t &weps, &w0, &wphi, &wth;
+  __device__ __forceinline__ bool operator()() const {
+    const double delta = -dU / kT + log_f64(st1 / st0) + extra;
+    const double eps = eps_uniform(wide, weps, w0, wphi, wth);
+    return (delta >= 0) || (eps < exp_f64(delta));
+  }
+};
+__device__ __forceinline__ bool metropolis_literal(const double dU, const double kT, const double st1, const double st0,
+                                                   const double extra, const bool wide, const uint32_t weps, const uint32_t w0,
+                                                   const uint32_t wphi, const uint32_t wth) {
+  return MetropolisLiteral{dU, kT, st1, st0, extra, wide, weps, w0, wphi, wth}();
+}
 template <bool STRAIGHT = false>
 __device__ __forceinline__ bool metropolis_f64(const double dU, const double kT, const double ninv_kT, const double st1,
                                                const double st0, const double extra, const bool wide, const uint32_t weps,
                                                const uint32_t w0, const uint32_t wphi, const uint32_t wth) {
-  return metropolis_filter<STRAIGHT>(dU * ninv_kT + extra, st1, st0, weps, [&]() -> bool {
-    const double delta = -dU / kT + log_f64(st1 / st0) + extra;
-    const double eps = eps_uniform(wide, weps, w0, wphi, wth);
-    return (delta >= 0) || (eps < exp_f64(delta));
-  });
+  return metropolis_filter<STRAIGHT>(dU * ninv_kT + extra, st1, st0, weps,
+                                     MetropolisLiteral{dU, kT, st1, st0, extra, wide, weps, w0, wphi, wth});
 }
 
 // dipole of one monomer: inc/dipole_response.jl:7-11 (dielectric), :27-29 with M = mu*I (polar)
@@ -233,7 +262,7 @@ __device__ __forceinline__ float pair_term_fast(float rx, float ry, float rz, fl
 // 1 / sqrt(x) in full double precision from v_rsq_f64 (relative error 5.2e-8, measured) and ONE third-order correction:
 // with e = 1 - x y^2,  1/sqrt(x) = y / sqrt(1 - e) = y (1 + e/2 + 3 e^2 / 8 + O(e^3)),  e^3 ~ 1e-22.  Five instructions
 // where two Newton steps take eight (+3...5 % on the f64 all-pairs kernels); max error 2.6 ulp over 4 M arguments of
-// 1e-12 ... 1e12 (tools/mathcheck; the two Newton steps gave 1.2 ulp: the rounding of x y enters e).  rsq(0) = inf gives
+// 1e-12 ... 1e12 (tests/test_gpu_math.py holds it to 3 ulp; the two Newton steps gave 1.2 ulp: the rounding of x y enters e).  rsq(0) = inf gives
 // x y = NaN and the result NaN: the callers' 1/r^3 singularity stays a NaN as in the reference.
 __device__ __forceinline__ double rsqrt_f64(const double x) {
   const double y = __builtin_amdgcn_rsq(x);
@@ -329,8 +358,13 @@ __device__ __forceinline__ v2d pfma(v2d a, v2d b, v2d c) { return a * b + c; }  
 // three-part Cody-Waite with fused multiply-adds (pi/2 = HI + MID + LO, the k HI product is exact inside
 // the fma; good far beyond any angle a chain reaches -- phi random-walks unwrapped, |phi| stays in the
 // hundreds), then the classic minimax kernels on [-pi/4, pi/4] with the low part of r carried through
-// (the fdlibm polynomials).  |x| >= 1e5 is first folded by whole turns (less accurate there; no chain
-// gets near it).  sin(fl(pi)) = 1.2246e-16 and
+// (the fdlibm polynomials).  Measured (tests/test_gpu_math.py, both contraction settings): 0.76 ulp -- EXCEPT where the
+// result is smaller than |k| MID, i.e. x is fl(k pi/2) to its last bit or two: there r0 and k MID cancel, r0 - r below rounds
+// a number near k MID, and the low word loses up to 2^-53 |k| MID of the reduced argument.  The result, a number below
+// 4e-12, is then off by up to 1e-31 absolute but hundreds of ulp of itself (640 ulp at cos(fl(29 pi/2)) = 6.2e-19; 1.1 ulp
+// at k = 15 and 30); k = 1 and 2 are exact as stated below.  Harmless where it is used (fills, recorders: sums of terms of
+// size 1), and held to that derived bound by the test.  |x| >= 1e5 is first folded by whole turns (two more roundings
+// of the argument, 2^-52 each: absolute 5.6e-16 there; no chain gets near it).  sin(fl(pi)) = 1.2246e-16 and
 // cos(fl(pi/2)) = 6.1e-17 come out as in glibc, which the clamp corner cases of the parity tests see.
 __device__ __forceinline__ void sincos_f64(double x, double *s, double *c) {
   if (!(fabs(x) < 1.0e5)) {   // fold by whole turns: 2 pi = HI2 + LO2
@@ -362,7 +396,7 @@ __device__ __forceinline__ void sincos_f64(double x, double *s, double *c) {
 }
 
 // sin and cos of a double for the HOT LOOP of the f64 sweep: ~30 instructions instead of ~50, each result within
-// 1.5 ulp (tools/mathcheck).  What is dropped against sincos_f64 is the low word of the reduced argument (r is carried
+// 1.5 ulp (tests/test_gpu_math.py: 1.17 measured).  What is dropped against sincos_f64 is the low word of the reduced argument (r is carried
 // as one double, itself correctly rounded: k HI is exact inside the first fma) and fdlibm's compensated final sums
 // (plain Horner forms in fused multiply-adds).  Nothing here can move a chain off the oracle's trajectory: angles are
 // stored and proposed without any trigonometry, and sin/cos only enter the energy difference and the Jacobian
@@ -372,7 +406,7 @@ __device__ __forceinline__ void sincos_f64(double x, double *s, double *c) {
 // sin(0) = 0, sin(fl(pi)) = 1.2246e-16 and cos(fl(pi/2)) = 6.1e-17 exactly as sincos_f64 gives them.
 // FOLD (unbounded arguments: phi random-walks unwrapped, inc/eap_chain.jl:232): arguments of |x| >= PSTAT_PHI_FOLD are first
 // folded by whole turns.  The two-word reduction below is good far beyond that (k HI is exact inside its fma and the
-// dropped third word contributes k * 1.5e-33: 1e-24 at |x| = 1e9; tools/mathcheck covers +-9e8), the bound only keeps k
+// dropped third word contributes k * 1.5e-33: 1e-24 at |x| = 1e9; tests/test_gpu_math.py covers both sides of the bound), the bound only keeps k
 // inside an int32.  The fold is seven instructions that no chain ever needs (|phi| ~ pi sqrt(steps / 3)); the f64 sweep
 // therefore compiles its step loop twice and runs the FOLD = false copy whenever no chain of the wave can reach the
 // bound within the segment (run_segment: max |phi| at fill + pi per remaining step).
@@ -399,7 +433,7 @@ __device__ __forceinline__ void sincos_fast_f64(double x, double *s, double *c) 
     // theta in [0, pi]: k is 0, 1 or 2 and sin(theta) >= 0, so the quadrant logic shrinks to two compares on k itself, an
     // |.| and two negations (source modifiers) -- the same bits as the general form below gives on [0, pi]: there the sin
     // kernel's sign is applied to r before the polynomial, here after it (an odd function of r, evaluated in the same
-    // operations), and for k = 0 the reduced r = theta is >= 0, for k = 2 it is theta - pi <= 0 (tools/mathcheck compares the two forms bit for bit).
+    // operations), and for k = 0 the reduced r = theta is >= 0, for k = 2 it is theta - pi <= 0 (tests/test_gpu_math.py compares the two forms bit for bit).
     const double ks = __builtin_fma(r * z, ps, r);
     const double kc = __builtin_fma(z, __builtin_fma(z, pc, -0.5), 1.0);
     const bool one = k == 1.0, two = k == 2.0;
@@ -446,7 +480,7 @@ __device__ __forceinline__ float acos_r(float x) {
 // asin(t) = t + t z g(z), z = t^2 <= 1/4 and g a degree-12 polynomial (Chebyshev-node fit of (asin(sqrt z)/sqrt z - 1)/z
 // on [0, 1/4], relative truncation error 3.6e-18):  |x| < 1/2: acos x = pi/2 - asin x;  |x| >= 1/2: with z = (1 - |x|)/2,
 // acos |x| = 2 asin(sqrt z), mirrored for x < 0.  sqrt z by v_rsq_f64 + one Goldschmidt step.  Max error 1.2 ulp
-// (tools/mathcheck); acos(1) = 0 and acos(-1) = fl(pi) exactly.  Bond angles feed the <psi> averager and, with
+// (tests/test_gpu_math.py: 1.15 measured); acos(1) = 0 and acos(-1) = fl(pi) exactly.  Bond angles feed the <psi> averager and, with
 // --bend-mod, the bending energy kappa/2 (psi - psi0)^2, hence dU and the Metropolis decision of the clustering main:
 // against the oracle's libm acos that perturbs dU by ~1 ulp of psi, the same 1e-16 class as the hot-loop sincos (a
 // decision compares against a 23-bit uniform: it moves with probability ~1e-16).

@@ -53,6 +53,10 @@ F32_ANGLE_BOUND_TURNS = 8 * U
 #       angle with |dg / dangle| <= 1 (cos^2 theta, cos theta): <= 31 u |A| / kT,                            400
 #   (d) v_exp_f32: 1 ulp = 2 u relative, i.e. 2 u absolute in the logarithm; its argument carries (a);
 #       v_rcp_f32 (alpha), v_rsq_f32 (pair terms): 1 ulp each; v_log_f32 is not on the decision path.         6
+#       (Measured by tests/test_gpu_math.py, profiles/math/math_probe.txt: v_sin / v_cos 2.1 u absolute over every turn the
+#       kernels use, v_exp_f32 1.4 u relative, v_rcp_f32 0.86 ulp, v_rsq_f32 0.83 ulp -- on NORMAL results: v_exp_f32
+#       and v_rcp_f32 return 0 for every result below 2^-126.  No decision gets there: exp2 underflows for d < -87, where
+#       eps >= 2^-23 has long rejected, and alpha is a ratio of link probabilities nowhere near 2^126.)
 #   (e) log sin.  The kernels never take it, they compare u sin0 against sin1 e; an absolute SINCOS_ABS on sin(theta) is a
 #       relative SINCOS_ABS / sin(theta) = the error of log sin, and (c) moves log sin(theta') by 31 u |cot theta'|.  mag grows
 #       only like 1 + |log sin|, so no constant covers the poles: these enter the margin as a term of their own,
