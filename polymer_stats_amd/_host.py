@@ -199,32 +199,6 @@ def check_numeric_type(pargs: dict):
         raise ReferenceError_(f"numeric-type '{pargs['numeric-type']}' not understood")
 
 
-def check_error_bars(pargs: dict, nbatches: int, write_csv: bool = False, devices: int | None = None):
-    """What --error-bars N (tools/run_sweep.py; run_cases(..., error_bars=N)) cannot be combined with, refused before any
-    GPU work.  `devices`: how many hold the chains (default: those --devices names)."""
-    if devices is None:
-        devices = len([d for d in str(pargs["devices"]).split(",") if d != ""][:max(1, int(pargs["num-chains"]))])
-    if nbatches < 32:
-        raise ReferenceError_(f"--error-bars {nbatches}: the blocking transform needs at least 32 batches")
-    if int(pargs["num-steps"]) < nbatches:
-        raise ReferenceError_(f"--error-bars {nbatches} needs --num-steps >= {nbatches}: a batch is num-steps / {nbatches} steps")
-    if write_csv:
-        raise ReferenceError_("--error-bars cannot be combined with --csv: the production run is recorded as batches, not as "
-                              "--stepout rows")
-    if devices > 1:
-        raise ReferenceError_(f"--error-bars needs one device, not {devices}: the devices hold different chains of a case and "
-                              "their series are not merged")
-    if int(pargs.get("num-inits", 1)) != 1:
-        raise ReferenceError_(f"--error-bars cannot be combined with --num-inits {pargs['num-inits']}: a re-initialisation "
-                              "between batches is not a stationary series")
-    if pargs["umbrella-sampling"]:
-        raise ReferenceError_("--error-bars cannot be combined with --umbrella-sampling: the recorded means are ratios with "
-                              "per-chain normalizers that the rows do not hold")
-    if pargs["numeric-type"] != "float64":
-        raise ReferenceError_(f"--error-bars cannot be combined with --numeric-type {pargs['numeric-type']}: the batches are "
-                              "differences of the device's Float64 reductions")
-
-
 def parse_hist(text: str):
     """One --hist CHANNEL:LO:HI:NBINS of tools/run_sweep.py -> (channel name, lo, hi, nbins)."""
     parts = str(text).split(":")
@@ -237,54 +211,6 @@ def parse_hist(text: str):
     if not (np.isfinite(lo) and np.isfinite(hi) and hi > lo and nbins >= 1):
         raise ReferenceError_(f"--hist '{text}': needs finite LO < HI and NBINS >= 1")
     return parts[0], lo, hi, nbins
-
-
-# What --hist, --corr and --shape record, in the words of their refusals: (the production run is recorded as ..., the devices
-# do not merge their ..., a re-initialisation falls between ..., the weights' gauge is not held by the ..., why float64 only)
-_RECORDER_WORDS = {
-    "--hist": ("histograms", "histograms", "samples", "counts", "the samples are the device's Float64 microstates"),
-    "--corr": ("correlations", "sums", "records", "sums", "like --hist it is offered for float64 runs only"),
-    "--shape": ("shape columns", "sums", "records", "sums", "like --hist it is offered for float64 runs only"),
-}
-
-
-def _check_recorder(flag: str, pargs: dict, write_csv: bool, devices: int | None, rivals: dict):
-    """The combinations that --hist, --corr and --shape (`flag`) all refuse, for the reasons --error-bars has
-    (check_error_bars): first the `rivals`, {flag: whether it is given}, that record the production run themselves."""
-    recorded_as, merged, between, held_by, float64_only = _RECORDER_WORDS[flag]
-    if devices is None:
-        devices = len([d for d in str(pargs["devices"]).split(",") if d != ""][:max(1, int(pargs["num-chains"]))])
-    for rival, given in rivals.items():
-        if given:
-            raise ReferenceError_(f"{flag} cannot be combined with {rival}: each records the production run in its own way")
-    if write_csv:
-        raise ReferenceError_(f"{flag} cannot be combined with --csv: the production run is recorded as {recorded_as}, not as "
-                              "--stepout rows")
-    if devices > 1:
-        raise ReferenceError_(f"{flag} needs one device, not {devices}: the devices hold different chains of a case and "
-                              f"their {merged} are not merged")
-    if int(pargs.get("num-inits", 1)) != 1:
-        raise ReferenceError_(f"{flag} cannot be combined with --num-inits {pargs['num-inits']}: a re-initialisation "
-                              f"between {between} is not a stationary series")
-    if pargs["umbrella-sampling"]:
-        raise ReferenceError_(f"{flag} cannot be combined with --umbrella-sampling: the samples carry per-chain weights whose "
-                              f"gauge the {held_by} do not hold")
-    if pargs["numeric-type"] != "float64":
-        raise ReferenceError_(f"{flag} cannot be combined with --numeric-type {pargs['numeric-type']}: {float64_only}")
-
-
-def check_hist(pargs: dict, specs, write_csv: bool = False, devices: int | None = None, error_bars: int = 0):
-    """What --hist (tools/run_sweep.py; run_cases(..., hist=[...])) cannot be combined with, refused before any GPU work: what
-    --error-bars cannot, for the same reasons (check_error_bars), and --error-bars itself."""
-    if not 1 <= len(specs) <= _lib.HIST_MAX_SPECS:
-        raise ReferenceError_(f"--hist: between 1 and {_lib.HIST_MAX_SPECS} histograms, not {len(specs)}")
-    if sum(s[3] for s in specs) > _lib.HIST_MAX_BINS:
-        raise ReferenceError_(f"--hist: {sum(s[3] for s in specs)} bins per case, at most {_lib.HIST_MAX_BINS}")
-    stepout = int(pargs["stepout"])
-    if not 1 <= stepout <= int(pargs["num-steps"]):
-        raise ReferenceError_(f"--hist samples every --stepout steps of the production run: --stepout {stepout} must be in 1 .. "
-                              f"--num-steps {pargs['num-steps']}")
-    _check_recorder("--hist", pargs, write_csv, devices, {"--error-bars": error_bars})
 
 
 CORR_MIN_RECORDS = 32      # the blocking transform's default min_blocks: a .corr's standard errors need that many records
@@ -302,26 +228,6 @@ def parse_corr(text: str):
         raise ReferenceError_(f"--corr '{text}' not understood: MAXLAG[:CHANNELS] with MAXLAG >= 0 and CHANNELS a comma-separated "
                               f"choice of {', '.join(_lib.CORR_NAMES)}")
     return max_lag, tuple(c for c in _lib.CORR_NAMES if c in names)
-
-
-def check_corr(pargs: dict, spec, write_csv: bool = False, devices: int | None = None, error_bars: int = 0, hist=None):
-    """What --corr (tools/run_sweep.py; run_cases(..., corr=(max_lag, channels))) cannot be combined with, refused before any GPU
-    work: what --hist cannot, for the same reasons (check_hist), --hist itself, a lag beyond n - 1 and a run of fewer records
-    than the blocked standard errors need."""
-    max_lag = spec[0]
-    if max_lag > int(pargs["num-monomers"]) - 1:
-        raise ReferenceError_(f"--corr: lag {max_lag} is beyond n - 1 = {int(pargs['num-monomers']) - 1}")
-    _check_records("--corr", pargs)
-    _check_recorder("--corr", pargs, write_csv, devices, {"--error-bars": error_bars, "--hist": hist})
-
-
-def _check_records(flag: str, pargs: dict):
-    """--corr and --shape (`flag`) keep a row per record: the run must give the blocking transform enough of them."""
-    stepout = int(pargs["stepout"])
-    if not 1 <= stepout <= int(pargs["num-steps"]) or int(pargs["num-steps"]) // stepout < CORR_MIN_RECORDS:
-        raise ReferenceError_(f"{flag} takes a record every --stepout steps of the production run and its standard errors from "
-                              f"at least {CORR_MIN_RECORDS} of them: --stepout {stepout} must be in 1 .. --num-steps "
-                              f"{pargs['num-steps']} / {CORR_MIN_RECORDS}")
 
 
 def parse_shape(text: str):
@@ -346,17 +252,150 @@ def parse_shape(text: str):
     return "shape", q
 
 
-def check_shape(pargs: dict, spec, write_csv: bool = False, devices: int | None = None, error_bars: int = 0, hist=None, corr=None):
-    """What --shape (tools/run_sweep.py; run_cases(..., shape=parse_shape(...))) cannot be combined with, refused before any GPU
-    work: what --corr cannot, for the same reasons (check_corr), --corr itself, and a wave-vector whose phase the library refuses."""
-    if corr:
-        raise ReferenceError_("--shape cannot be combined with --corr: each records the production run in its own way")
+# ---------------------------------------------------------------------------------------------- recording the production run
+@dataclass(frozen=True)
+class Recording:
+    """How the production run is recorded in place of --stepout rows: `kind` names a row of RECORDINGS, `spec` is what the
+    row's `parse` returns (for error_bars the batch count N).  One kind by construction: the kinds exclude each other."""
+    kind: str
+    spec: object
+
+
+def _check_batches(pargs: dict, nbatches: int):
+    if nbatches < 32:
+        raise ReferenceError_(f"--error-bars {nbatches}: the blocking transform needs at least 32 batches")
+    if int(pargs["num-steps"]) < nbatches:
+        raise ReferenceError_(f"--error-bars {nbatches} needs --num-steps >= {nbatches}: a batch is num-steps / {nbatches} steps")
+
+
+def _check_hist_specs(pargs: dict, specs):
+    if not 1 <= len(specs) <= _lib.HIST_MAX_SPECS:
+        raise ReferenceError_(f"--hist: between 1 and {_lib.HIST_MAX_SPECS} histograms, not {len(specs)}")
+    if sum(s[3] for s in specs) > _lib.HIST_MAX_BINS:
+        raise ReferenceError_(f"--hist: {sum(s[3] for s in specs)} bins per case, at most {_lib.HIST_MAX_BINS}")
+    stepout = int(pargs["stepout"])
+    if not 1 <= stepout <= int(pargs["num-steps"]):
+        raise ReferenceError_(f"--hist samples every --stepout steps of the production run: --stepout {stepout} must be in 1 .. "
+                              f"--num-steps {pargs['num-steps']}")
+
+
+def _check_records(flag: str, pargs: dict):
+    """--corr and --shape (`flag`) keep a row per record: the run must give the blocking transform enough of them."""
+    stepout = int(pargs["stepout"])
+    if not 1 <= stepout <= int(pargs["num-steps"]) or int(pargs["num-steps"]) // stepout < CORR_MIN_RECORDS:
+        raise ReferenceError_(f"{flag} takes a record every --stepout steps of the production run and its standard errors from "
+                              f"at least {CORR_MIN_RECORDS} of them: --stepout {stepout} must be in 1 .. --num-steps "
+                              f"{pargs['num-steps']} / {CORR_MIN_RECORDS}")
+
+
+def _check_lags(pargs: dict, spec):
+    if spec[0] > int(pargs["num-monomers"]) - 1:
+        raise ReferenceError_(f"--corr: lag {spec[0]} is beyond n - 1 = {int(pargs['num-monomers']) - 1}")
+    _check_records("--corr", pargs)
+
+
+def _check_wave_vectors(pargs: dict, spec):
     _check_records("--shape", pargs)
-    _check_recorder("--shape", pargs, write_csv, devices, {"--error-bars": error_bars, "--hist": hist})
     reach = float(pargs["mlen"]) * int(pargs["num-monomers"])
-    for v in spec[1]:
+    for v in spec[1]:      # (the library refuses such a phase too)
         if sum(abs(c) for c in v) * reach >= 1.0e5:
             raise ReferenceError_(f"--shape: |q| b n = {sum(abs(c) for c in v) * reach:g} for q = {v} is not below 1e5")
+
+
+def _totals_and_error_bars(g):
+    """What a Corr or a Shape with kept rows gives at the end of a recorded run."""
+    return g.read(), g.error_bars(min_blocks=CORR_MIN_RECORDS)
+
+
+def _every_stepout(nsteps, spec, stepout):
+    return nsteps // stepout, stepout
+
+
+@dataclass(frozen=True)
+class _Kind:
+    """Everything that is particular to one kind of Recording."""
+    flag: str
+    ext: str                        # of the file beside every <case>.out
+    parse: object                   # the flag's value(s) -> spec
+    words: tuple                    # of the shared refusals (check_recording): the production run is recorded as ..., the devices do
+                                    # not merge their ..., a re-initialisation falls between ..., why not under umbrella sampling,
+                                    # why float64 only
+    check: object                   # (pargs, spec): the kind's own refusals
+    records: object                 # (nsteps, spec, --stepout) -> (how many records, how many steps apart)
+    open: object                    # (ensemble, spec, records) -> the recorder
+    advance: object                 # (ensemble, recorder, nsteps, stepout): the Ensemble.advance_* that drives it
+    read: object                    # recorder -> what info[kind] holds at the end
+    lines: object                   # (main, that, spec, k, case k's pargs) -> the lines of the file
+    restore_after_failure: bool = True      # a failed recorded run puts the checkpoint back
+
+
+_GAUGE = "the samples carry per-chain weights whose gauge the %s do not hold"
+_LIKE_HIST = "like --hist it is offered for float64 runs only"
+RECORDINGS = {
+    "error_bars": _Kind(
+        flag="--error-bars", ext=".err", parse=int,
+        words=("batches", "series", "batches", "the recorded means are ratios with per-chain normalizers that the rows do not hold",
+               "the batches are differences of the device's Float64 reductions"),
+        check=_check_batches,
+        records=lambda nsteps, n, stepout: (n, nsteps // n),
+        open=lambda e, n, nrec: e.open_series(n),
+        advance=Ensemble.advance_series,
+        read=lambda series: series.error_bars(),
+        lines=lambda main, eb, n, k, p: error_lines(main, eb, k, p),
+        restore_after_failure=False),
+    "hist": _Kind(
+        flag="--hist", ext=".hist", parse=lambda texts: [parse_hist(t) for t in texts],
+        words=("histograms", "histograms", "samples", _GAUGE % "counts", "the samples are the device's Float64 microstates"),
+        check=_check_hist_specs,
+        records=_every_stepout,
+        open=lambda e, specs, nrec: e.open_hist([_lib.hist_spec(channel, nbins, lo, hi) for channel, lo, hi, nbins in specs]),
+        advance=Ensemble.advance_hist,
+        read=lambda h: h.read(),
+        lines=lambda main, res, specs, k, p: hist_lines(res, specs, k, int(p["num-chains"]))),
+    "corr": _Kind(
+        flag="--corr", ext=".corr", parse=parse_corr,
+        words=("correlations", "sums", "records", _GAUGE % "sums", _LIKE_HIST),
+        check=_check_lags,
+        records=_every_stepout,
+        open=lambda e, spec, nrec: e.open_corr(spec[1], spec[0], capacity_rows=nrec),
+        advance=Ensemble.advance_corr,
+        read=_totals_and_error_bars,
+        lines=lambda main, res, spec, k, p: corr_lines(*res, k)),
+    "shape": _Kind(
+        flag="--shape", ext=".shape", parse=parse_shape,
+        words=("shape columns", "sums", "records", _GAUGE % "sums", _LIKE_HIST),
+        check=_check_wave_vectors,
+        records=_every_stepout,
+        open=lambda e, spec, nrec: e.open_shape(spec[1], capacity_rows=nrec),
+        advance=Ensemble.advance_shape,
+        read=_totals_and_error_bars,
+        lines=lambda main, res, spec, k, p: shape_lines(*res, k)),
+}
+
+
+def check_recording(pargs: dict, rec: Recording, write_csv: bool = False, devices: int | None = None):
+    """What a Recording (tools/run_sweep.py's --error-bars, --hist, --corr, --shape; run_cases(..., record=rec)) cannot be
+    combined with, refused before any GPU work: the kind's own limits, then what all kinds refuse.  `devices`: how many hold the
+    chains (default: those --devices names)."""
+    row = RECORDINGS[rec.kind]
+    flag = row.flag
+    recorded_as, merged, between, no_umbrella, float64_only = row.words
+    if devices is None:
+        devices = len([d for d in str(pargs["devices"]).split(",") if d != ""][:max(1, int(pargs["num-chains"]))])
+    row.check(pargs, rec.spec)
+    if write_csv:
+        raise ReferenceError_(f"{flag} cannot be combined with --csv: the production run is recorded as {recorded_as}, not as "
+                              "--stepout rows")
+    if devices > 1:
+        raise ReferenceError_(f"{flag} needs one device, not {devices}: the devices hold different chains of a case and "
+                              f"their {merged} are not merged")
+    if int(pargs.get("num-inits", 1)) != 1:
+        raise ReferenceError_(f"{flag} cannot be combined with --num-inits {pargs['num-inits']}: a re-initialisation "
+                              f"between {between} is not a stationary series")
+    if pargs["umbrella-sampling"]:
+        raise ReferenceError_(f"{flag} cannot be combined with --umbrella-sampling: {no_umbrella}")
+    if pargs["numeric-type"] != "float64":
+        raise ReferenceError_(f"{flag} cannot be combined with --numeric-type {pargs['numeric-type']}: {float64_only}")
 
 
 def burn_ladder(pargs: dict) -> list[float]:
@@ -422,11 +461,6 @@ def _averagers(s):
 
 
 # ---------------------------------------------------------------------------------------------- the pool
-def _totals_and_error_bars(g):
-    """What a Corr or a Shape with kept rows gives at the end of a recorded run."""
-    return g.read(), g.error_bars(min_blocks=CORR_MIN_RECORDS)
-
-
 class _Pool:
     """The cases of one ensemble -- one for the command line, many for a sweep (polymer_stats_amd/sweep.py; they differ only
     in their physics scalars, pstat_create) --, every case's chains sharded over one or more devices in this process;
@@ -551,69 +585,36 @@ class _Pool:
             if tick:
                 tick(nsteps)
 
-    def error_bars(self, nsteps, nbatches):
-        """advance(nsteps), recorded on the device as exactly `nbatches` batches of nsteps // nbatches steps (no angles; the
-        remainder, nsteps % nbatches steps, is not part of any batch) -> the blocked standard errors of every case
-        (Series.error_bars).  Called where the
-        averages are empty (after burn_in / stage / creation), so the rows' differences are the batch means.  The chains
-        are sharded over one device only: the shards of a case hold different chains, and their series are not merged.
-        The run is made TWICE from the same state: recorded for the error bars, then, from a checkpoint taken before it, as
-        the one launch of advance(nsteps), which leaves the handle -- and so the averages the caller prints -- exactly as
-        a run without error bars does.  (Recording leaves trajectories alone, but N launches add the running sums in another
-        order than one launch: the step kernels fold them in blocks that start at a launch's first step.)"""
-        check_error_bars(self.plist[0], nbatches, devices=len(self.parts))
-        return self._recorded_twice(nsteps, nbatches, nsteps // nbatches, lambda e: e.open_series(nbatches), Ensemble.advance_series,
-                                    lambda series: series.error_bars(), restore_after_failure=False)
-
-    def _recorded_twice(self, nsteps, nrec, stepout, open_, advance, read, restore_after_failure=True):
-        """advance(nsteps), made TWICE from the same state, as error_bars explains: first `nrec` records `stepout` steps apart
-        (the remainder would be lost with the restore anyway) into the recorder that `open_(ensemble)` opens, by
-        `advance(ensemble, recorder, nsteps, stepout)`; then, from a checkpoint taken before it, as the one launch of
-        advance(nsteps).  Returns `read(recorder)`.  The recorder is closed whatever happens; the checkpoint is put back also when
-        the recorded run failed, so that the handle is never left mid-run (error_bars alone leaves a failed run where it stopped)."""
+    def record(self, nsteps, rec):
+        """advance(nsteps), made TWICE from the same state: first recorded on the device the way `rec` (a Recording) says -- as the
+        records its row of RECORDINGS counts, so many steps apart (error_bars: exactly N batches of nsteps // N steps; the others:
+        a record after every --stepout-th step; a remainder belongs to no record), into the recorder the row opens, by the row's
+        Ensemble.advance_* --; then, from a checkpoint taken before it, as the one launch of advance(nsteps), which leaves the
+        handle -- and so the averages the caller prints -- exactly as a run without a recording does.  (Recording leaves
+        trajectories alone, but N launches add the running sums in another order than one launch: the step kernels fold them in
+        blocks that start at a launch's first step.)  Returns what the row reads at the end (error_bars: the blocked standard
+        errors of every case, Series.error_bars; hist: HistResult; corr, shape: (CorrResult | ShapeResult, ErrorBars of the rows)).
+        Called where the averages are empty (after burn_in / stage / creation), so an error_bars row's differences are the batch
+        means.  The chains are on one device only: the shards of a case hold different chains, and their records are not merged.
+        The recorder is closed whatever happens; the checkpoint is put back also when the recorded run failed, so that the handle
+        is never left mid-run (error_bars alone leaves a failed run where it stopped)."""
+        check_recording(self.plist[0], rec, devices=len(self.parts))
+        row = RECORDINGS[rec.kind]
+        nrec, stepout = row.records(nsteps, rec.spec, int(self.plist[0]["stepout"]))
         e = self.parts[0]
         image = e.checkpoint()
-        recorder = open_(e)
+        recorder = row.open(e, rec.spec, nrec)
         done = False
         try:
-            advance(e, recorder, nrec * stepout, stepout)
-            res = read(recorder)
+            row.advance(e, recorder, nrec * stepout, stepout)
+            res = row.read(recorder)
             done = True
         finally:
             recorder.close()
-            if done or restore_after_failure:
+            if done or row.restore_after_failure:
                 e.restore(image)
         self.advance(nsteps)
         return res
-
-    def histograms(self, nsteps, stepout, specs):
-        """advance(nsteps) with every chain's configuration added, after every `stepout`-th step, to the histograms `specs`
-        ((channel name, lo, hi, nbins), shared by all cases) on the device -> HistResult.  Made TWICE from the same state like
-        error_bars, and for the same reason, so that the averages the caller prints are exactly those of a run without
-        histograms."""
-        check_hist(self.plist[0], specs, devices=len(self.parts))
-        return self._recorded_twice(
-            nsteps, nsteps // stepout, stepout,
-            lambda e: e.open_hist([_lib.hist_spec(channel, nbins, lo, hi) for channel, lo, hi, nbins in specs]),
-            Ensemble.advance_hist, lambda h: h.read())
-
-    def correlations(self, nsteps, stepout, spec):
-        """advance(nsteps) with one record of the lag correlations `spec` = (max_lag, channel names) after every `stepout`-th
-        step, rows kept -> (CorrResult, ErrorBars of the rows).  Made TWICE from the same state like histograms, and for the
-        same reason."""
-        check_corr(self.plist[0], spec, devices=len(self.parts))
-        nrec = nsteps // stepout
-        return self._recorded_twice(nsteps, nrec, stepout, lambda e: e.open_corr(spec[1], spec[0], capacity_rows=nrec),
-                                    Ensemble.advance_corr, _totals_and_error_bars)
-
-    def shapes(self, nsteps, stepout, spec):
-        """advance(nsteps) with one record of the gyration block and of S at the wave-vectors of `spec` = parse_shape(...) after
-        every `stepout`-th step, rows kept -> (ShapeResult, ErrorBars of the rows).  Made TWICE from the same state like
-        correlations, and for the same reason."""
-        check_shape(self.plist[0], spec, devices=len(self.parts))
-        nrec = nsteps // stepout
-        return self._recorded_twice(nsteps, nrec, stepout, lambda e: e.open_shape(spec[1], capacity_rows=nrec),
-                                    Ensemble.advance_shape, _totals_and_error_bars)
 
     def chain0(self, k=0):
         return self.parts[0].chain_state(k * self.counts[0])      # the first chain of case k
@@ -707,18 +708,14 @@ class CsvFiles:
 
 
 def recorded_stage(pool, nsteps, write: bool, traj_header, roll_header, rows, angles=False, runs=(None,), report=None,
-                   error_bars: int = 0, hist=None, corr=None, shape=None):
+                   record=None):
     """One recorded run of `nsteps` for every case of the pool, the body of the reference's mcmc(nsteps, pargs[, chain]):
     with `write` the two CSV files of every case (headers `traj_header(pargs)` and `roll_header`, a row per --stepout
     steps: `rows(pargs, step, micro, ang, summary)` -> the case's (trajectory row, rolling row)), then the summaries, the
     total time and the acceptance rates on stderr (`report(k, summary)` right after case k's rate).  `runs` yields the
     progress line of each run of `nsteps` into the same files (the fixed-force main's inits; it is resumed after the run).
-    `error_bars` = N > 0 (without `write`): the run is recorded as N batches instead (_Pool.error_bars) and the pool's `info`
-    gets their blocked standard errors under "error_bars".  `hist` = [(channel, lo, hi, nbins), ...] (without `write`): every
-    chain is histogrammed every --stepout steps of the run (_Pool.histograms) and `info` gets the HistResult under "hist".  `corr` = (max_lag, channels)
-    (without `write`): the lag correlations are recorded every --stepout steps (_Pool.correlations) and `info` gets the
-    (CorrResult, ErrorBars) under "corr".  `shape` = parse_shape(...) (without `write`): likewise the gyration block and the form
-    factor (_Pool.shapes), `info` gets the (ShapeResult, ErrorBars) under "shape"."""
+    `record` = a Recording (without `write`): the run is recorded its way instead (_Pool.record) and the pool's `info` gets what
+    that returns under the recording's kind ("error_bars" | "hist" | "corr" | "shape")."""
     plist = pool.plist
     pargs = plist[0]
     stepout = int(pargs["stepout"]) if write else 0
@@ -736,25 +733,10 @@ def recorded_stage(pool, nsteps, write: bool, traj_header, roll_header, rows, an
                         _log(pargs, 3, "Info", progress)
                     _log(pargs, 3, "Info", f"step:    {step} / {nsteps}")
                     last_update[0] = time.time()
-            if error_bars:
-                eb = pool.error_bars(nsteps, error_bars)
+            if record:
+                res = pool.record(nsteps, record)
                 if pool.info is not None:
-                    pool.info["error_bars"] = eb
-                continue
-            if hist:
-                res = pool.histograms(nsteps, int(pargs["stepout"]), hist)
-                if pool.info is not None:
-                    pool.info["hist"] = res
-                continue
-            if corr:
-                res = pool.correlations(nsteps, int(pargs["stepout"]), corr)
-                if pool.info is not None:
-                    pool.info["corr"] = res
-                continue
-            if shape:
-                res = pool.shapes(nsteps, int(pargs["stepout"]), shape)
-                if pool.info is not None:
-                    pool.info["shape"] = res
+                    pool.info[record.kind] = res
                 continue
             for step, micro, ang, sums in pool.recorded(nsteps, stepout, angles=angles, tick=tick):
                 for k in range(len(files)):

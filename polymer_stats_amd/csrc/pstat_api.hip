@@ -1413,18 +1413,18 @@ int pstat_corr_open(pstat_handle *h, int32_t channels, int32_t max_lag, int64_t 
   if (h->cfg.umbrella)
     return fail(PSTAT_ERR_UNSUPPORTED, "correlations under --umbrella-sampling: the samples carry per-chain weights whose gauge "
                 "the sums do not hold");
-  if (n > corr_max_n(h->cfg.planar))
+  if (n > tile_max_n(h->cfg.planar))
     return fail(PSTAT_ERR_UNSUPPORTED, "n = %lld: a chain's unit vectors must fit the LDS of a workgroup, n <= %lld for a %s handle",
-                (long long)n, (long long)corr_max_n(h->cfg.planar), h->cfg.planar ? "planar" : "3D");
+                (long long)n, (long long)tile_max_n(h->cfg.planar), h->cfg.planar ? "planar" : "3D");
   if (max_lag < 0) max_lag = (int32_t)(n - 1);
   const int nch = (channels & 1) + ((channels >> 1) & 1) + ((channels >> 2) & 1);
   CorrArgs a{};
   a.per = h->base.num_chains; a.ncases = h->ncases; a.n = n;
   a.channels = channels; a.max_lag = max_lag; a.ncols = nch * (max_lag + 1);
   a.elem = (int32_t)h->elem; a.planar = h->cfg.planar ? 1 : 0; a.polar = h->cfg.chain_type == PSTAT_POLAR ? 1 : 0;
-  corr_shape(a);
+  tile_layout(a, max_lag + 1);
   std::unique_ptr<pstat_corr> g;
-  PSTAT_TRY(new_totals(h, a.ncols, capacity_rows, corr_partial_doubles(a), kCorrText, g));
+  PSTAT_TRY(new_totals(h, a.ncols, capacity_rows, tile_partial_doubles(a), kCorrText, g));
   g->args = a;
   return adopt(h->corrs, g, out);
 }
@@ -1479,16 +1479,16 @@ int pstat_shape_open(pstat_handle *h, const double *q, int32_t nq, int64_t capac
   if (h->cfg.umbrella)
     return fail(PSTAT_ERR_UNSUPPORTED, "chain shape under --umbrella-sampling: the samples carry per-chain weights whose gauge "
                 "the sums do not hold");
-  if (n > corr_max_n(h->cfg.planar))
+  if (n > tile_max_n(h->cfg.planar))
     return fail(PSTAT_ERR_UNSUPPORTED, "n = %lld: a chain's positions must fit the LDS of a workgroup, n <= %lld for a %s handle",
-                (long long)n, (long long)corr_max_n(h->cfg.planar), planar ? "planar" : "3D");
+                (long long)n, (long long)tile_max_n(h->cfg.planar), planar ? "planar" : "3D");
   ShapeArgs a{};
   a.per = h->base.num_chains; a.ncases = h->ncases; a.n = n;
   a.nq = nq; a.ncols = PSTAT_SHAPE_GYR + nq;
   a.elem = (int32_t)h->elem; a.planar = planar ? 1 : 0;
-  shape_layout(a);
+  tile_layout(a, nq);
   std::unique_ptr<pstat_shape> g;
-  PSTAT_TRY(new_totals(h, a.ncols, capacity_rows, shape_partial_doubles(a), kShapeText, g));
+  PSTAT_TRY(new_totals(h, a.ncols, capacity_rows, tile_partial_doubles(a), kShapeText, g));
   g->args = a;
   if (nq > 0) {   // the wave-vectors: a copy, the caller's table may go
     hipError_t e = g->d_q.malloc(3 * (size_t)nq);

@@ -25,10 +25,12 @@
 //       A thread reads n_i (the same word for the whole group: a broadcast) and n_{i+k} (consecutive words over the group:
 //       conflict-free) and forms mu on the fly, so LDS holds nothing but the unit vectors.  The groups' sums are then added in
 //       order of g from 0.0 by group 0 through 4 KiB of LDS, and the tile's partial leaves as partial[tile][sum | sumsq][column].
-//   corr_stage2   one wavefront per (case, column): lane l adds the partials of the case's tiles l, l + 64, ... in order from
+//   tile_fold     one wavefront per (case, column): lane l adds the partials of the case's tiles l, l + 64, ... in order from
 //       0.0, wave_sum's tree follows, lane 0 adds the two results to the running totals it alone owns and writes the row's mean.
 // A chain's vectors must fit the 64 KiB a workgroup is given beside the 4 KiB of scratch: n <= 2560 for a 3D handle, n <= 3840
-// for a planar one (corr_max_n); pstat_corr_open refuses longer chains.
+// for a planar one (tile_max_n); pstat_corr_open refuses longer chains.
+// The tile frame -- the layout rule, phase 1, the groups' fold and tile_fold -- is the shape recorder's too: pstat_tile.h states
+// the device pieces, this file defines the host ones and the fold kernel.
 // It reads DevState::ang and the case table only and writes the correlation object's own buffers only.
 // Plain HIP C++; sincos_f64 (pstat_math.h) is the < 1 ulp one the initialisation kernels use.
 #include <hip/hip_runtime.h>
@@ -36,53 +38,22 @@
 #include "../../include/pstat.h"
 #include "pstat_device.h"
 #include "pstat_math.h"
+#include "pstat_tile.h"
 
 namespace pstat {
 
 namespace {
 
-constexpr int CTHREADS = 256;
-constexpr int CORR_TILE = 16;                       // chains per workgroup at most
-constexpr size_t CORR_LDS = 65536;                  // what a workgroup may have
-constexpr size_t CORR_SCRATCH = 2 * CTHREADS * sizeof(double);   // the groups' sums on their way to group 0
-
-// monomers of a chain as LDS keeps them: odd where several chains share a tile, so that the phase-1 stores of consecutive chains
-// do not meet in one bank
-__host__ __device__ inline int64_t padded_n(const int64_t n, const int tile_chains) { return tile_chains > 1 ? (n | 1) : n; }
-
 template <bool PLANAR, bool MM>
-__global__ __launch_bounds__(CTHREADS) void corr_stage1(const CorrArgs a, const void *__restrict__ ang,
-                                                        const CaseConst *__restrict__ cases, double *__restrict__ partial) {
+__global__ __launch_bounds__(TILE_THREADS) void corr_stage1(const CorrArgs a, const void *__restrict__ ang,
+                                                            const CaseConst *__restrict__ cases, double *__restrict__ partial) {
   extern __shared__ double lds[];
-  double *s1 = lds, *s2 = lds + CTHREADS;
   const int t = threadIdx.x;
-  const int64_t kcase = (int64_t)blockIdx.x / a.tiles, tile = (int64_t)blockIdx.x % a.tiles;
-  const int64_t first = tile * a.tile_chains;                       // the tile's first chain within its case
-  const int64_t left = a.per - first;
-  const int tc = (int)(left < a.tile_chains ? left : a.tile_chains);  // chains this tile holds
-  const int64_t c0 = kcase * a.per + first, C = a.ncases * a.per;
-  const int n = (int)a.n, ns = (int)padded_n(a.n, a.tile_chains);
-  // vx[q][i], (vy[q][i],) vz[q][i] for chain q of the tile
-  double *vx = lds + 2 * CTHREADS;
-  double *vz = vx + (int64_t)a.tile_chains * ns;
-  double *vy = vz + (int64_t)a.tile_chains * ns;                    // 3D only
-
-  for (int e = t; e < tc * n; e += CTHREADS) {
-    const int q = e % tc, i = e / tc;
-    double sp, cp;
-    sincos_f64(load_angle(ang, ((int64_t)n + i) * C + c0 + q, (size_t)a.elem, false), &sp, &cp);
-    if constexpr (PLANAR) {
-      vx[q * ns + i] = cp;
-      vz[q * ns + i] = sp;
-    } else {
-      double st, ct;
-      sincos_f64(load_angle(ang, (int64_t)i * C + c0 + q, (size_t)a.elem, true), &st, &ct);
-      vx[q * ns + i] = cp * st;
-      vy[q * ns + i] = sp * st;
-      vz[q * ns + i] = ct;
-    }
-  }
-  __syncthreads();
+  const Tile w = tile_of(a, lds);
+  tile_unit_vectors<PLANAR>(a, w, ang);
+  const int64_t kcase = w.kcase;
+  const int n = (int)a.n, tc = w.tc, ns = w.ns;
+  const double *vx = w.x, *vz = w.z, *vy = w.y;
 
   // mu = f n + mb z with f = ma * n_z (dielectric) or mu (polar)
   double ma = 0.0, mb = 0.0;
@@ -130,15 +101,7 @@ __global__ __launch_bounds__(CTHREADS) void corr_stage1(const CorrArgs a, const 
     for (int ch = 0; ch < 3; ++ch) {
       if (!(a.channels & (1 << ch))) continue;
       double r1 = a1[ch], r2 = a2[ch];
-      if (a.groups > 1) {
-        s1[t] = r1; s2[t] = r2;
-        __syncthreads();
-        if (g == 0 && active) {
-          r1 = 0.0; r2 = 0.0;
-          for (int gg = 0; gg < a.groups; ++gg) { r1 += s1[sub + gg * a.lpc]; r2 += s2[sub + gg * a.lpc]; }
-        }
-        __syncthreads();   // the scratch is rewritten for the next channel
-      }
+      tile_group_fold(a, lds, sub, g, active, r1, r2);
       if (g == 0 && active) {
         mine[col * width + k] = r1;
         mine[ncols + col * width + k] = r2;
@@ -150,55 +113,68 @@ __global__ __launch_bounds__(CTHREADS) void corr_stage1(const CorrArgs a, const 
 
 }  // namespace
 
-// wave w of the grid takes (case, column) w (declared in pstat_device.h: the shape recorder's fold is this kernel too)
-__global__ __launch_bounds__(CTHREADS) void corr_stage2(const CorrArgs a, const double *__restrict__ partial,
-                                                        double *__restrict__ totals, double *__restrict__ row) {
+// wave w of the grid takes (case, column) w
+__global__ __launch_bounds__(TILE_THREADS) void tile_fold(const int64_t ncases, const int64_t ncols, const int64_t tiles,
+                                                          const int64_t per, const double *__restrict__ partial,
+                                                          double *__restrict__ totals, double *__restrict__ row) {
   const int lane = threadIdx.x & 63;
-  const int64_t w = (int64_t)blockIdx.x * (CTHREADS / 64) + (threadIdx.x >> 6);
-  const int64_t ncols = a.ncols;
-  if (w >= a.ncases * ncols) return;
+  const int64_t w = (int64_t)blockIdx.x * (TILE_THREADS / 64) + (threadIdx.x >> 6);
+  if (w >= ncases * ncols) return;
   const int64_t kcase = w / ncols, col = w % ncols;
-  const double *p = partial + kcase * a.tiles * 2 * ncols + col;
+  const double *p = partial + kcase * tiles * 2 * ncols + col;
   double r1 = 0.0, r2 = 0.0;
-  for (int64_t tile = lane; tile < a.tiles; tile += 64) {
+  for (int64_t tile = lane; tile < tiles; tile += 64) {
     r1 += p[tile * 2 * ncols];
     r2 += p[tile * 2 * ncols + ncols];
   }
   r1 = wave_sum(r1);
   r2 = wave_sum(r2);
   if (lane == 0) {
-    totals[w] += r1;                       // sum[ncases][ncols]
-    totals[a.ncases * ncols + w] += r2;    // sumsq[ncases][ncols]
-    if (row) row[w] = r1 / (double)a.per;
+    totals[w] += r1;                     // sum[ncases][ncols]
+    totals[ncases * ncols + w] += r2;    // sumsq[ncases][ncols]
+    if (row) row[w] = r1 / (double)per;
   }
 }
 
-int64_t corr_max_n(int planar) { return (int64_t)((CORR_LDS - CORR_SCRATCH) / ((planar ? 2 : 3) * sizeof(double))); }
+hipError_t launch_tile_fold(const TileArgs &a, const double *partial, double *totals, double *row, hipStream_t stream) {
+  const int64_t waves = a.ncases * a.ncols;
+  tile_fold<<<dim3((unsigned)((waves + TILE_THREADS / 64 - 1) / (TILE_THREADS / 64))), dim3(TILE_THREADS), 0, stream>>>(
+      a.ncases, a.ncols, a.tiles, a.per, partial, totals, row);
+  return hipGetLastError();
+}
 
-void corr_shape(CorrArgs &a) {
-  const int comps = a.planar ? 2 : 3;
-  int tc = (int)(a.per < CORR_TILE ? a.per : CORR_TILE);
-  while (tc > 1 && CORR_SCRATCH + (size_t)tc * (size_t)padded_n(a.n, tc) * comps * sizeof(double) > CORR_LDS) --tc;
+int64_t tile_max_n(int planar) { return (int64_t)((TILE_LDS - TILE_SCRATCH) / ((planar ? 2 : 3) * sizeof(double))); }
+
+void tile_layout(TileArgs &a, const int width) {
+  int tc = (int)(a.per < TILE_CHAINS ? a.per : TILE_CHAINS);
+  while (tc > 1 && tile_lds_bytes(a.n, tc, a.planar) > TILE_LDS) --tc;
   a.tile_chains = tc;
   a.tiles = (a.per + tc - 1) / tc;
   int lpc = 1;
-  while (lpc < CTHREADS && lpc < a.max_lag + 1) lpc *= 2;
+  while (lpc < TILE_THREADS && lpc < width) lpc *= 2;
   a.lpc = lpc;
-  a.groups = CTHREADS / lpc;
-  a.nslots = (a.max_lag + lpc) / lpc;
+  a.groups = TILE_THREADS / lpc;
+  a.nslots = (width + lpc - 1) / lpc;
 }
 
-size_t corr_partial_doubles(const CorrArgs &a) { return (size_t)a.ncases * (size_t)a.tiles * 2 * (size_t)a.ncols; }
+size_t tile_partial_doubles(const TileArgs &a) { return (size_t)a.ncases * (size_t)a.tiles * 2 * (size_t)a.ncols; }
+
+hipError_t tile_launch_shape(const TileArgs &a, int64_t *blocks, size_t *lds) {
+  *blocks = a.ncases * a.tiles > 0 ? a.ncases * a.tiles : 0;
+  *lds = tile_lds_bytes(a.n, a.tile_chains, a.planar);
+  if (*blocks > 0x7fffffffll || *lds > TILE_LDS || a.tile_chains > TILE_CHAINS || a.lpc * a.groups != TILE_THREADS)
+    return hipErrorInvalidConfiguration;
+  return hipSuccess;
+}
 
 hipError_t launch_corr(const CorrArgs &a, const void *ang, const CaseConst *cases, double *partial, double *totals, double *row,
                        hipStream_t stream) {
-  const int64_t blocks = a.ncases * a.tiles;
-  if (blocks <= 0) return hipSuccess;
-  if (blocks > 0x7fffffffll) return hipErrorInvalidConfiguration;
-  const size_t lds = CORR_SCRATCH + (size_t)a.tile_chains * (size_t)padded_n(a.n, a.tile_chains) * (a.planar ? 2 : 3) * sizeof(double);
-  if (lds > CORR_LDS) return hipErrorInvalidConfiguration;
+  int64_t blocks;
+  size_t lds;
+  hipError_t e = tile_launch_shape(a, &blocks, &lds);
+  if (e != hipSuccess || blocks == 0) return e;
   const bool mm = (a.channels & PSTAT_CORR_MM) != 0;
-  const dim3 grid((unsigned)blocks), block(CTHREADS);
+  const dim3 grid((unsigned)blocks), block(TILE_THREADS);
   if (a.planar) {
     if (mm) corr_stage1<true, true><<<grid, block, lds, stream>>>(a, ang, cases, partial);
     else corr_stage1<true, false><<<grid, block, lds, stream>>>(a, ang, cases, partial);
@@ -206,11 +182,9 @@ hipError_t launch_corr(const CorrArgs &a, const void *ang, const CaseConst *case
     if (mm) corr_stage1<false, true><<<grid, block, lds, stream>>>(a, ang, cases, partial);
     else corr_stage1<false, false><<<grid, block, lds, stream>>>(a, ang, cases, partial);
   }
-  hipError_t e = hipGetLastError();
+  e = hipGetLastError();
   if (e != hipSuccess) return e;
-  const int64_t waves = a.ncases * a.ncols;
-  corr_stage2<<<dim3((unsigned)((waves + CTHREADS / 64 - 1) / (CTHREADS / 64))), block, 0, stream>>>(a, partial, totals, row);
-  return hipGetLastError();
+  return launch_tile_fold(a, partial, totals, row, stream);
 }
 
 }  // namespace pstat

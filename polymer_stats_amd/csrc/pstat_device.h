@@ -399,46 +399,39 @@ struct HistArgs {
 hipError_t launch_hist(const HistArgs &a, const double *src, const HistSpec *specs, int64_t *counts, int64_t *tails,
                        hipStream_t stream);
 
-// Per-case lag correlations of the chains' current orientations and dipoles (pstat_corr.hip states the contract; DESIGN.md 3.15).
-struct CorrArgs {
+// The tile frame the correlation and the shape recorder share (pstat_tile.h): a workgroup takes a tile of consecutive chains of
+// one case, and its 256 threads are `groups` groups of `lpc` threads over the columns of the kind's hot loop.
+struct TileArgs {
   int64_t per, ncases, n;      // chains per case, cases, monomers
   int64_t tiles;               // workgroups per case: ceil(per / tile_chains)
-  int32_t channels;            // PSTAT_CORR_* mask
-  int32_t max_lag;
-  int32_t ncols;               // (max_lag + 1) * channels set
-  int32_t elem;                // bytes per stored angle of DevState::ang
-  int32_t planar, polar;
-  int32_t tile_chains;         // chains per workgroup
-  int32_t lpc, groups, nslots; // threads per group, groups per workgroup (lpc * groups = 256), lags per thread
-};
-// fills tiles, tile_chains, lpc, groups, nslots from the other fields: the shape of the reduction, which is part of the result
-void corr_shape(CorrArgs &a);
-// the longest chain whose unit vectors fit a workgroup's LDS
-int64_t corr_max_n(int planar);
-size_t corr_partial_doubles(const CorrArgs &a);
-// one record: totals[2][ncases][ncols] (sum, then sumsq) += this record's, row[ncases][ncols] (unless null) = the cases' means
-hipError_t launch_corr(const CorrArgs &a, const void *ang, const CaseConst *cases, double *partial, double *totals, double *row,
-                       hipStream_t stream);
-// the fold over the tiles of one record (defined in pstat_corr.hip; pstat_shape.hip launches it too): one wavefront per
-// (case, column) in workgroups of 256 threads.  It reads a.ncases, a.ncols, a.tiles and a.per only; partial is
-// [ncases][tiles][sum | sumsq][ncols].
-__global__ void corr_stage2(const CorrArgs a, const double *__restrict__ partial, double *__restrict__ totals,
-                            double *__restrict__ row);
-
-// Per-case gyration tensor and form factor of the chains' current positions (pstat_shape.hip states the contract; DESIGN.md 3.16).
-struct ShapeArgs {
-  int64_t per, ncases, n;      // chains per case, cases, monomers
-  int64_t tiles;               // workgroups per case: ceil(per / tile_chains)
-  int32_t nq;                  // wave-vectors
-  int32_t ncols;               // PSTAT_SHAPE_GYR + nq
+  int32_t ncols;               // columns of a case's record
   int32_t elem;                // bytes per stored angle of DevState::ang
   int32_t planar;
   int32_t tile_chains;         // chains per workgroup
-  int32_t lpc, groups, nslots; // threads per group, groups per workgroup (lpc * groups = 256), wave-vectors per thread
+  int32_t lpc, groups, nslots; // threads per group, groups per workgroup (lpc * groups = 256), columns per thread
 };
-// fills tiles, tile_chains, lpc, groups, nslots from the other fields: the shape of the reduction, which is part of the result
-void shape_layout(ShapeArgs &a);
-size_t shape_partial_doubles(const ShapeArgs &a);
+// fills tiles, tile_chains, lpc, groups, nslots from the other fields and the `width` of the hot loop (lags, wave-vectors): 16
+// chains per tile, fewer where a case has fewer or LDS is short; lpc = min(256, 2^ceil(log2 width)).  The shape of the
+// reduction, which is part of the result
+void tile_layout(TileArgs &a, int width);
+// the longest chain whose unit vectors fit a workgroup's LDS
+int64_t tile_max_n(int planar);
+size_t tile_partial_doubles(const TileArgs &a);
+
+// Per-case lag correlations of the chains' current orientations and dipoles (pstat_corr.hip states the contract; DESIGN.md 3.15).
+struct CorrArgs : TileArgs {   // ncols = (max_lag + 1) * channels set; tile_layout's width = max_lag + 1
+  int32_t channels;            // PSTAT_CORR_* mask
+  int32_t max_lag;
+  int32_t polar;
+};
+// one record: totals[2][ncases][ncols] (sum, then sumsq) += this record's, row[ncases][ncols] (unless null) = the cases' means
+hipError_t launch_corr(const CorrArgs &a, const void *ang, const CaseConst *cases, double *partial, double *totals, double *row,
+                       hipStream_t stream);
+
+// Per-case gyration tensor and form factor of the chains' current positions (pstat_shape.hip states the contract; DESIGN.md 3.16).
+struct ShapeArgs : TileArgs {  // ncols = PSTAT_SHAPE_GYR + nq; tile_layout's width = nq
+  int32_t nq;                  // wave-vectors
+};
 // one record: totals[2][ncases][ncols] (sum, then sumsq) += this record's, row[ncases][ncols] (unless null) = the cases' means;
 // q = the wave-vectors [nq][3] in device memory (may be null when nq = 0)
 hipError_t launch_shape(const ShapeArgs &a, const void *ang, const CaseConst *cases, const double *q, double *partial,

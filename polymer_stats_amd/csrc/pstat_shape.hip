@@ -33,8 +33,9 @@
 //       chains, whose odd padding keeps them in different banks), forms the phase, takes ONE sincos_f64 and keeps sum cos and sum
 //       sin in registers.  The groups' sums are then added in order of g from 0.0 by group 0 through 4 KiB of LDS, and the tile's
 //       partial leaves as partial[tile][sum | sumsq][column].  With nq = 0 the phase is skipped.
-//   corr_stage2   (pstat_corr.hip) the fold over the tiles per (case, column), launched as it is.
-// A chain's positions take the LDS its unit vectors take in corr_stage1: n <= corr_max_n(planar); pstat_shape_open refuses longer
+//   tile_fold     (pstat_corr.hip) the fold over the tiles per (case, column).
+// The tile frame -- the layout rule, phase 1 and the groups' fold -- is the correlation recorder's too (pstat_tile.h).
+// A chain's positions take the LDS its unit vectors take in corr_stage1: n <= tile_max_n(planar); pstat_shape_open refuses longer
 // chains, more than PSTAT_SHAPE_MAX_Q wave-vectors, and a wave-vector whose phase could reach 1e5 (below that sincos_f64 is the
 // < 1 ulp routine).
 // It reads DevState::ang and the case table only and writes the shape object's own buffers only.  Plain HIP C++.
@@ -43,18 +44,11 @@
 #include "../../include/pstat.h"
 #include "pstat_device.h"
 #include "pstat_math.h"
+#include "pstat_tile.h"
 
 namespace pstat {
 
 namespace {
-
-constexpr int STHREADS = 256;
-constexpr int SHAPE_TILE = 16;                      // chains per workgroup at most
-constexpr size_t SHAPE_LDS = 65536;                 // what a workgroup may have
-constexpr size_t SHAPE_SCRATCH = 2 * STHREADS * sizeof(double);   // the chains' gyration values, then the groups' sums
-
-// monomers of a chain as LDS keeps them: odd where several chains share a tile (pstat_corr.hip's padded_n)
-__host__ __device__ inline int64_t shape_padded_n(const int64_t n, const int tile_chains) { return tile_chains > 1 ? (n | 1) : n; }
 
 // inclusive scan over the 64 lanes: the shift-and-add tree whose order is part of every position
 __device__ __forceinline__ double wave_scan(double v, const int lane) {
@@ -67,45 +61,22 @@ __device__ __forceinline__ double wave_scan(double v, const int lane) {
 }
 
 template <bool PLANAR>
-__global__ __launch_bounds__(STHREADS) void shape_stage1(const ShapeArgs a, const void *__restrict__ ang,
-                                                         const CaseConst *__restrict__ cases, const double *__restrict__ qtab,
-                                                         double *__restrict__ partial) {
+__global__ __launch_bounds__(TILE_THREADS) void shape_stage1(const ShapeArgs a, const void *__restrict__ ang,
+                                                             const CaseConst *__restrict__ cases, const double *__restrict__ qtab,
+                                                             double *__restrict__ partial) {
   extern __shared__ double lds[];
-  double *s1 = lds, *s2 = lds + STHREADS;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int64_t kcase = (int64_t)blockIdx.x / a.tiles, tile = (int64_t)blockIdx.x % a.tiles;
-  const int64_t first = tile * a.tile_chains;                       // the tile's first chain within its case
-  const int64_t left = a.per - first;
-  const int tc = (int)(left < a.tile_chains ? left : a.tile_chains);  // chains this tile holds
-  const int64_t c0 = kcase * a.per + first, C = a.ncases * a.per;
-  const int n = (int)a.n, ns = (int)shape_padded_n(a.n, a.tile_chains);
-  constexpr int COMPS = PLANAR ? 2 : 3;
   // px[q][i], pz[q][i], (py[q][i]) for chain q of the tile: unit vectors first, positions after phase 2
-  double *px = lds + 2 * STHREADS;
-  double *pz = px + (int64_t)a.tile_chains * ns;
-  double *py = pz + (int64_t)a.tile_chains * ns;                    // 3D only
-  const double b = cases[kcase].b;
-
-  for (int e = t; e < tc * n; e += STHREADS) {
-    const int q = e % tc, i = e / tc;
-    double sp, cp;
-    sincos_f64(load_angle(ang, ((int64_t)n + i) * C + c0 + q, (size_t)a.elem, false), &sp, &cp);
-    if constexpr (PLANAR) {
-      px[q * ns + i] = cp;
-      pz[q * ns + i] = sp;
-    } else {
-      double st, ct;
-      sincos_f64(load_angle(ang, (int64_t)i * C + c0 + q, (size_t)a.elem, true), &st, &ct);
-      px[q * ns + i] = cp * st;
-      py[q * ns + i] = sp * st;
-      pz[q * ns + i] = ct;
-    }
-  }
-  __syncthreads();
+  const Tile w = tile_of(a, lds);
+  const int n = (int)a.n, tc = w.tc, ns = w.ns;
+  constexpr int COMPS = PLANAR ? 2 : 3;
+  double *px = w.x, *pz = w.z, *py = w.y;
+  const double b = cases[w.kcase].b;
+  tile_unit_vectors<PLANAR>(a, w, ang);
 
   // phase 2: sequence s = (component, chain) of the tile, one wavefront each
   const int seg = (n + 63) / 64;
-  for (int s = wave; s < COMPS * tc; s += STHREADS / 64) {
+  for (int s = wave; s < COMPS * tc; s += TILE_THREADS / 64) {
     double *v = px + (int64_t)(s / tc) * a.tile_chains * ns + (s % tc) * ns;   // px, pz, py lie one behind the other
     const int i0 = lane * seg, i1 = i0 + seg < n ? i0 + seg : n;
     double mine = 0.0;
@@ -121,9 +92,9 @@ __global__ __launch_bounds__(STHREADS) void shape_stage1(const ShapeArgs a, cons
   __syncthreads();
 
   // phase 3: centre and gyration tensor, a wavefront per chain; the chain's eight values go to gy[q][8]
-  double *gy = lds;                                                 // SHAPE_TILE * 8 doubles of the scratch
+  double *gy = lds;                                                 // TILE_CHAINS * 8 doubles of the scratch
   const double dn = (double)n;
-  for (int q = wave; q < tc; q += STHREADS / 64) {
+  for (int q = wave; q < tc; q += TILE_THREADS / 64) {
     const double *x = px + q * ns, *z = pz + q * ns, *y = py + q * ns;
     double mx = 0.0, my = 0.0, mz = 0.0;
     for (int i = lane; i < n; i += 64) {
@@ -203,15 +174,7 @@ __global__ __launch_bounds__(STHREADS) void shape_stage1(const ShapeArgs a, cons
         r2 += v * v;
       }
     }
-    if (a.groups > 1) {
-      s1[t] = r1; s2[t] = r2;
-      __syncthreads();
-      if (g == 0 && active) {
-        r1 = 0.0; r2 = 0.0;
-        for (int gg = 0; gg < a.groups; ++gg) { r1 += s1[sub + gg * a.lpc]; r2 += s2[sub + gg * a.lpc]; }
-      }
-      __syncthreads();   // the scratch is rewritten for the next slot
-    }
+    tile_group_fold(a, lds, sub, g, active, r1, r2);
     if (g == 0 && active) {
       out[PSTAT_SHAPE_GYR + k] = r1;
       out[ncols + PSTAT_SHAPE_GYR + k] = r2;
@@ -221,39 +184,18 @@ __global__ __launch_bounds__(STHREADS) void shape_stage1(const ShapeArgs a, cons
 
 }  // namespace
 
-void shape_layout(ShapeArgs &a) {
-  const int comps = a.planar ? 2 : 3;
-  int tc = (int)(a.per < SHAPE_TILE ? a.per : SHAPE_TILE);
-  while (tc > 1 && SHAPE_SCRATCH + (size_t)tc * (size_t)shape_padded_n(a.n, tc) * comps * sizeof(double) > SHAPE_LDS) --tc;
-  a.tile_chains = tc;
-  a.tiles = (a.per + tc - 1) / tc;
-  int lpc = 1;
-  while (lpc < STHREADS && lpc < a.nq) lpc *= 2;
-  a.lpc = lpc;
-  a.groups = STHREADS / lpc;
-  a.nslots = (a.nq + lpc - 1) / lpc;
-}
-
-size_t shape_partial_doubles(const ShapeArgs &a) { return (size_t)a.ncases * (size_t)a.tiles * 2 * (size_t)a.ncols; }
-
 hipError_t launch_shape(const ShapeArgs &a, const void *ang, const CaseConst *cases, const double *q, double *partial,
                         double *totals, double *row, hipStream_t stream) {
-  const int64_t blocks = a.ncases * a.tiles;
-  if (blocks <= 0) return hipSuccess;
-  if (blocks > 0x7fffffffll) return hipErrorInvalidConfiguration;
-  const size_t lds = SHAPE_SCRATCH + (size_t)a.tile_chains * (size_t)shape_padded_n(a.n, a.tile_chains) * (a.planar ? 2 : 3) * sizeof(double);
-  if (lds > SHAPE_LDS || a.tile_chains > SHAPE_TILE || a.lpc * a.groups != STHREADS) return hipErrorInvalidConfiguration;
-  const dim3 grid((unsigned)blocks), block(STHREADS);
+  int64_t blocks;
+  size_t lds;
+  hipError_t e = tile_launch_shape(a, &blocks, &lds);
+  if (e != hipSuccess || blocks == 0) return e;
+  const dim3 grid((unsigned)blocks), block(TILE_THREADS);
   if (a.planar) shape_stage1<true><<<grid, block, lds, stream>>>(a, ang, cases, q, partial);
   else shape_stage1<false><<<grid, block, lds, stream>>>(a, ang, cases, q, partial);
-  hipError_t e = hipGetLastError();
+  e = hipGetLastError();
   if (e != hipSuccess) return e;
-  // the fold over the tiles is the correlation recorder's: it reads ncases, ncols, tiles and per only
-  CorrArgs f{};
-  f.per = a.per; f.ncases = a.ncases; f.n = a.n; f.tiles = a.tiles; f.ncols = a.ncols;
-  const int64_t waves = a.ncases * a.ncols;
-  corr_stage2<<<dim3((unsigned)((waves + STHREADS / 64 - 1) / (STHREADS / 64))), block, 0, stream>>>(f, partial, totals, row);
-  return hipGetLastError();
+  return launch_tile_fold(a, partial, totals, row, stream);
 }
 
 }  // namespace pstat

@@ -94,20 +94,14 @@ def averagers(s):
     return sas + [Averager(ex[0], exse[0]), Averager(ex[1], exse[1])], vas, ar
 
 
-def run_cases(plist: list, write_csv: bool = True, info: dict | None = None, error_bars: int = 0, hist=None, corr=None, shape=None) -> list:
+def run_cases(plist: list, write_csv: bool = True, info: dict | None = None, record=None) -> list:
     """The top level of the clustering main for every case of `plist` at once -- parsed options that differ only in their
     physics scalars, prefix and seed (one case: the command line; many: a sweep, polymer_stats_amd/sweep.py) -- as ONE
-    ensemble: every rung of the ladder and the recorded run are one launch (per segment) for all of them.  `error_bars` = N:
-    the production run is recorded as N batches and info["error_bars"] holds the blocked standard errors of every case."""
+    ensemble: every rung of the ladder and the recorded run are one launch (per segment) for all of them.  `record` = a
+    _host.Recording: the production run is recorded its way and info[record.kind] holds what that gives (_Pool.record)."""
     pargs = plist[0]
-    if error_bars:
-        _host.check_error_bars(pargs, error_bars, write_csv)
-    if hist:      # every chain histogrammed every --stepout steps of the production run: info["hist"] (_Pool.histograms)
-        _host.check_hist(pargs, hist, write_csv, error_bars=error_bars)
-    if corr:      # the lag correlations recorded every --stepout steps of the production run: info["corr"] (_Pool.correlations)
-        _host.check_corr(pargs, corr, write_csv, error_bars=error_bars, hist=hist)
-    if shape:     # the gyration block and the form factor recorded every --stepout steps of the production run: info["shape"] (_Pool.shapes)
-        _host.check_shape(pargs, shape, write_csv, error_bars=error_bars, hist=hist, corr=corr)
+    if record:
+        _host.check_recording(pargs, record, write_csv)
     _host.check_numeric_type(pargs)                                     # :191
     ladder = _host.burn_ladder(pargs)
     with _host._Pool(plist, params_from_pargs, info=info) as pool:
@@ -119,10 +113,10 @@ def run_cases(plist: list, write_csv: bool = True, info: dict | None = None, err
                     e.restart_from_x0(x0, dx0[0], dx0[1])
         # every stage is one call of the reference's mcmc(nsteps, pargs, chain) (:172-352) at kT x mult: the rungs (:366-383), then
         # the production run (:385-386).  Every call rewrites the two CSV files, so only the last one's survive: the rungs skip them
-        for mult, nsteps, write, eb, hs, cs, ss in [(m, pargs["burn-in"], False, 0, None, None, None) for m in ladder] + [(1.0, pargs["num-steps"], write_csv, error_bars, hist, corr, shape)]:
+        for mult, nsteps, write, rec in [(m, pargs["burn-in"], False, None) for m in ladder] + [(1.0, pargs["num-steps"], write_csv, record)]:
             pool.stage(mult)
             out = _host.recorded_stage(pool, int(nsteps), write, lambda p: traj_header(p["num-monomers"]), ROLL_HEADER, _rows,
-                                       angles=True, error_bars=eb, hist=hs, corr=cs, shape=ss)
+                                       angles=True, record=rec)
         for k, s in enumerate(out):
             pool.report_failures(k, s)
     return [averagers(s) for s in out]

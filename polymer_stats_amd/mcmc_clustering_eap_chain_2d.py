@@ -69,19 +69,13 @@ def averagers(s):
     return sas, [Averager(_planar(a.value), _planar(a.stderr)) for a in vas], ar
 
 
-def run_cases(plist: list, write_csv: bool = True, info: dict | None = None, error_bars: int = 0, hist=None, corr=None, shape=None) -> list:
+def run_cases(plist: list, write_csv: bool = True, info: dict | None = None, record=None) -> list:
     """The top level of the planar main for every case of `plist` at once -- parsed options that differ only in their physics
     scalars, prefix and seed (one case: the command line; many: a sweep, polymer_stats_amd/sweep.py) -- as ONE ensemble.
-    `error_bars` = N: the production run is recorded as N batches and info["error_bars"] holds every case's blocked standard errors."""
+    `record` = a _host.Recording: the production run is recorded its way and info[record.kind] holds what that gives (_Pool.record)."""
     pargs = plist[0]
-    if error_bars:
-        _host.check_error_bars(pargs, error_bars, write_csv)
-    if hist:      # every chain histogrammed every --stepout steps of the production run: info["hist"] (_Pool.histograms)
-        _host.check_hist(pargs, hist, write_csv, error_bars=error_bars)
-    if corr:      # the lag correlations recorded every --stepout steps of the production run: info["corr"] (_Pool.correlations)
-        _host.check_corr(pargs, corr, write_csv, error_bars=error_bars, hist=hist)
-    if shape:     # the gyration block and the form factor recorded every --stepout steps of the production run: info["shape"] (_Pool.shapes)
-        _host.check_shape(pargs, shape, write_csv, error_bars=error_bars, hist=hist, corr=corr)
+    if record:
+        _host.check_recording(pargs, record, write_csv)
     _host.check_numeric_type(pargs)                                                        # :167
     ladder = _host.burn_ladder(pargs)                                                      # :323 (evaluated whatever follows)
     with _host._Pool(plist, params_from_pargs, planar=True, info=info) as pool:
@@ -90,11 +84,10 @@ def run_cases(plist: list, write_csv: bool = True, info: dict | None = None, err
                                             "from a fresh chain (2D/mcmc_clustering_eap_chain.jl:151), so --burn-in / --burn-schedule "
                                             "change no output; --carry-burn-in carries the chains through the ladder")
         # every stage is one call of the reference's mcmc(nsteps, pargs, chain) (:148-310) at kT x mult on the pool's chains
-        rungs = [(m, pargs["burn-in"], False, 0) for m in ladder] if pargs["carry-burn-in"] else []
-        for mult, nsteps, write, eb, hs, cs, ss in [r + (None, None, None) for r in rungs] + [(1.0, pargs["num-steps"], write_csv, error_bars, hist, corr, shape)]:         # :336
+        rungs = [(m, pargs["burn-in"], False, None) for m in ladder] if pargs["carry-burn-in"] else []
+        for mult, nsteps, write, rec in rungs + [(1.0, pargs["num-steps"], write_csv, record)]:         # :336
             pool.stage(mult)
-            out = _host.recorded_stage(pool, int(nsteps), write, lambda p: TRAJ_HEADER, ROLL_HEADER, _rows,
-                                       error_bars=eb, hist=hs, corr=cs, shape=ss)
+            out = _host.recorded_stage(pool, int(nsteps), write, lambda p: TRAJ_HEADER, ROLL_HEADER, _rows, record=rec)
         for k, s in enumerate(out):
             pool.report_failures(k, s)
     return [averagers(s) for s in out]

@@ -54,22 +54,15 @@ def mcmc(nsteps: int, pargs: dict):
 averagers = _host._averagers      # a summary -> (scalar_averagers, vector_averagers, ar)
 
 
-def mcmc_cases(nsteps: int, plist: list, write_csv: bool = True, info: dict | None = None, error_bars: int = 0, hist=None, corr=None, shape=None) -> list:
+def mcmc_cases(nsteps: int, plist: list, write_csv: bool = True, info: dict | None = None, record=None) -> list:
     """mcmc(nsteps, pargs) for every case of `plist` at once -- parsed options that differ only in their physics scalars,
     prefix and seed (one case: the command line; many: a sweep, polymer_stats_amd/sweep.py) -- as ONE ensemble: one launch
     per init for all of them, or, with the two CSV files of every case (`write_csv`), one per --stepout steps followed by the
-    launch that records the row of every case on the device (_Pool.recorded).  `error_bars` = N: the run is recorded as N
-    batches and info["error_bars"] holds the blocked standard errors of every case (_host.recorded_stage).  `hist`: every chain
-    is histogrammed every --stepout steps and info["hist"] holds the counts (_host.check_hist, _Pool.histograms)."""
+    launch that records the row of every case on the device (_Pool.recorded).  `record` = a _host.Recording: the run is
+    recorded its way and info[record.kind] holds what that gives (_host.check_recording, _Pool.record)."""
     pargs = plist[0]
-    if error_bars:
-        _host.check_error_bars(pargs, error_bars, write_csv)
-    if hist:
-        _host.check_hist(pargs, hist, write_csv, error_bars=error_bars)
-    if corr:      # the lag correlations recorded every --stepout steps: info["corr"] (_host.check_corr, _Pool.correlations)
-        _host.check_corr(pargs, corr, write_csv, error_bars=error_bars, hist=hist)
-    if shape:     # the gyration block and the form factor recorded every --stepout steps: info["shape"] (_host.check_shape, _Pool.shapes)
-        _host.check_shape(pargs, shape, write_csv, error_bars=error_bars, hist=hist, corr=corr)
+    if record:
+        _host.check_recording(pargs, record, write_csv)
     if pargs["acc"] != "metropolis":
         raise ReferenceError_(f"'{pargs['acc']}' acceptance criteria has not yet been implemented.")  # :184
     _host.check_numeric_type(pargs)                                                                    # :195
@@ -87,13 +80,13 @@ def mcmc_cases(nsteps: int, plist: list, write_csv: bool = True, info: dict | No
                 if init < pargs["num-inits"]:                        # :352-361
                     pool.reinit(bool(pargs["force-init"]))
         out = _host.recorded_stage(pool, nsteps, write_csv, lambda p: TRAJ_HEADER, ROLL_HEADER, _rows, runs=inits(),
-                                   report=pool.report_failures, error_bars=error_bars, hist=hist, corr=corr, shape=shape)
+                                   report=pool.report_failures, record=record)
     return [averagers(s) for s in out]
 
 
-def run_cases(plist: list, write_csv: bool = True, info: dict | None = None, error_bars: int = 0, hist=None, corr=None, shape=None) -> list:
+def run_cases(plist: list, write_csv: bool = True, info: dict | None = None, record=None) -> list:
     """mcmc_cases for each case's own --num-steps: the call every main offers (polymer_stats_amd/sweep.py)."""
-    return mcmc_cases(int(plist[0]["num-steps"]), plist, write_csv=write_csv, info=info, error_bars=error_bars, hist=hist, corr=corr, shape=shape)
+    return mcmc_cases(int(plist[0]["num-steps"]), plist, write_csv=write_csv, info=info, record=record)
 
 
 def main(argv=None) -> int:

@@ -41,11 +41,8 @@ from . import _lib          # (tools/run_sweep.py counts the devices through it)
 from . import mcmc_clustering_eap_chain as cluster_main
 from . import mcmc_clustering_eap_chain_2d as planar_main
 from . import mcmc_eap_chain as fixed_main
-from ._host import ReferenceError_, arith, error_lines, fresh_seed, number
-from ._host import check_error_bars as _host_check_error_bars
-from ._host import check_hist as _host_check_hist, hist_lines, parse_hist
-from ._host import check_corr as _host_check_corr, corr_lines, parse_corr
-from ._host import check_shape as _host_check_shape, parse_shape, shape_lines
+from ._host import RECORDINGS, Recording, ReferenceError_, arith, check_recording, fresh_seed, number
+from ._host import parse_corr, parse_hist, parse_shape      # (reached through this module too)
 
 # (the planar main: 2D/run/Ising_2024-11-06.jl and its siblings launch 2D/mcmc_clustering_eap_chain.jl the same way)
 MAINS = {"mcmc_eap_chain": fixed_main, "mcmc_clustering_eap_chain": cluster_main, "mcmc_clustering_eap_chain_2d": planar_main}
@@ -197,58 +194,33 @@ def plan(main_name: str, fixed_argv: list[str], cases: list[dict], workdir: str,
     return out
 
 
-def check_error_bars(main_name: str, fixed_argv: list[str], nbatches: int, write_csv: bool = False, world: int = 1):
-    """--error-bars N of tools/run_sweep.py: what it cannot be combined with (_host.check_error_bars, and more than one rank),
-    judged from the options every case shares; no GPU is touched."""
+def recording(main_name: str, fixed_argv: list[str], cases: list[dict], *, error_bars: int = 0, hist=None, corr=None, shape=None,
+              write_csv: bool = False, world: int = 1) -> Recording | None:
+    """--error-bars N | --hist SPEC ... | --corr SPEC | --shape [SPEC] of tools/run_sweep.py (the texts as the command line gives
+    them; shape "" is the bare flag, None its absence) -> the Recording of the production run, or None where none is asked for.
+    Parses the flag that is given and refuses what it cannot be combined with -- another of the four, more than one rank, and
+    what _host.check_recording refuses, judged from the options every case shares and from every chain and monomer length
+    among the cases; no GPU is touched."""
+    given = [(kind, text) for kind, text in (("error_bars", error_bars or None), ("hist", hist or None), ("corr", corr or None),
+                                             ("shape", shape)) if text is not None]
+    if not given:
+        return None
+    row = RECORDINGS[given[0][0]]
+    rec = Recording(given[0][0], row.parse(given[0][1]))
+    if len(given) > 1:
+        raise ReferenceError_(f"{RECORDINGS[given[1][0]].flag} cannot be combined with {row.flag}: each records the production run "
+                              "in its own way")
     if world > 1:
-        raise ReferenceError_(f"--error-bars needs one device, not --gpus {world}")
-    _host_check_error_bars(MAINS[main_name].parse_args(list(fixed_argv)), nbatches, write_csv)
-
-
-def check_hist(main_name: str, fixed_argv: list[str], hist: list[str], write_csv: bool = False, world: int = 1, error_bars: int = 0):
-    """--hist of tools/run_sweep.py: parses the specs and refuses what they cannot be combined with (_host.check_hist, and more
-    than one rank), judged from the options every case shares; no GPU is touched.  Returns [(channel, lo, hi, nbins), ...]."""
-    specs = [parse_hist(t) for t in hist]
-    if world > 1:
-        raise ReferenceError_(f"--hist needs one device, not --gpus {world}")
-    _host_check_hist(MAINS[main_name].parse_args(list(fixed_argv)), specs, write_csv, error_bars=error_bars)
-    return specs
-
-
-def check_corr(main_name: str, fixed_argv: list[str], corr: str, cases: list[dict], write_csv: bool = False, world: int = 1,
-               error_bars: int = 0, hist=None):
-    """--corr of tools/run_sweep.py: parses it and refuses what it cannot be combined with (_host.check_corr, and more than one
-    rank), judged from the options every case shares and from every chain length among the cases; no GPU is touched.  Returns
-    (max_lag, channels)."""
-    spec = parse_corr(corr)
-    if world > 1:
-        raise ReferenceError_(f"--corr needs one device, not --gpus {world}")
+        raise ReferenceError_(f"{row.flag} needs one device, not --gpus {world}")
     main = MAINS[main_name]
-    lengths = {}
-    for case in cases or [{}]:
-        lengths.setdefault(repr(case.get("n", case.get("num-monomers"))), case)
-    for case in lengths.values():
-        _host_check_corr(main.parse_args(list(fixed_argv) + case_argv(case)), spec, write_csv, error_bars=error_bars, hist=hist)
-    return spec
-
-
-def check_shape(main_name: str, fixed_argv: list[str], shape: str, cases: list[dict], write_csv: bool = False, world: int = 1,
-                error_bars: int = 0, hist=None, corr=None):
-    """--shape of tools/run_sweep.py: parses it and refuses what it cannot be combined with (_host.check_shape, and more than one
-    rank), judged from the options every case shares and from every chain and monomer length among the cases; no GPU is touched.
-    Returns parse_shape's spec."""
-    spec = parse_shape(shape)
-    if world > 1:
-        raise ReferenceError_(f"--shape needs one device, not --gpus {world}")
-    main = MAINS[main_name]
-    if main is planar_main and any(v[1] != 0.0 for v in spec[1]):
+    if rec.kind == "shape" and main is planar_main and any(v[1] != 0.0 for v in rec.spec[1]):
         raise ReferenceError_("--shape: the planar main's chains lie in the x-z plane: no wave-vectors along y")
     sizes = {}
     for case in cases or [{}]:
         sizes.setdefault(repr((case.get("n", case.get("num-monomers")), case.get("b", case.get("mlen")))), case)
     for case in sizes.values():
-        _host_check_shape(main.parse_args(list(fixed_argv) + case_argv(case)), spec, write_csv, error_bars=error_bars, hist=hist, corr=corr)
-    return spec
+        check_recording(main.parse_args(list(fixed_argv) + case_argv(case)), rec, write_csv)
+    return rec
 
 
 def _signature(pargs: dict):
@@ -261,29 +233,22 @@ def run_sweep(main_name: str, fixed_argv: list[str], cases: list[dict], workdir:
               error_bars: int = 0, hist=None, corr=None, shape=None) -> dict:
     """Runs the cases whose `.out` does not exist yet (run/interacting_dielectric_study.jl:39) and that fall to this rank
     (position in the full case list modulo `world`).  `write_csv` also writes every case's two time-series files (rows
-    recorded on the device for the whole ensemble, _Pool.recorded).  `error_bars` = N: the production run is recorded as N batches
-    and every `<case>.out` gets a `<case>.err` beside it (_host.error_lines: blocked standard errors under the .out's names); the
-    .out files are those of a run without it, and a case whose .err is missing is run again.  `hist` = ["CHANNEL:LO:HI:NBINS", ...]:
-    every chain is histogrammed every --stepout steps of the production run and every `<case>.out` gets a `<case>.hist` beside it
-    (_host.hist_lines), under the same two rules.  `corr` = "MAXLAG[:nn,zz,mm]": the lag correlations are recorded every --stepout
-    steps of the production run and every `<case>.out` gets a `<case>.corr` beside it (_host.corr_lines), likewise.  `shape` = "[AXIS:QMAX:NQ,...]"
-    ("" for the gyration block alone; None: no shape): the gyration tensor and the form factor at those wave-vectors, recorded the
-    same way, in a `<case>.shape` (_host.shape_lines).  Returns {"ran": [...], "skipped": [...], "launches": k}."""
+    recorded on the device for the whole ensemble, _Pool.recorded).  `error_bars` = N | `hist` = ["CHANNEL:LO:HI:NBINS", ...] | `corr` =
+    "MAXLAG[:nn,zz,mm]" | `shape` = "[AXIS:QMAX:NQ,...]" ("" for the gyration block alone; None: no shape), the command line's four
+    options and at most one of them (recording): the production run is recorded that way (_Pool.record: N batches | every chain
+    histogrammed | the lag correlations | the gyration tensor and the form factor at those wave-vectors, every --stepout steps)
+    and every `<case>.out` gets a `<case>.err` | `.hist` | `.corr` | `.shape` beside it (_host.error_lines: blocked standard
+    errors under the .out's names | hist_lines | corr_lines | shape_lines); the .out files are those of a run without it, and a
+    case whose file beside the .out is missing is run again.  Returns {"ran": [...], "skipped": [...], "launches": k}."""
     main = MAINS[main_name]
-    if error_bars:
-        check_error_bars(main_name, fixed_argv, error_bars, write_csv=write_csv, world=world)
-    specs = check_hist(main_name, fixed_argv, list(hist), write_csv=write_csv, world=world, error_bars=error_bars) if hist else None
-    cspec = check_corr(main_name, fixed_argv, corr, cases, write_csv=write_csv, world=world, error_bars=error_bars, hist=hist) if corr else None
-    sspec = check_shape(main_name, fixed_argv, shape, cases, write_csv=write_csv, world=world, error_bars=error_bars, hist=hist,
-                        corr=corr) if shape is not None else None
+    rec = recording(main_name, fixed_argv, cases, error_bars=error_bars, hist=hist, corr=corr, shape=shape, write_csv=write_csv,
+                    world=world)
     os.makedirs(workdir, exist_ok=True)
     todo_all = plan(main_name, fixed_argv, cases, workdir, name=name, num_chains=num_chains, seed=seed, precision=precision,
                     rng=rng, device=device)
-    # with error bars a case is complete when its .err is there too (a directory first swept without them: run again)
-    beside = lambda p, ext: p["_out"][:-len(".out")] + ext
-    done = lambda p: (os.path.isfile(p["_out"]) and (not error_bars or os.path.isfile(beside(p, ".err")))
-                      and (not specs or os.path.isfile(beside(p, ".hist"))) and (not cspec or os.path.isfile(beside(p, ".corr")))
-                      and (not sspec or os.path.isfile(beside(p, ".shape"))))
+    # a recorded case is complete when the recording's file is there too (a directory first swept without it: run again)
+    beside = lambda p: p["_out"][:-len(".out")] + RECORDINGS[rec.kind].ext
+    done = lambda p: os.path.isfile(p["_out"]) and (rec is None or os.path.isfile(beside(p)))
     skipped = [p["_name"] for p in todo_all if done(p) and not overwrite]
     todo = [p for p in todo_all if overwrite or not done(p)]
     mine = [p for p in todo if p["_index"] % world == rank]     # by position in the full list: ranks need not agree on what is done
@@ -298,19 +263,11 @@ def run_sweep(main_name: str, fixed_argv: list[str], cases: list[dict], workdir:
             t0 = time.time()
             info = {}
             # the main's own protocol, every case of the ensemble at once
-            res = main.run_cases(plist, write_csv=write_csv, info=info, **({"error_bars": error_bars} if error_bars else {}),
-                                 **({"hist": specs} if specs else {}), **({"corr": cspec} if cspec else {}),
-                                 **({"shape": sspec} if sspec else {}))
+            res = main.run_cases(plist, write_csv=write_csv, info=info, record=rec)
             for k, (p, (sas, vas, ar)) in enumerate(zip(plist, res)):
                 texts = [(p["_out"], main.summary_lines(sas, vas, ar, p))]      # println x 10 (12)
-                if error_bars:      # (first: a case whose .out is there is complete)
-                    texts.insert(0, (p["_out"][:-len(".out")] + ".err", error_lines(main, info["error_bars"], k, p)))
-                if specs:
-                    texts.insert(0, (beside(p, ".hist"), hist_lines(info["hist"], specs, k, int(num_chains))))
-                if cspec:
-                    texts.insert(0, (beside(p, ".corr"), corr_lines(*info["corr"], k)))
-                if sspec:
-                    texts.insert(0, (beside(p, ".shape"), shape_lines(*info["shape"], k)))
+                if rec:      # (first: a case whose .out is there is complete)
+                    texts.insert(0, (beside(p), RECORDINGS[rec.kind].lines(main, info[rec.kind], rec.spec, k, p)))
                 for path, lines in texts:           # complete or absent: an interrupted sweep re-runs the case
                     tmp = path + f".tmp{os.getpid()}"
                     with open(tmp, "w") as f:

@@ -382,7 +382,7 @@ def test_sweep_writes_shape_files(tmp_path):
     plist = sw.plan("mcmc_eap_chain", FIXED, cases, str(tmp_path / "api"), num_chains=64, seed=11)
     info = {}
     spec = sw.parse_shape("z:6:8,x:6:8")
-    sw.MAINS["mcmc_eap_chain"].run_cases(plist, write_csv=False, info=info, shape=spec)
+    sw.MAINS["mcmc_eap_chain"].run_cases(plist, write_csv=False, info=info, record=sw.Recording("shape", spec))
     res, eb = info["shape"]
     assert res.records == 32 and res.q.shape == (16, 3)
     np.testing.assert_array_equal(res.q[:8, 2], 6.0 * np.arange(1, 9) / 8)

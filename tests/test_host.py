@@ -204,6 +204,36 @@ def test_hosts_state_what_the_recorded_tables_hold():
         assert all(e["type"] is not None for e in want[name]["errors"])          # every recorded branch did raise
 
 
+def test_recorder_refusals_keep_their_recorded_words(tmp_path, monkeypatch, capsys):
+    """tests/golden/recorder_refusals.json was recorded (tests/golden/make_recorder_refusals.py) from the commit before
+    --error-bars, --hist, --corr and --shape became one Recording (polymer_stats_amd/_host.py): for every command line of the
+    refusal tests, every pairing of two of the flags and two command lines with three, tools/run_sweep.py's exit status and
+    the one line it leaves.  The tool under test must refuse each with exactly that line, before any GPU work (--dry-run)."""
+    import importlib.util
+    import json
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("run_sweep_tool", os.path.join(root, "tools", "run_sweep.py"))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    with open(os.path.join(root, "tests", "golden", "recorder_refusals.json"), encoding="utf-8") as f:
+        want = json.load(f)
+    flags = ("--error-bars", "--hist", "--corr", "--shape")
+    given = [tuple(f for f in flags if f in row["argv"]) for row in want]
+    assert len(want) >= 49 and all(row["argv"][0] == "--dry-run" and row["status"] == 1 for row in want)
+    assert {g for g in given if len(g) == 2} == {(a, b) for i, a in enumerate(flags) for b in flags[i + 1:]}
+    assert sum(len(g) == 3 for g in given) == 2 and all(given)
+    for row, g in zip(want, given):
+        if len(g) > 1:
+            assert row["line"] == f"{g[1]} cannot be combined with {g[0]}: each records the production run in its own way"
+        monkeypatch.setattr("sys.argv", ["run_sweep.py", str(tmp_path / "w")] + row["argv"])
+        with pytest.raises(SystemExit) as e:
+            tool.main()
+        # (a text as the exit code: the interpreter prints it on stderr and exits with status 1)
+        assert e.value.code == row["line"], (row["argv"], e.value.code)
+        assert capsys.readouterr() == ("", "") and not (tmp_path / "w").exists()
+
+
 # ------------------------------------------------------------------ seed contract
 def test_default_seed_is_fresh_entropy_and_echoed(capsys):
     """The reference never seeds its RNG (its sweeps launch one command 25x and use the scatter,

@@ -101,28 +101,11 @@ def main():
     if not cases:
         raise SystemExit("no cases: give --axis and/or --cases")
 
-    if args.error_bars:
-        try:
-            sw.check_error_bars(args.main, fixed, args.error_bars, write_csv=args.csv, world=args.gpus)
-        except sw.ReferenceError_ as e:
-            raise SystemExit(str(e))
-    if args.hist:
-        try:
-            sw.check_hist(args.main, fixed, args.hist, write_csv=args.csv, world=args.gpus, error_bars=args.error_bars)
-        except sw.ReferenceError_ as e:
-            raise SystemExit(str(e))
-    if args.corr:
-        try:
-            sw.check_corr(args.main, fixed, args.corr, cases, write_csv=args.csv, world=args.gpus, error_bars=args.error_bars,
-                          hist=args.hist)
-        except sw.ReferenceError_ as e:
-            raise SystemExit(str(e))
-    if args.shape is not None:
-        try:
-            sw.check_shape(args.main, fixed, args.shape, cases, write_csv=args.csv, world=args.gpus, error_bars=args.error_bars,
-                           hist=args.hist, corr=args.corr)
-        except sw.ReferenceError_ as e:
-            raise SystemExit(str(e))
+    recording = dict(error_bars=args.error_bars, hist=args.hist, corr=args.corr, shape=args.shape)
+    try:
+        sw.recording(args.main, fixed, cases, write_csv=args.csv, world=args.gpus, **recording)
+    except sw.ReferenceError_ as e:
+        raise SystemExit(str(e))
     if args.dry_run:
         pl = sw.plan(args.main, fixed, cases, args.workdir, name=args.name or None, num_chains=args.num_chains,
                      seed=0 if args.seed is None else args.seed, precision=args.precision, rng=args.rng)
@@ -180,8 +163,7 @@ def main():
     t0 = time.time()
     res = sw.run_sweep(args.main, fixed, cases, args.workdir, name=args.name or None, num_chains=args.num_chains, seed=args.seed,
                        precision=args.precision, rng=args.rng, rank=rank, world=world, device=local % ndev,
-                       overwrite=args.overwrite, write_csv=args.csv, max_chains=args.max_chains, error_bars=args.error_bars, **({"hist": args.hist} if args.hist else {}),
-                       **({"corr": args.corr} if args.corr else {}), **({"shape": args.shape} if args.shape is not None else {}),
+                       overwrite=args.overwrite, write_csv=args.csv, max_chains=args.max_chains, **recording,
                        log=lambda m: print("# " + m, file=sys.stderr, flush=True))
     print(f"# rank {rank} of {world}: {len(res['ran'])} cases run in {res['launches']} ensembles, {len(res['skipped'])} already "
           f"there; {time.time() - t0:.2f} s", file=sys.stderr, flush=True)
