@@ -105,7 +105,7 @@ __device__ __forceinline__ void run_cluster_segment(const SweepArgs &A, const De
   R c2sum = (R)S.obs[OBS_C2 * C + c], psisum = (R)S.obs[OBS_PSI * C + c];
   R lag = (R)S.lag[c];                      // log(alpha) of the last accepted proposal of this mcmc() call
   const bool umb = umb_on != 0;
-  const R wscale = umb ? (R)((0.2 + 0.8 * exp(-(cc.Fx * cc.Fx + cc.Fz * cc.Fz) / cc.kT)) / cc.kT) : (R)0;
+  const R wscale = umb ? (R)umbrella_wscale(cc) : (R)0;
   R uref = umb ? (R)S.uref[c] : (R)0;
   bool regauged = false;
   double wnorm = umb ? S.wnorm[c] : 0.0;
@@ -469,17 +469,8 @@ __device__ __forceinline__ void run_cluster_segment(const SweepArgs &A, const De
       to_adj -= chunk;
       if (to_adj == 0) {
         to_adj = spa;
-        const int64_t nacc = nacc_off + nacc_seg, natt = natt_off + steps_seg;
-        const double ratio = (double)nacc / (double)natt;
-        if (ratio > A.adj_ub && phistep_d != K<double>::pi && thstep_d != K<double>::half_pi) {
-          nacc_off = -nacc_seg; natt_off = -steps_seg;
-          phistep_d = fmin(K<double>::pi, phistep_d * A.adj_scale);
-          thstep_d = fmin(K<double>::half_pi, thstep_d * A.adj_scale);
-        } else if (ratio < A.adj_lb) {
-          nacc_off = -nacc_seg; natt_off = -steps_seg;
-          phistep_d /= A.adj_scale;
-          thstep_d /= A.adj_scale;
-        }
+        const Adapted a = adapt_steps(nacc_off, natt_off, nacc_seg, steps_seg, A.adj_lb, A.adj_ub, A.adj_scale, phistep_d, thstep_d);
+        phistep_d = a.phistep; thstep_d = a.thstep; nacc_off = a.nacc_off; natt_off = a.natt_off;
         phistep = (R)(phistep_d / ph_unit); thstep = (R)(thstep_d / th_unit);
       }
     }

@@ -125,6 +125,14 @@ __device__ __attribute__((noinline)) bool literal_accept(const double dU, const 
   return (delta >= 0) || (eps < exp_r(delta));
 }
 
+// Lane q keeps moment q of record!: its first-moment sum (q < 9) goes to row sums_row1(q) of DevState::sums, its second-moment
+// sum (q < 7) to row sums_row2(q) -- the map the chain-per-lane kernels write out row by row at their flush, as arithmetic.
+constexpr int sums_row1(const int q) { return q < 3 ? q : (q < 6 ? q + 3 : (q == 6 ? (int)S_U : q + 7)); }
+constexpr int sums_row2(const int q) { return q < 3 ? q + 3 : (q < 6 ? q + 6 : (int)S_USQ); }
+static_assert(sums_row1(0) == S_R1 && sums_row1(2) == S_R3 && sums_row1(3) == S_P1 && sums_row1(5) == S_P3 && sums_row1(6) == S_U &&
+              sums_row1(7) == S_C2 && sums_row1(8) == S_PSI && sums_row2(0) == S_R1SQ && sums_row2(2) == S_R3SQ &&
+              sums_row2(3) == S_P1SQ && sums_row2(5) == S_P3SQ && sums_row2(6) == S_USQ, "the S_* rows of pstat_device.h");
+
 #ifndef PSTAT_CW_WAVES
 #define PSTAT_CW_WAVES 4   // waves per SIMD asked of the register allocator (see the header)
 #endif
@@ -143,8 +151,8 @@ __global__ __launch_bounds__(64, PSTAT_CW_WAVES) void cluster_cw_kernel(SweepArg
   __shared__ double2 cA[NC + 3];      // (n_x, n_y); entry NC + 2: the moved monomer BEFORE the move (the bonds before it read that)
   __shared__ double2 cB[NC + 3];      // (n_z, theta)
   __shared__ double cP[NC + 2];       // phi
-  __shared__ uint32_t draws[NPOS];
-  __shared__ double KT[NK];
+  __shared__ __attribute__((aligned(16))) uint32_t draws[NPOS];   // (both are read as b128)
+  __shared__ __attribute__((aligned(16))) double KT[NK];
 
   const int lane = threadIdx.x;
   const int64_t c = blockIdx.x;
@@ -243,7 +251,7 @@ __global__ __launch_bounds__(64, PSTAT_CW_WAVES) void cluster_cw_kernel(SweepArg
   R lag = S.lag[c], lag_num = 1, lag_den = 1;
   bool lag_pending = false;
   const bool umb = umb_on != 0;
-  const R wscale = umb ? (0.2 + 0.8 * exp(-(cc.Fx * cc.Fx + cc.Fz * cc.Fz) / cc.kT)) / cc.kT : 0.0;
+  const R wscale = umb ? umbrella_wscale(cc) : 0.0;
   R uref = umb ? S.uref[c] : 0.0;
   bool regauged = false;
   double wnorm = umb ? S.wnorm[c] : 0.0;
@@ -547,8 +555,7 @@ __global__ __launch_bounds__(64, PSTAT_CW_WAVES) void cluster_cw_kernel(SweepArg
           const double f = exp_f64(-wrel);
           double *const sums_c = cold->sums;
           const int64_t Cc = cold->C;
-          const int r1 = lane < 3 ? lane : (lane < 6 ? lane + 3 : (lane == 6 ? (int)S_U : lane + 7));
-          const int r2 = lane < 3 ? lane + 3 : (lane < 6 ? lane + 6 : (int)S_USQ);
+          const int r1 = sums_row1(lane), r2 = sums_row2(lane);
           if (lane < 9) sums_c[(int64_t)r1 * Cc] *= f;
           if (lane < 7) sums_c[(int64_t)r2 * Cc] *= f;
           a1v *= f; a2v *= f; accw *= f; wnorm *= f;
@@ -563,8 +570,7 @@ __global__ __launch_bounds__(64, PSTAT_CW_WAVES) void cluster_cw_kernel(SweepArg
 
     // add the block to the averagers' sums (inc/average.jl:9): lane q its own rows; <psi> is sum psi / (n - 1)
     {
-      const int r1 = lane < 3 ? lane : (lane < 6 ? lane + 3 : (lane == 6 ? (int)S_U : lane + 7));       // S_R*, S_P*, S_U, S_C2, S_PSI
-      const int r2 = lane < 3 ? lane + 3 : (lane < 6 ? lane + 6 : (int)S_USQ);                         // S_R*SQ, S_P*SQ, S_USQ
+      const int r1 = sums_row1(lane), r2 = sums_row2(lane);
       double *const sums_c = cold->sums;
       const int64_t Cc = cold->C;
       if (lane < 9) sums_c[(int64_t)r1 * Cc] += lane == 8 ? a1v * inv_nm1 : a1v;
@@ -579,18 +585,8 @@ __global__ __launch_bounds__(64, PSTAT_CW_WAVES) void cluster_cw_kernel(SweepArg
       to_adj -= chunk;
       if (to_adj == 0) {
         to_adj = cold->spa;
-        const double adj_lb = cold->adj_lb, adj_ub = cold->adj_ub, adj_scale = cold->adj_scale;
-        const int64_t nacc = nacc_off + nacc_seg, natt = natt_off + steps_seg;
-        const double ratio = (double)nacc / (double)natt;
-        if (ratio > adj_ub && phistep != K<double>::pi && thstep != K<double>::half_pi) {
-          nacc_off = -nacc_seg; natt_off = -steps_seg;
-          phistep = fmin(K<double>::pi, phistep * adj_scale);
-          thstep = fmin(K<double>::half_pi, thstep * adj_scale);
-        } else if (ratio < adj_lb) {
-          nacc_off = -nacc_seg; natt_off = -steps_seg;
-          phistep /= adj_scale;
-          thstep /= adj_scale;
-        }
+        const Adapted a = adapt_steps(nacc_off, natt_off, nacc_seg, steps_seg, cold->adj_lb, cold->adj_ub, cold->adj_scale, phistep, thstep);
+        phistep = a.phistep; thstep = a.thstep; nacc_off = a.nacc_off; natt_off = a.natt_off;
         phs = phistep; ths = thstep;
       }
     }

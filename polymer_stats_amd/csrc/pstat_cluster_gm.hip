@@ -154,7 +154,7 @@ __device__ __forceinline__ void run_cluster_segment_gm(const SweepArgs &A, const
   R lag = (R)S.lag[c], lag_alpha = 1;
   bool lag_pending = false;
   const bool umb = umb_on != 0;
-  const R wscale = umb ? (R)((0.2 + 0.8 * exp(-(cc.Fx * cc.Fx + cc.Fz * cc.Fz) / cc.kT)) / cc.kT) : (R)0;
+  const R wscale = umb ? (R)umbrella_wscale(cc) : (R)0;
   R uref = umb ? (R)S.uref[c] : (R)0;
   bool regauged = false;
   double wnorm = umb ? S.wnorm[c] : 0.0;
@@ -659,17 +659,8 @@ __device__ __forceinline__ void run_cluster_segment_gm(const SweepArgs &A, const
       to_adj -= chunk;
       if (to_adj == 0) {
         to_adj = spa;
-        const int64_t nacc = nacc_off + nacc_seg, natt = natt_off + steps_seg;
-        const double ratio = (double)nacc / (double)natt;
-        if (ratio > A.adj_ub && phistep != K<double>::pi && thstep != K<double>::half_pi) {
-          nacc_off = -nacc_seg; natt_off = -steps_seg;
-          phistep = fmin(K<double>::pi, phistep * A.adj_scale);
-          thstep = fmin(K<double>::half_pi, thstep * A.adj_scale);
-        } else if (ratio < A.adj_lb) {
-          nacc_off = -nacc_seg; natt_off = -steps_seg;
-          phistep /= A.adj_scale;
-          thstep /= A.adj_scale;
-        }
+        const Adapted a = adapt_steps(nacc_off, natt_off, nacc_seg, steps_seg, A.adj_lb, A.adj_ub, A.adj_scale, phistep, thstep);
+        phistep = a.phistep; thstep = a.thstep; nacc_off = a.nacc_off; natt_off = a.natt_off;
         phs = (R)(phistep / AG::unit); ths = (R)(thstep / AG::unit);
       }
     }

@@ -169,7 +169,7 @@ void cluster_wave_kernel(SweepArgs A, DevState S, const CaseConst *__restrict__ 
   int nacc_seg = 0, steps_seg = 0;
   int nnan_seg = 0;   // proposals whose trial energy was NaN or +-Inf (1/r^3 at r -> 0)
   R lag = (R)S.lag[c];
-  const R wscale = umb ? (R)((0.2 + 0.8 * exp(-(cc.Fx * cc.Fx + cc.Fz * cc.Fz) / cc.kT)) / cc.kT) : (R)0;
+  const R wscale = umb ? (R)umbrella_wscale(cc) : (R)0;
   R uref = umb ? (R)S.uref[c] : (R)0;
   bool regauged = false;
   double wnorm = umb ? S.wnorm[c] : 0.0;
@@ -339,17 +339,8 @@ void cluster_wave_kernel(SweepArgs A, DevState S, const CaseConst *__restrict__ 
       to_adj -= chunk;
       if (to_adj == 0) {
         to_adj = spa;
-        const int64_t nacc = nacc_off + nacc_seg, natt = natt_off + steps_seg;
-        const double ratio = (double)nacc / (double)natt;
-        if (ratio > A.adj_ub && phistep_d != K<double>::pi && thstep_d != K<double>::half_pi) {
-          nacc_off = -nacc_seg; natt_off = -steps_seg;
-          phistep_d = fmin(K<double>::pi, phistep_d * A.adj_scale);
-          thstep_d = fmin(K<double>::half_pi, thstep_d * A.adj_scale);
-        } else if (ratio < A.adj_lb) {
-          nacc_off = -nacc_seg; natt_off = -steps_seg;
-          phistep_d /= A.adj_scale;
-          thstep_d /= A.adj_scale;
-        }
+        const Adapted a = adapt_steps(nacc_off, natt_off, nacc_seg, steps_seg, A.adj_lb, A.adj_ub, A.adj_scale, phistep_d, thstep_d);
+        phistep_d = a.phistep; thstep_d = a.thstep; nacc_off = a.nacc_off; natt_off = a.natt_off;
         phistep = (R)(phistep_d / AG::unit); thstep = (R)(thstep_d / AG::unit);
       }
     }

@@ -53,6 +53,10 @@ struct CaseConst {      // physics scalars of one case (inc/eap_chain.jl:89-108)
   double cluster_prob;    // --cluster-prob: probability of NOT attempting a cluster flip (planar main: OF flipping)
   double cutoff_radius;   // --cutoff-radius in monomer lengths (energy-type cutoff)
 };
+// AntiDipoleWeightFunction's scale (inc/average.jl:104-124): the umbrella weight of a configuration is sum(u) times this
+__host__ __device__ inline double umbrella_wscale(const CaseConst &cc) {
+  return (0.2 + 0.8 * exp(-(cc.Fx * cc.Fx + cc.Fz * cc.Fz) / cc.kT)) / cc.kT;
+}
 
 struct InitOpts {       // how EAPChain(pargs) draws the first configuration (inc/eap_chain.jl:61-79)
   int use_x0;           // 0: uniform angles; 1: (x0_phi, x0_theta) for every monomer; 2: per monomer from x0_vec
@@ -81,6 +85,37 @@ struct SweepArgs {
                              // chains than a wave has lanes (run_job_queue<true>); 0: blocks never straddle a case
   int32_t pad_;
 };
+
+template <typename R> struct K;  // constants of the adaptation logic (f64, like the reference)
+template <> struct K<double> {
+  static constexpr double pi = 3.14159265358979323846;
+  static constexpr double half_pi = 1.57079632679489661923;
+};
+// The step-size adaptation of mcmc_eap_chain.jl:301-322 and mcmc_clustering_eap_chain.jl:287-308, per chain and in f64 like
+// the reference, at the end of an adaptation window.  The acceptance window is kept as its value when the segment began
+// (nacc_off, natt_off) plus the segment's own counts; a window that restarts becomes minus those counts.  The steps are in
+// radians.  Returns the new steps and the new window.  THETA = false is the planar main's form
+// (2D/mcmc_clustering_eap_chain.jl:257-275): phi_step alone, thstep passed through.  Every step kernel calls this; run_segment
+// of pstat_kernels.hip keeps a copy of its own.  Everything goes in and out by value and the function is always
+// inlined: that compiles to what the rule written in place compiles to (profiles/cluster_step/ab_stated_once.txt).
+struct Adapted { double phistep, thstep; int64_t nacc_off, natt_off; };
+template <bool THETA = true>
+__host__ __device__ __forceinline__ Adapted adapt_steps(int64_t nacc_off, int64_t natt_off, const int nacc_seg, const int steps_seg,
+                                                        const double lb, const double ub, const double scale, double phistep,
+                                                        double thstep) {
+  const int64_t nacc = nacc_off + nacc_seg, natt = natt_off + steps_seg;
+  const double ratio = (double)nacc / (double)natt;
+  if (ratio > ub && phistep != K<double>::pi && (!THETA || thstep != K<double>::half_pi)) {
+    nacc_off = -nacc_seg; natt_off = -steps_seg;
+    phistep = fmin(K<double>::pi, phistep * scale);
+    if (THETA) thstep = fmin(K<double>::half_pi, thstep * scale);
+  } else if (ratio < lb) {
+    nacc_off = -nacc_seg; natt_off = -steps_seg;
+    phistep /= scale;
+    if (THETA) thstep /= scale;
+  }
+  return Adapted{phistep, thstep, nacc_off, natt_off};
+}
 
 // ---------------------------------------------------------------------------------------------
 // Random stream contract (restated, not shared, in oracle/eap_oracle.c).  Two generators:

@@ -258,7 +258,7 @@ __device__ __forceinline__ void run_segment(const SweepArgs &A, const DevState &
   // umbrella sampling (inc/average.jl:104-124): w = sum(u) * wscale - log_gauge enters log pi, and
   // every record is weighted by 1/e^w.  Only w - w(first configuration) is ever needed here.
   const bool umb = RARE && rare.umb;
-  const R wscale = umb ? (R)((0.2 + 0.8 * exp(-(cc.Fx * cc.Fx + cc.Fz * cc.Fz) / cc.kT)) / cc.kT) : (R)0;
+  const R wscale = umb ? (R)umbrella_wscale(cc) : (R)0;
   R uref = umb ? (R)S.uref[c] : (R)0;
   bool regauged = false;
   double wnorm = umb ? S.wnorm[c] : 0.0;
@@ -851,7 +851,8 @@ __device__ __forceinline__ void run_segment(const SweepArgs &A, const DevState &
     left -= chunk;
     steps_seg += chunk;
 
-    // ---- step-size adaptation, mcmc_eap_chain.jl:301-322 (per chain, in f64 like the reference)
+    // ---- step-size adaptation, mcmc_eap_chain.jl:301-322 (per chain, in f64 like the reference): this kernel's own copy of
+    // adapt_steps (pstat_device.h), kept in place because the loop's compiled shape reacts to edits around it
     if (A.adaptive) {
       to_adj -= chunk;
       if (to_adj == 0) {
@@ -997,7 +998,7 @@ __global__ void reinit_kernel(SweepArgs A, DevState S, const CaseConst *__restri
   if (adopt) {
     // the cached log-density includes the umbrella weight function w = sum(u) * wscale (inc/acceptance.jl:13-16,
     // inc/average.jl:104-124); wscale as in run_segment
-    const double ws = umbrella ? (0.2 + 0.8 * exp(-(cc.Fx * cc.Fx + cc.Fz * cc.Fz) / cc.kT)) / cc.kT : 0.0;
+    const double ws = umbrella ? umbrella_wscale(cc) : 0.0;
     const double lp_old = -U_old / cc.kT + log(prod_old) + S.obs[OBS_USUM * C + c] * ws;
     const double lp_new = -U_new / cc.kT + log(prod_new) + usum * ws;
     S.lag[c] = (lp_old + S.lag[c]) - lp_new;

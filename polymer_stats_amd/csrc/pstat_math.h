@@ -15,12 +15,6 @@ template <typename R> struct Vec2;
 template <> struct Vec2<float> { using type = float2; };
 template <> struct Vec2<double> { using type = double2; };
 
-template <typename R> struct K;  // constants of the adaptation logic (f64, like the reference)
-template <> struct K<double> {
-  static constexpr double pi = 3.14159265358979323846;
-  static constexpr double half_pi = 1.57079632679489661923;
-};
-
 // exp and log of a double for the acceptance test of the f64 kernels, ~30 instructions each (the library
 // versions cost several times that).  Classic forms: exp by x = k ln2 + r, |r| <= ln2/2, a degree-13
 // polynomial and one v_ldexp; log by x = 2^k (1 + f), sqrt(1/2) < 1 + f < sqrt(2), s = f / (2 + f) and the

@@ -103,7 +103,7 @@ __device__ __forceinline__ void run_planar_segment(const SweepArgs &A, const Dev
   double OU = S.obs[OBS_U * C + c], usum = S.obs[OBS_USUM * C + c];
   double lag = S.lag[c];                            // log(alpha) of the last accepted proposal of this mcmc() call
   const bool umb = umb_on != 0;
-  const double wscale = umb ? (0.2 + 0.8 * exp(-(cc.Fx * cc.Fx + cc.Fz * cc.Fz) / cc.kT)) / cc.kT : 0.0;
+  const double wscale = umb ? umbrella_wscale(cc) : 0.0;
   double uref = umb ? S.uref[c] : 0.0;
   bool regauged = false;
   double wnorm = umb ? S.wnorm[c] : 0.0;
@@ -312,15 +312,8 @@ __device__ __forceinline__ void run_planar_segment(const SweepArgs &A, const Dev
       to_adj -= chunk;
       if (to_adj == 0) {
         to_adj = spa;
-        const int64_t nacc = nacc_off + nacc_seg, natt = natt_off + steps_seg;
-        const double ratio = (double)nacc / (double)natt;
-        if (ratio > A.adj_ub && phistep != K<double>::pi) {
-          nacc_off = -nacc_seg; natt_off = -steps_seg;
-          phistep = fmin(K<double>::pi, phistep * A.adj_scale);
-        } else if (ratio < A.adj_lb) {
-          nacc_off = -nacc_seg; natt_off = -steps_seg;
-          phistep /= A.adj_scale;
-        }
+        const Adapted a = adapt_steps<false>(nacc_off, natt_off, nacc_seg, steps_seg, A.adj_lb, A.adj_ub, A.adj_scale, phistep, 0.0);
+        phistep = a.phistep; nacc_off = a.nacc_off; natt_off = a.natt_off;
       }
     }
   }

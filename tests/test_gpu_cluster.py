@@ -73,7 +73,9 @@ def _run_gpu(e, pp, nsteps, burn_sched=(), burn_in=0):
 
 
 def _bit_parity(ps, oracle, nsteps, nchains, burn_sched=(), burn_in=0, home=None, **kw):
+    """Returns the chains' final (phi_step, theta_step), which it has compared with the oracle's."""
     op, pp = _pair(ps, nsteps, nchains, ps.F64, burn_sched, burn_in, **kw)
+    steps = np.zeros((nchains, 2))
     with ps.Ensemble(pp) as e:
         _check_home(e, home)
         _run_gpu(e, pp, nsteps, burn_sched, burn_in)
@@ -86,10 +88,12 @@ def _bit_parity(ps, oracle, nsteps, nchains, burn_sched=(), burn_in=0, home=None
             assert np.array_equal(g["rng"], o.rng), f"rng differs, chain {c}"
             assert g["nacc_total"] == o.nacc_total
             assert g["phi_step"] == o.phi_step and g["theta_step"] == o.theta_step
+            steps[c] = g["phi_step"], g["theta_step"]
             # value / normalizer: with --umbrella-sampling the gauge constant of the weights cancels
             np.testing.assert_allclose(g["sums"] / g["normalizer"], o.avg, rtol=1e-9, atol=1e-9)
             np.testing.assert_allclose(x["sums"] / g["normalizer"], o.extra_sums / o.norm, rtol=1e-9, atol=1e-9)
             np.testing.assert_allclose(e.microstate(c), np.r_[o.r, o.p, o.U], rtol=1e-9, atol=1e-8)
+    return steps
 
 
 @pytest.mark.parametrize("rng", [0, 1])
@@ -166,6 +170,22 @@ def test_f64_bit_parity_per_monomer_x0(ps, oracle, f64_home):
 def test_f64_bit_parity_cluster_umbrella(ps, oracle, f64_home):
     _bit_parity(ps, oracle, 3000, 64, home=f64_home, n=14, E0=1.5, K1=1.0, K2=0.0, Fz=0.2, seed=27, umbrella=1,
                 bend_mod=0.4, bend_angle=0.2, cluster_prob=0.5, steps_per_adjust=500)
+
+
+@pytest.mark.parametrize("umbrella", [0, 1])
+def test_f64_bit_parity_adaptation_both_branches(ps, oracle, umbrella, f64_home):
+    """Both branches of the adaptation rule (adapt_steps) in every f64 home, the chain-per-wavefront kernel included.  Twelve
+    windows of 50 steps with adj_lb = adj_ub = 0.31: nacc / 50 is never 0.31, so every window takes exactly one branch, u
+    growths and d = 12 - u shrinkages.  The chain is stretched hard (F b / kT = 20) and starts with steps far too wide,
+    so it shrinks first and grows once the acceptance has risen: no step reaches its clamp, and k = log(step / step0) /
+    log(scale) = u - d is an integer with -12 < k < 12, i.e. u >= 1 and d >= 1, for every chain.  _bit_parity compares the
+    step sizes, and everything they steer, bit for bit with the oracle's."""
+    kw = dict(n=6, E0=1.0, K1=1.0, K2=0.1, Fz=10.0, kT=0.5, seed=71, umbrella=umbrella, bend_mod=0.3, cluster_prob=0.5,
+              phi_step=3.0, theta_step=1.5, steps_per_adjust=50, adj_lb=0.31, adj_ub=0.31, adj_scale=1.5)
+    steps = _bit_parity(ps, oracle, 600, 64, home=f64_home, **kw)
+    k = np.log(steps / [3.0, 1.5]) / np.log(1.5)
+    assert np.all(np.abs(k - np.round(k)) < 1e-9) and np.array_equal(np.round(k[:, 0]), np.round(k[:, 1]))
+    assert np.all(np.abs(k) < 12) and np.all(np.round(k) % 2 == 0)
 
 
 @pytest.mark.parametrize("n,kw", [
@@ -268,6 +288,34 @@ def test_f32_cluster_statistics(ps, oracle, energy_type, K1, f32_home):
     ex = np.array([oracle.run(op, chain_id=(1 << 20) + c, mode="cluster").extra_sums / nsteps for c in range(96)])
     zx = (gx - ex.mean(0)) / np.sqrt(gxs ** 2 + ex.var(0, ddof=1) / len(ex))
     assert np.all(np.abs(zx) < 4.5), (zx, gx, ex.mean(0))
+
+
+def test_f32_cluster_umbrella_with_adaptation(ps, oracle, f32_home):
+    """Umbrella sampling while the adaptation fires, in both f32 homes: the physics and the adaptation settings of
+    test_f64_bit_parity_adaptation_both_branches (every one of the twelve windows of the recorded run takes one branch, and
+    both are taken: k = log(step / step0) / log(scale) is even with |k| < 12), after a burn-in rung of 300 steps.
+    As in test_f32_cluster_statistics: the pooled weighted averages (value / normaliser per chain) and the acceptance ratio
+    within 4.5 combined standard errors of the oracle's, whose chains run the same protocol."""
+    kw = dict(n=6, E0=1.0, K1=1.0, K2=0.1, Fz=10.0, kT=0.5, seed=37, umbrella=1, bend_mod=0.3, cluster_prob=0.5,
+              phi_step=3.0, theta_step=1.5, steps_per_adjust=50, adj_lb=0.31, adj_ub=0.31, adj_scale=1.5)
+    nsteps, burn, nref = 600, 300, 1024
+    op, pp = _pair(ps, nsteps, 4096, ps.F32, (1.0,), burn, **kw)
+    with ps.Ensemble(pp) as e:
+        assert ("state in memory" in e.launch_info().kernel.decode()) == (f32_home == "memory")
+        _run_gpu(e, pp, nsteps, (1.0,), burn)
+        s = e.summary()
+        steps = np.array([e.chain_state(c)["phi_step"] for c in range(64)])
+    k = np.log(steps / 3.0) / np.log(1.5)
+    assert np.all(np.abs(k - np.round(k)) < 1e-9) and np.all(np.abs(k) < 12) and np.all(np.round(k) % 2 == 0)
+    gm, gs = np.array(s.avg), np.array(s.stderr)
+    assert np.all(np.isfinite(gm)) and np.all(np.isfinite(gs))
+    sums, norm, nacc = oracle.run_many(op, 1 << 20, nref, nthreads=8, mode="cluster")
+    om, os_ = pooled(sums, norm)
+    z = (gm - om) / np.sqrt(gs ** 2 + os_ ** 2 + 1e-300)
+    assert np.all(np.abs(z) < 4.5), (z, gm, om)
+    oar = nacc / nsteps
+    zar = (s.acceptance_ratio - oar.mean()) / np.hypot(s.ar_stderr, oar.std(ddof=1) / np.sqrt(nref))
+    assert abs(zar) < 4.5, (s.acceptance_ratio, oar.mean())
 
 
 @pytest.mark.parametrize("energy_type,K1", [(0, 1.0), (2, 0.2)])
