@@ -464,6 +464,27 @@ def _allpairs_configs():
                  cutoff_radius=3.0, **_X0, **phys)
         out.append(Config(f"f32-allpairs-cluster-n{n}-{'cutoff' if en == CUTOFF else 'interacting'}", "cluster_wave_kernel<float>",
                           F32, p, chains=6, T=600, cluster=True))
+    # The packed ring sums (ring_pair_sum_pk<4>, <8>, and its cutoff select) and every M >= 2 form of the clustering kernel: the
+    # same recipe at the lengths the reference's phase sweeps use (n = 100, 200, 400) and at partial rings (n = 130: M = 4,
+    # L = 34; n = 257: M = 8, L = 34).  A judged step costs the oracle two O(n^2) sums, so the long chains judge fewer
+    # chains (`chains`), never fewer steps: T is set by the rule above (test_step_judge_cpu.py: a judge with E0 (1 + 2^-8)
+    # is caught at this length).
+    for i, (n, T, chains) in enumerate(((200, 800, 3), (257, 800, 2))):
+        ct = dict(chain_type=DIELECTRIC, E0=30.0, K1=0.0125, K2=0.0025, Fz=0.3, Fx=8.0, b=1.0) if i % 2 == 0 else \
+            dict(chain_type=POLAR, E0=100.0, mu=0.1, Fz=0.3, Fx=8.0, b=1.0, do_flips=1)
+        p = dict(n=n, energy_type=INTERACTING, rng=MWC if i % 2 else XOSHIRO, kT=1.0, seed=3000 + n, **ct, **_X0,
+                 **(_ADAPT if i % 2 else _FIXED))
+        out.append(Config(f"f32-allpairs-n{n}", "interacting_kernel<float>", F32, p, chains=chains, T=T))
+    inter = dict(E0=20.0, K1=0.02, K2=0.005, Fz=0.3, Fx=8.0, **_ADAPT)
+    cut = dict(E0=10.0, K1=0.4, K2=0.3, Fz=0.3, Fx=8.0, phi_step=0.15, theta_step=0.15, **_FIXED)
+    # (the perturbed judge is caught about once in 3000 ... 7000 judged steps of these rows, hence their T; at n = 130 the
+    #  seeds 3630 ... 3633 do not meet it within 1200 steps of three chains, 3634 does)
+    for n, en, phys, T, chains, seed in ((100, INTERACTING, inter, 1200, 4, 3600), (200, CUTOFF, cut, 1200, 3, 3700),
+                                         (400, CUTOFF, cut, 2400, 1, 3900), (130, INTERACTING, inter, 1200, 4, 3634)):
+        p = dict(n=n, energy_type=en, rng=MWC, kT=1.0, seed=seed, chain_type=DIELECTRIC, b=1.0, cluster_prob=0.5,
+                 cutoff_radius=3.0, **_X0, **phys)
+        out.append(Config(f"f32-allpairs-cluster-n{n}-{'cutoff' if en == CUTOFF else 'interacting'}", "cluster_wave_kernel<float>",
+                          F32, p, chains=chains, T=T, cluster=True))
     return out
 
 

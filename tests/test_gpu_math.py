@@ -194,6 +194,9 @@ def test_f32_sincos_in_turns(flavour):
     assert max(worst) <= sj.SINCOS_ABS
     q = mr.probe(flavour, "sc_f32", np.array([0.0, 0.25, 0.5, 0.75]))
     report(flavour, "v_sin/v_cos at 0, 1/4, 1/2, 3/4 turns", " ".join("%g" % v for v in q.ravel()))
+    # exact at the quarter turns.  The pair census (tests/pair_ref.py) rests on cos(1/4 turn) == 0: a monomer at theta = 1/4
+    # turn then has the dipole a n_z n = 0 exactly and its pair terms are exact zeros, not dust
+    assert np.array_equal(q, [[0.0, 1.0], [1.0, 0.0], [0.0, -1.0], [-1.0, 0.0]])
 
 
 @FLAV

@@ -150,7 +150,8 @@ def test_configurations_stay_inside_the_margin_derivation():
     names = " ".join(sj.CONFIG_IDS)
     for must in ("f32-sweep", "q16-sweep", "f32lds-cluster", "q16lds-cluster", "f32mem-cluster", "f32-allpairs-n23",
                  "f32-allpairs-n64", "f32-allpairs-n100", "f32-allpairs-n130", "allpairs-cluster-n20-interacting",
-                 "allpairs-cluster-n64-cutoff"):
+                 "allpairs-cluster-n64-cutoff", "f32-allpairs-n200", "f32-allpairs-n257", "allpairs-cluster-n100-interacting",
+                 "allpairs-cluster-n200-cutoff", "allpairs-cluster-n400-cutoff", "allpairs-cluster-n130-interacting"):
         assert must in names
 
 
