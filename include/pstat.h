@@ -291,7 +291,7 @@ int pstat_microstate(pstat_handle *h, int64_t chain, double out[7]);
 
 /* The quantities printed at mcmc_eap_chain.jl:365,386-395.  Synchronises.  Like every accessor that
  * synchronises (pstat_sync, pstat_reduce_host, pstat_rolling, pstat_microstate, pstat_chain_state,
- * pstat_chain_extras, pstat_checkpoint, pstat_corr_read, pstat_corr_rows, pstat_shape_read, pstat_shape_rows, pstat_series_read, pstat_series_error_bars, pstat_hist_read) it fails with PSTAT_ERR_HIP if a launch since the last successful
+ * pstat_chain_extras, pstat_checkpoint, pstat_corr_read, pstat_corr_rows, pstat_shape_read, pstat_shape_rows, pstat_pdist_read, pstat_pdist_rows, pstat_series_read, pstat_series_error_bars, pstat_hist_read) it fails with PSTAT_ERR_HIP if a launch since the last successful
  * call did not run to completion (a job of the persistent kernels timed out waiting for its predecessor):
  * the handle's averages are then not the averages of the steps it was asked for. */
 int pstat_summary_get(pstat_handle *h, int32_t icase, pstat_summary *out);
@@ -586,6 +586,72 @@ int pstat_shape_read(pstat_handle *h, pstat_shape *g, double *sum /* [ncases][nc
 int pstat_shape_rows(pstat_handle *h, pstat_shape *g, const double **dev_rows /* DEVICE memory */, int64_t *nrows, int64_t *stride);
 int pstat_shape_clear(pstat_handle *h, pstat_shape *g);
 void pstat_shape_close(pstat_handle *h, pstat_shape *g);
+
+/* Pair distances on the device: per case the mean-square internal distance R^2(s), the closest approach of two monomers, the
+ * distribution P(r) of the distances r_ij = |x_i - x_j| between two monomers of ONE chain, and the orientationally averaged
+ * (Debye) structure factor.  The pair energies collapse into 1 / r^3 contacts; this is the recorder that shows how close the
+ * closest pair is.  A pdist object is a sibling of a shape object: it belongs to the handle it was opened on, one record is a
+ * pair of launches on the handle's stream that reads the stored angles of EVERY chain where they sit and writes the object's
+ * own buffers only.
+ * The contract (DESIGN.md 3.18 states it in full; polymer_stats_amd/csrc/pstat_pdist.hip is the device's statement).  All in f64
+ * from the doubles pstat_chain_state returns for the angles, whatever the handle's precision:
+ *   positions       exactly the shape recorder's: x_i = b (sum_{j <= i} n_j - n_i / 2); a planar handle's n_i sits in the x and z
+ *                   slots, y = 0.
+ *   pair distance   for i < j: d = x_j - x_i;  r2 = (d_x d_x + d_y d_y) + d_z d_z, every product rounded (a planar handle: without
+ *                   the y term);  r = sqrt(r2), correctly rounded.
+ *   options         fixed at open (pstat_pdist_spec): max_sep in 0 .. n - 1 (-1 means n - 1); min_sep in 1 .. n - 1; nbins >= 0;
+ *                   rmax > 0 and finite, needed when nbins > 0, in absolute units, shared by all cases (spec.rmax) or one per
+ *                   case (rmax_per_case, which then replaces spec.rmax); the device gets inv = nbins / rmax, computed once on the
+ *                   host; q[nq], nq >= 0 magnitudes >= 0 in absolute units.
+ *   columns         per chain, in this order; ncols = max_sep + 1 + (nbins ? nbins + 1 : 0) + nq:
+ *     msd           max_sep columns, s = 1 .. max_sep:  R2(s) = (1 / (n - s)) sum_{i = 0}^{n - 1 - s} r2_{i,i+s}.
+ *     rmin          one column: the minimum of r_ij over the pairs with j - i >= min_sep.
+ *     histogram     nbins + 1 columns, absent when nbins = 0: per-chain COUNTS, as doubles, of the pairs with j - i >= min_sep.
+ *                   t = r * inv; the pair goes to bin (int)t if t < nbins, otherwise to the last column, "above": r = 0 falls in
+ *                   bin 0 and r = rmax in "above".  A chain's columns add up to (n - min_sep)(n - min_sep + 1) / 2 exactly.
+ *     Debye         nq columns:  S(q) = 1 + (2 / n) sum_{i < j} sinc(q r_ij) over ALL pairs, whatever min_sep is;  x = q r is
+ *                   rounded once, sinc(0) = 1 exactly and otherwise sin(x) / x with the device's < 1 ulp sine; q = 0 gives
+ *                   exactly n.  A planar handle uses the same formula: the flat chain oriented at random in space.  The average
+ *                   over in-plane orientations only would need the Bessel function J0, which the device math does not have.
+ *   totals          as for a shape object: per case and column one record adds the sum over the case's chains of the per-chain
+ *                   value to `sum` and the sum of its square to `sumsq`; both are additive across handles; a row is the record's
+ *                   sum / num_chains.
+ *   reproducible    no floating-point atomics; the order of every floating-point addition depends on (ncases, num_chains, n, the
+ *                   object's options) only.  A chain's histogram is counted with integer adds, whose sum has no order.
+ *
+ *   pstat_pdist_open    q and rmax_per_case: host memory, copied; rmax_per_case may be NULL.  capacity_rows as for a shape object.
+ *                       Before the device is touched, with a message naming the argument, PSTAT_ERR_INVALID_ARG: null
+ *                       arguments (a null q with nq > 0 among them); n < 2 (there is no pair); max_sep or min_sep out of range;
+ *                       nbins < 0; nq < 0; nbins > 0 with an rmax that is not finite or not positive or leaves no finite
+ *                       nbins / rmax; a q that is negative or not finite; q b n >= 1e5 for any case (below that the device's
+ *                       sine is its < 1 ulp routine); capacity_rows < 0.  PSTAT_ERR_UNSUPPORTED: nq > PSTAT_PDIST_MAX_Q = 64;
+ *                       nbins > PSTAT_PDIST_MAX_BINS = 512; an umbrella-sampling handle (its samples carry per-chain weights
+ *                       whose gauge the sums do not hold); a chain whose positions and one chain's nbins + 1 32-bit counters do
+ *                       not fit the 60 KiB of LDS a workgroup keeps them in: n > (61440 - 8 ceil((nbins + 1) / 2)) / 24, that
+ *                       is 2560 without a histogram and 2474 with 512 bins (planar handles: / 16, 3840 and 3711).
+ *   pstat_pdist_record, pstat_advance_pdist, pstat_pdist_read, pstat_pdist_rows, pstat_pdist_clear, pstat_pdist_close
+ *                       what the pstat_shape_* call of the same name does for a shape object, every rule included:
+ *                       PSTAT_ERR_TOO_SMALL before anything is enqueued; _read and _rows synchronise and fail after an
+ *                       incomplete launch; pstat_blocking_device accepts the rows; pstat_destroy closes the objects still open;
+ *                       the object is not part of a checkpoint.
+ *   An object of another handle (or a closed one) is PSTAT_ERR_INVALID_ARG.  Every home, every precision and planar handles
+ *   are accepted. */
+#define PSTAT_PDIST_MAX_Q 64
+#define PSTAT_PDIST_MAX_BINS 512
+typedef struct pstat_pdist_spec {
+  int32_t max_sep, min_sep, nbins, nq;
+  double rmax;
+} pstat_pdist_spec;
+typedef struct pstat_pdist pstat_pdist;
+int pstat_pdist_open(pstat_handle *h, const pstat_pdist_spec *spec, const double *q /* host [nq] */,
+                     const double *rmax_per_case /* host [ncases], or NULL */, int64_t capacity_rows, pstat_pdist **out);
+int pstat_pdist_record(pstat_handle *h, pstat_pdist *g);
+int pstat_advance_pdist(pstat_handle *h, pstat_pdist *g, int64_t nsteps, int64_t stepout);
+int pstat_pdist_read(pstat_handle *h, pstat_pdist *g, double *sum /* [ncases][ncols] */, double *sumsq /* [ncases][ncols] */,
+                     int64_t *records);
+int pstat_pdist_rows(pstat_handle *h, pstat_pdist *g, const double **dev_rows /* DEVICE memory */, int64_t *nrows, int64_t *stride);
+int pstat_pdist_clear(pstat_handle *h, pstat_pdist *g);
+void pstat_pdist_close(pstat_handle *h, pstat_pdist *g);
 
 /* Per-chain accessors for tests and tooling (host buffers).  angles: theta[n] then phi[n] as
  * doubles, radians; sums: the 16 per-chain running sums in rolling.csv order;

@@ -252,6 +252,43 @@ def parse_shape(text: str):
     return "shape", q
 
 
+def parse_pdist(text: str):
+    """--pdist RMAX:NBINS[,sep=MAXSEP][,min=MINSEP][,q=QMAX:NQ] of tools/run_sweep.py -> ("pdist", dict(rmax, nbins, max_sep,
+    min_sep, q)): the distances below RMAX (absolute units) in NBINS bins (NBINS 0: no histogram), R2(s) up to s = MAXSEP
+    (default -1: n - 1), closest approach and histogram over the pairs at least MINSEP apart along the chain (default 1), and the
+    Debye S(q) at the NQ magnitudes QMAX (1 .. NQ) / NQ (default: none)."""
+    parts = [t.strip() for t in str(text).split(",")]
+    spec = dict(max_sep=-1, min_sep=1, q=[])
+    try:
+        head = parts[0].split(":")
+        if len(head) != 2:
+            raise ValueError
+        spec["rmax"], spec["nbins"] = float(head[0]), int(head[1])
+        if not np.isfinite(spec["rmax"]) or spec["rmax"] <= 0.0 or spec["nbins"] < 0:
+            raise ValueError
+        for entry in parts[1:]:
+            key, _, value = entry.partition("=")
+            if key == "sep" and int(value) >= -1:
+                spec["max_sep"] = int(value)
+            elif key == "min" and int(value) >= 1:
+                spec["min_sep"] = int(value)
+            elif key == "q" and len(value.split(":")) == 2:
+                qmax, nq = float(value.split(":")[0]), int(value.split(":")[1])
+                if nq < 1 or not np.isfinite(qmax) or qmax <= 0.0:
+                    raise ValueError
+                spec["q"] = [qmax * j / nq for j in range(1, nq + 1)]
+            else:
+                raise ValueError
+    except ValueError:
+        raise ReferenceError_(f"--pdist '{text}' not understood: RMAX:NBINS[,sep=MAXSEP][,min=MINSEP][,q=QMAX:NQ] with RMAX > 0, "
+                              "NBINS >= 0, MAXSEP >= -1, MINSEP >= 1, QMAX > 0 and NQ >= 1")
+    if spec["nbins"] > _lib.PDIST_MAX_BINS:
+        raise ReferenceError_(f"--pdist '{text}': {spec['nbins']} bins, at most {_lib.PDIST_MAX_BINS}")
+    if len(spec["q"]) > _lib.PDIST_MAX_Q:
+        raise ReferenceError_(f"--pdist '{text}': {len(spec['q'])} magnitudes, at most {_lib.PDIST_MAX_Q}")
+    return "pdist", spec
+
+
 # ---------------------------------------------------------------------------------------------- recording the production run
 @dataclass(frozen=True)
 class Recording:
@@ -280,7 +317,7 @@ def _check_hist_specs(pargs: dict, specs):
 
 
 def _check_records(flag: str, pargs: dict):
-    """--corr and --shape (`flag`) keep a row per record: the run must give the blocking transform enough of them."""
+    """--corr, --shape and --pdist (`flag`) keep a row per record: the run must give the blocking transform enough of them."""
     stepout = int(pargs["stepout"])
     if not 1 <= stepout <= int(pargs["num-steps"]) or int(pargs["num-steps"]) // stepout < CORR_MIN_RECORDS:
         raise ReferenceError_(f"{flag} takes a record every --stepout steps of the production run and its standard errors from "
@@ -302,8 +339,21 @@ def _check_wave_vectors(pargs: dict, spec):
             raise ReferenceError_(f"--shape: |q| b n = {sum(abs(c) for c in v) * reach:g} for q = {v} is not below 1e5")
 
 
+def _check_pdist(pargs: dict, spec):
+    _check_records("--pdist", pargs)
+    n, o = int(pargs["num-monomers"]), spec[1]
+    if n < 2:
+        raise ReferenceError_(f"--pdist: a chain of n = {n} monomers has no pair")
+    if o["max_sep"] > n - 1 or o["min_sep"] > n - 1:
+        raise ReferenceError_(f"--pdist: sep={o['max_sep']}, min={o['min_sep']} must not be beyond n - 1 = {n - 1}")
+    reach = float(pargs["mlen"]) * n
+    for v in o["q"]:       # (the library refuses such a phase too)
+        if v * reach >= 1.0e5:
+            raise ReferenceError_(f"--pdist: q b n = {v * reach:g} for q = {v} is not below 1e5")
+
+
 def _totals_and_error_bars(g):
-    """What a Corr or a Shape with kept rows gives at the end of a recorded run."""
+    """What a Corr, a Shape or a Pdist with kept rows gives at the end of a recorded run."""
     return g.read(), g.error_bars(min_blocks=CORR_MIN_RECORDS)
 
 
@@ -370,11 +420,22 @@ RECORDINGS = {
         advance=Ensemble.advance_shape,
         read=_totals_and_error_bars,
         lines=lambda main, res, spec, k, p: shape_lines(*res, k)),
+    "pdist": _Kind(
+        flag="--pdist", ext=".pdist", parse=parse_pdist,
+        words=("pair-distance columns", "sums", "records", _GAUGE % "sums", _LIKE_HIST),
+        check=_check_pdist,
+        records=_every_stepout,
+        open=lambda e, spec, nrec: e.open_pdist(spec[1]["max_sep"], spec[1]["min_sep"],
+                                                (spec[1]["nbins"], spec[1]["rmax"]) if spec[1]["nbins"] else None, spec[1]["q"],
+                                                capacity_rows=nrec),
+        advance=Ensemble.advance_pdist,
+        read=_totals_and_error_bars,
+        lines=lambda main, res, spec, k, p: pdist_lines(*res, k)),
 }
 
 
 def check_recording(pargs: dict, rec: Recording, write_csv: bool = False, devices: int | None = None):
-    """What a Recording (tools/run_sweep.py's --error-bars, --hist, --corr, --shape; run_cases(..., record=rec)) cannot be
+    """What a Recording (tools/run_sweep.py's --error-bars, --hist, --corr, --shape, --pdist; run_cases(..., record=rec)) cannot be
     combined with, refused before any GPU work: the kind's own limits, then what all kinds refuse.  `devices`: how many hold the
     chains (default: those --devices names)."""
     row = RECORDINGS[rec.kind]
@@ -807,6 +868,29 @@ def shape_lines(res, eb, k: int) -> list[str]:
     for j, v in enumerate(res.q):
         i = len(_lib.SHAPE_NAMES) + j
         out.append(f"sq,{float(v[0])!r},{float(v[1])!r},{float(v[2])!r},{float(res.mean[k, i])!r},{float(eb.stderr[k, i])!r}")
+    return out
+
+
+def pdist_lines(res, eb, k: int) -> list[str]:
+    """`<case>.pdist`: CSV `name,x,value,stderr`: a row `msd` per separation (x = s), `rmin` (no x), a row `hist` per bin (x = the
+    bin's centre, value = the density P(r)), `above` (the share of the counted pairs at or beyond rmax) and a row `sq` per Debye
+    magnitude (x = q): the mean over records and chains and its blocked standard error from the records' rows (the histogram's
+    in the units of its value)."""
+    out = ["name,x,value,stderr"]
+    row = lambda name, x, v, e: f"{name},{x},{float(v)!r},{float(e)!r}"
+    for s in range(1, res.max_sep + 1):
+        out.append(row("msd", s, res.mean[k, s - 1], eb.stderr[k, s - 1]))
+    out.append(row("rmin", "", res.rmin[k], eb.stderr[k, res.max_sep]))
+    h0 = res.max_sep + 1
+    if res.nbins:
+        width, centers, density = float(res.rmax[k]) / res.nbins, res.centers(k), res.density(k)
+        for j in range(res.nbins):     # a row's column is the chains' mean count: / (pairs * width) turns it into the density
+            out.append(row("hist", repr(float(centers[j])), density[j], eb.stderr[k, h0 + j] / (res.pairs * width)))
+        share = res.above[k] / (res.records * res.num_chains * res.pairs)
+        out.append(row("above", "", share, eb.stderr[k, h0 + res.nbins] / res.pairs))
+        h0 += res.nbins + 1
+    for j, v in enumerate(res.q):
+        out.append(row("sq", repr(float(v)), res.mean[k, h0 + j], eb.stderr[k, h0 + j]))
     return out
 
 

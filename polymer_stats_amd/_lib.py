@@ -41,6 +41,10 @@ CORR_NAMES = ("nn", "zz", "mm")
 # the gyration block of a shape object (pstat_shape_*): its first PSTAT_SHAPE_GYR columns, in this order; S(q) columns follow
 SHAPE_NAMES = ("gxx", "gyy", "gzz", "gxy", "gxz", "gyz", "rg2", "trg2")
 SHAPE_MAX_Q = 512
+# a pair-distance object (pstat_pdist_*): its column families in column order, and the library's limits
+PDIST_NAMES = ("msd", "rmin", "hist", "sq")
+PDIST_MAX_Q = 64
+PDIST_MAX_BINS = 512
 
 # every symbol include/pstat.h declares (tests check the built library exports all of them)
 SYMBOLS = [
@@ -58,6 +62,8 @@ SYMBOLS = [
     "pstat_corr_close",
     "pstat_shape_open", "pstat_shape_record", "pstat_advance_shape", "pstat_shape_read", "pstat_shape_rows", "pstat_shape_clear",
     "pstat_shape_close",
+    "pstat_pdist_open", "pstat_pdist_record", "pstat_advance_pdist", "pstat_pdist_read", "pstat_pdist_rows", "pstat_pdist_clear",
+    "pstat_pdist_close",
 ]
 ABI_VERSION = 6
 
@@ -92,6 +98,10 @@ class Summary(C.Structure):
 
 class HistSpec(C.Structure):
     _fields_ = [("channel", C.c_int32), ("nbins", C.c_int32), ("lo", C.c_double), ("hi", C.c_double)]
+
+
+class PdistSpec(C.Structure):
+    _fields_ = [("max_sep", C.c_int32), ("min_sep", C.c_int32), ("nbins", C.c_int32), ("nq", C.c_int32), ("rmax", C.c_double)]
 
 
 def hist_spec(channel, nbins: int, lo: float, hi: float) -> HistSpec:
@@ -193,6 +203,14 @@ def load():
     L.pstat_shape_clear.argtypes = [vp, vp]
     L.pstat_shape_close.argtypes = [vp, vp]
     L.pstat_shape_close.restype = None
+    L.pstat_pdist_open.argtypes = [vp, C.POINTER(PdistSpec), dp, dp, i64, C.POINTER(vp)]
+    L.pstat_pdist_record.argtypes = [vp, vp]
+    L.pstat_advance_pdist.argtypes = [vp, vp, i64, i64]
+    L.pstat_pdist_read.argtypes = [vp, vp, dp, dp, ip]
+    L.pstat_pdist_rows.argtypes = [vp, vp, C.POINTER(vp), ip, ip]
+    L.pstat_pdist_clear.argtypes = [vp, vp]
+    L.pstat_pdist_close.argtypes = [vp, vp]
+    L.pstat_pdist_close.restype = None
     if L.pstat_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI version {L.pstat_abi_version()}, this binding needs {ABI_VERSION}: "
                           "rebuild it with `make -C polymer_stats_amd/csrc`")

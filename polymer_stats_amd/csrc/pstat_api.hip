@@ -135,6 +135,7 @@ struct pstat_handle {
   OpenList<pstat_hist> hists;
   OpenList<pstat_corr> corrs;
   OpenList<pstat_shape> shapes;
+  OpenList<pstat_pdist> pdists;
 };
 
 // ---- the recorder objects of a handle.  Each owns its device memory; the handle owns those that are open.
@@ -167,7 +168,7 @@ struct pstat_hist {
   size_t slots = 0;                 // int64 words of d_counts
 };
 
-// What the correlation and the shape recorder share: per-case column totals, summed over the chains of every record.
+// What the correlation, the shape and the pair-distance recorder share: per-case column totals, summed over the chains of every record.
 struct ColumnTotals {
   size_t stride = 0;                // ncases * ncols: doubles of one row
   int64_t records = 0;              // records enqueued since open / the last clear (known when a record is enqueued)
@@ -187,6 +188,12 @@ struct pstat_corr : ColumnTotals {
 struct pstat_shape : ColumnTotals {
   ShapeArgs args{};
   DeviceDoubles d_q;                // [nq][3]: the wave-vectors
+};
+
+// Per-case pair distances of one handle (pstat_pdist.hip).
+struct pstat_pdist : ColumnTotals {
+  PdistArgs args{};
+  DeviceDoubles d_tab;              // [nq] the magnitudes, then [ncases] nbins / rmax (the latter only with nbins > 0)
 };
 
 namespace {
@@ -651,6 +658,9 @@ int open_corr(pstat_handle *h, const pstat_corr *g, bool others = true) {
 int open_shape(pstat_handle *h, const pstat_shape *g, bool others = true) {
   return check_open(h, &pstat_handle::shapes, g, others, "the shape object is not an open one of this handle");
 }
+int open_pdist(pstat_handle *h, const pstat_pdist *g, bool others = true) {
+  return check_open(h, &pstat_handle::pdists, g, others, "the pdist object is not an open one of this handle");
+}
 
 // The end of every pstat_X_open: the handle takes the finished object and the caller gets its address.
 template <class T>
@@ -759,8 +769,10 @@ constexpr TotalsText kCorrText{"correlation object", "%lld rows of correlations 
                                "correlations of %zu columns, %lld rows: %s", "correlation totals: %s"};
 constexpr TotalsText kShapeText{"shape object", "%lld rows of shape columns do not fit the address space",
                                 "shape object of %zu columns, %lld rows: %s", "shape totals: %s"};
+constexpr TotalsText kPdistText{"pdist object", "%lld rows of pair-distance columns do not fit the address space",
+                                "pdist object of %zu columns, %lld rows: %s", "pdist totals: %s"};
 
-// The allocation tail of pstat_corr_open / pstat_shape_open, after the kind's own argument checks: a new object g with zeroed
+// The allocation tail of pstat_corr_open / pstat_shape_open / pstat_pdist_open, after the kind's own argument checks: a new object g with zeroed
 // totals of ncols columns per case, `partial` doubles of scratch and capacity_rows kept rows.
 template <class T>
 int new_totals(pstat_handle *h, int32_t ncols, int64_t capacity_rows, size_t partial, const TotalsText &text, std::unique_ptr<T> &g) {
@@ -831,6 +843,13 @@ int enqueue_corr(pstat_handle *h, pstat_corr *g) {
 
 int enqueue_shape(pstat_handle *h, pstat_shape *g) {
   HIP_TRY(launch_shape(g->args, h->S.ang, h->d_cases, g->d_q.p, g->d_partial.p, g->d_totals.p, g->next_row(), h->stream));
+  return recorded(g);
+}
+
+int enqueue_pdist(pstat_handle *h, pstat_pdist *g) {
+  const double *q = g->args.nq > 0 ? g->d_tab.p : nullptr;
+  const double *inv = g->args.nbins > 0 ? g->d_tab.p + g->args.nq : nullptr;
+  HIP_TRY(launch_pdist(g->args, h->S.ang, h->d_cases, q, inv, g->d_partial.p, g->d_totals.p, g->next_row(), h->stream));
   return recorded(g);
 }
 
@@ -1525,6 +1544,105 @@ int pstat_shape_clear(pstat_handle *h, pstat_shape *g) {
 }
 
 void pstat_shape_close(pstat_handle *h, pstat_shape *g) { close_object(h, &pstat_handle::shapes, g); }
+
+int pstat_pdist_open(pstat_handle *h, const pstat_pdist_spec *spec, const double *q, const double *rmax_per_case,
+                     int64_t capacity_rows, pstat_pdist **out) {
+  if (!h || !spec || !out) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
+  *out = nullptr;
+  const int64_t n = h->base.n;
+  const bool planar = h->cfg.planar;
+  const int32_t nbins = spec->nbins, nq = spec->nq, min_sep = spec->min_sep;
+  int32_t max_sep = spec->max_sep;
+  if (n < 2) return fail(PSTAT_ERR_INVALID_ARG, "n = %lld: a chain of fewer than two monomers has no pair", (long long)n);
+  if (max_sep < -1 || max_sep > n - 1)
+    return fail(PSTAT_ERR_INVALID_ARG, "max_sep must be in 0 .. n - 1 = %lld (or -1 for n - 1), not %d", (long long)n - 1, max_sep);
+  if (min_sep < 1 || min_sep > n - 1)
+    return fail(PSTAT_ERR_INVALID_ARG, "min_sep must be in 1 .. n - 1 = %lld, not %d", (long long)n - 1, min_sep);
+  if (nbins < 0) return fail(PSTAT_ERR_INVALID_ARG, "nbins must be >= 0, not %d", nbins);
+  if (nq < 0) return fail(PSTAT_ERR_INVALID_ARG, "nq must be >= 0, not %d", nq);
+  if (nbins > PSTAT_PDIST_MAX_BINS)
+    return fail(PSTAT_ERR_UNSUPPORTED, "nbins = %d: at most PSTAT_PDIST_MAX_BINS = %d bins per pdist object (a workgroup keeps a "
+                "chain's counters in LDS)", nbins, PSTAT_PDIST_MAX_BINS);
+  if (nq > PSTAT_PDIST_MAX_Q)
+    return fail(PSTAT_ERR_UNSUPPORTED, "nq = %d: at most PSTAT_PDIST_MAX_Q = %d magnitudes per pdist object", nq, PSTAT_PDIST_MAX_Q);
+  std::vector<double> tab;
+  try {
+    tab.resize((size_t)nq + (nbins > 0 ? (size_t)h->ncases : 0));
+  } catch (const std::bad_alloc &) {
+    return fail(PSTAT_ERR_NOMEM, "host allocation failed");
+  }
+  for (int c = 0; nbins > 0 && c < h->ncases; ++c) {
+    const double rmax = rmax_per_case ? rmax_per_case[c] : spec->rmax;
+    const char *which = rmax_per_case ? "rmax_per_case" : "rmax";
+    if (!std::isfinite(rmax) || !(rmax > 0.0))
+      return fail(PSTAT_ERR_INVALID_ARG, "%s = %g (case %d) must be finite and > 0 when nbins = %d", which, rmax, c, nbins);
+    const double inv = (double)nbins / rmax;
+    if (!std::isfinite(inv) || !(inv > 0.0))   // t = r * inv is then never NaN for a finite r
+      return fail(PSTAT_ERR_INVALID_ARG, "%s = %g (case %d) leaves no finite positive nbins / rmax for %d bins", which, rmax, c, nbins);
+    tab[(size_t)nq + (size_t)c] = inv;
+  }
+  if (nq > 0 && !q) return fail(PSTAT_ERR_INVALID_ARG, "q is null with nq = %d", nq);
+  for (int32_t k = 0; k < nq; ++k) {
+    if (!std::isfinite(q[k]) || q[k] < 0.0) return fail(PSTAT_ERR_INVALID_ARG, "q[%d] = %g must be finite and >= 0", k, q[k]);
+    for (int c = 0; c < h->ncases; ++c)
+      if (!(q[k] * std::fabs(h->cases[(size_t)c].b) * (double)n < 1.0e5))
+        return fail(PSTAT_ERR_INVALID_ARG, "q[%d] = %g with case %d (b = %g, n = %lld): q b n must stay below 1e5, where the device's "
+                    "sincos is its < 1 ulp routine", k, q[k], c, h->cases[(size_t)c].b, (long long)n);
+    tab[(size_t)k] = q[k];
+  }
+  if (capacity_rows < 0) return fail(PSTAT_ERR_INVALID_ARG, "capacity_rows must be >= 0, not %lld", (long long)capacity_rows);
+  if (h->cfg.umbrella)
+    return fail(PSTAT_ERR_UNSUPPORTED, "pair distances under --umbrella-sampling: the samples carry per-chain weights whose gauge "
+                "the sums do not hold");
+  if (n > pdist_max_n(planar, nbins))
+    return fail(PSTAT_ERR_UNSUPPORTED, "n = %lld: a chain's positions and its %d bin counters must fit the LDS of a workgroup, "
+                "n <= %lld for a %s handle", (long long)n, nbins > 0 ? nbins + 1 : 0, (long long)pdist_max_n(planar, nbins),
+                planar ? "planar" : "3D");
+  if (max_sep < 0) max_sep = (int32_t)(n - 1);
+  PdistArgs a{};
+  a.per = h->base.num_chains; a.ncases = h->ncases; a.n = n;
+  a.max_sep = max_sep; a.min_sep = min_sep; a.nbins = nbins; a.nq = nq;
+  a.ncols = max_sep + 1 + (nbins > 0 ? nbins + 1 : 0) + nq;
+  a.elem = (int32_t)h->elem; a.planar = planar ? 1 : 0;
+  pdist_layout(a);
+  std::unique_ptr<pstat_pdist> g;
+  PSTAT_TRY(new_totals(h, a.ncols, capacity_rows, tile_partial_doubles(a), kPdistText, g));
+  g->args = a;
+  if (!tab.empty()) {   // the magnitudes and the cases' nbins / rmax: a copy, the caller's tables may go
+    hipError_t e = g->d_tab.malloc(tab.size());
+    if (e != hipSuccess) return fail(PSTAT_ERR_NOMEM, kPdistText.nomem, g->stride, (long long)capacity_rows, hipGetErrorString(e));
+    e = hipMemcpy(g->d_tab.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(PSTAT_ERR_HIP, kPdistText.hip, hipGetErrorString(e));
+  }
+  return adopt(h->pdists, g, out);
+}
+
+int pstat_pdist_record(pstat_handle *h, pstat_pdist *g) {
+  PSTAT_TRY(open_pdist(h, g));
+  return totals_record(h, g, kPdistText, [&] { return enqueue_pdist(h, g); });
+}
+
+int pstat_advance_pdist(pstat_handle *h, pstat_pdist *g, int64_t nsteps, int64_t stepout) {
+  PSTAT_TRY(open_pdist(h, g));
+  return advance_recording(h, nsteps, stepout, g->capacity, g->rows, kPdistText.object, [&] { return enqueue_pdist(h, g); });
+}
+
+int pstat_pdist_read(pstat_handle *h, pstat_pdist *g, double *sum, double *sumsq, int64_t *records) {
+  PSTAT_TRY(open_pdist(h, g));
+  return totals_read(h, g, sum, sumsq, records);
+}
+
+int pstat_pdist_rows(pstat_handle *h, pstat_pdist *g, const double **dev_rows, int64_t *nrows, int64_t *stride) {
+  PSTAT_TRY(open_pdist(h, g, dev_rows && nrows && stride));
+  return totals_rows(h, g, dev_rows, nrows, stride);
+}
+
+int pstat_pdist_clear(pstat_handle *h, pstat_pdist *g) {
+  PSTAT_TRY(open_pdist(h, g));
+  return totals_clear(h, g);
+}
+
+void pstat_pdist_close(pstat_handle *h, pstat_pdist *g) { close_object(h, &pstat_handle::pdists, g); }
 
 int pstat_sync(pstat_handle *h) {
   if (!h) return fail(PSTAT_ERR_INVALID_ARG, "null handle");

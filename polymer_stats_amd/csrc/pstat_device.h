@@ -434,7 +434,7 @@ struct HistArgs {
 hipError_t launch_hist(const HistArgs &a, const double *src, const HistSpec *specs, int64_t *counts, int64_t *tails,
                        hipStream_t stream);
 
-// The tile frame the correlation and the shape recorder share (pstat_tile.h): a workgroup takes a tile of consecutive chains of
+// The tile frame the correlation, the shape and the pair-distance recorder share (pstat_tile.h): a workgroup takes a tile of consecutive chains of
 // one case, and its 256 threads are `groups` groups of `lpc` threads over the columns of the kind's hot loop.
 struct TileArgs {
   int64_t per, ncases, n;      // chains per case, cases, monomers
@@ -471,5 +471,20 @@ struct ShapeArgs : TileArgs {  // ncols = PSTAT_SHAPE_GYR + nq; tile_layout's wi
 // q = the wave-vectors [nq][3] in device memory (may be null when nq = 0)
 hipError_t launch_shape(const ShapeArgs &a, const void *ang, const CaseConst *cases, const double *q, double *partial,
                         double *totals, double *row, hipStream_t stream);
+
+// Per-case pair distances of the chains' current positions (pstat_pdist.hip states the contract).
+struct PdistArgs : TileArgs {  // ncols = max_sep + 1 + (nbins ? nbins + 1 : 0) + nq
+  int32_t max_sep, min_sep;    // R2(s) for s = 1 .. max_sep; rmin and the histogram over the pairs with j - i >= min_sep
+  int32_t nbins, nq;           // bins below rmax (0: no histogram); Debye magnitudes
+};
+// fills the tile fields of `a` from the others: tile_layout's, with fewer chains per tile where one chain's bin counters would
+// not fit LDS behind the positions
+void pdist_layout(PdistArgs &a);
+// the longest chain whose positions and one chain's nbins + 1 counters fit a workgroup's LDS beside the scratch
+int64_t pdist_max_n(int planar, int nbins);
+// one record, as launch_shape; q = the magnitudes [nq], inv = nbins / rmax per case [ncases] in device memory (null when there
+// are none)
+hipError_t launch_pdist(const PdistArgs &a, const void *ang, const CaseConst *cases, const double *q, const double *inv,
+                        double *partial, double *totals, double *row, hipStream_t stream);
 
 }  // namespace pstat

@@ -21,7 +21,7 @@
 //       case has fewer or LDS is short), as corr_stage1 does.
 //       Phase 1: the threads load the tile's angles with the chain index fastest, take two sincos per monomer (one for a planar
 //       handle) and leave the unit vectors in LDS, component by component (24 n bytes per chain, 16 n planar).
-//       Phase 2: the prefix sum, in place.  A wavefront takes one (chain, component) sequence at a time: lane l sums its segment
+//       Phase 2 (tile_positions, pstat_tile.h: the pair-distance recorder's too): the prefix sum, in place.  A wavefront takes one (chain, component) sequence at a time: lane l sums its segment
 //       of ceil(n / 64) consecutive monomers in order, the lanes' sums go through a 6-level shift-and-add scan, and the lane
 //       rewrites its segment as b (running sum - n_i / 2).  The tree depends on n alone.
 //       Phase 3: a wavefront per chain, lanes strided over i: wave_sum of the three coordinates gives the centre, wave_sum of the
@@ -50,16 +50,6 @@ namespace pstat {
 
 namespace {
 
-// inclusive scan over the 64 lanes: the shift-and-add tree whose order is part of every position
-__device__ __forceinline__ double wave_scan(double v, const int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const double up = __shfl_up(v, off, 64);
-    if (lane >= off) v += up;
-  }
-  return v;
-}
-
 template <bool PLANAR>
 __global__ __launch_bounds__(TILE_THREADS) void shape_stage1(const ShapeArgs a, const void *__restrict__ ang,
                                                              const CaseConst *__restrict__ cases, const double *__restrict__ qtab,
@@ -69,27 +59,11 @@ __global__ __launch_bounds__(TILE_THREADS) void shape_stage1(const ShapeArgs a, 
   // px[q][i], pz[q][i], (py[q][i]) for chain q of the tile: unit vectors first, positions after phase 2
   const Tile w = tile_of(a, lds);
   const int n = (int)a.n, tc = w.tc, ns = w.ns;
-  constexpr int COMPS = PLANAR ? 2 : 3;
   double *px = w.x, *pz = w.z, *py = w.y;
   const double b = cases[w.kcase].b;
   tile_unit_vectors<PLANAR>(a, w, ang);
 
-  // phase 2: sequence s = (component, chain) of the tile, one wavefront each
-  const int seg = (n + 63) / 64;
-  for (int s = wave; s < COMPS * tc; s += TILE_THREADS / 64) {
-    double *v = px + (int64_t)(s / tc) * a.tile_chains * ns + (s % tc) * ns;   // px, pz, py lie one behind the other
-    const int i0 = lane * seg, i1 = i0 + seg < n ? i0 + seg : n;
-    double mine = 0.0;
-    for (int i = i0; i < i1; ++i) mine += v[i];
-    const double before = __shfl_up(wave_scan(mine, lane), 1, 64);
-    double run = lane ? before : 0.0;                               // what lies before this lane's segment
-    for (int i = i0; i < i1; ++i) {
-      const double u = v[i];
-      run += u;
-      v[i] = b * (run - 0.5 * u);
-    }
-  }
-  __syncthreads();
+  tile_positions<PLANAR>(a, w, b);                                  // phase 2 (pstat_tile.h)
 
   // phase 3: centre and gyration tensor, a wavefront per chain; the chain's eight values go to gy[q][8]
   double *gy = lds;                                                 // TILE_CHAINS * 8 doubles of the scratch

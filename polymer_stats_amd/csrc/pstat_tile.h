@@ -1,8 +1,8 @@
-// pstat_tile.h -- the tile frame under the correlation and the shape recorder (pstat_corr.hip, pstat_shape.hip; TileArgs and
-// tile_layout are in pstat_device.h).  A workgroup (case, tile) of 256 threads takes `tile_chains` consecutive chains of one
-// case, leaves their unit vectors in LDS behind 4 KiB of scratch, and its `groups` groups of `lpc` threads fold their
-// (sum, sumsq) through that scratch; tile_fold then adds the tiles' partials per (case, column).  Every order below is part of
-// the recorders' results: tests/corr_ref.py and tests/shape_ref.py restate it.
+// pstat_tile.h -- the tile frame under the correlation, the shape and the pair-distance recorder (pstat_corr.hip,
+// pstat_shape.hip, pstat_pdist.hip; TileArgs and tile_layout are in pstat_device.h).  A workgroup (case, tile) of 256 threads
+// takes `tile_chains` consecutive chains of one case, leaves their unit vectors in LDS behind 4 KiB of scratch, and its `groups`
+// groups of `lpc` threads fold their (sum, sumsq) through that scratch; tile_fold then adds the tiles' partials per (case,
+// column).  Every order below is part of the recorders' results: tests/corr_ref.py and tests/shape_ref.py restate it.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -74,6 +74,42 @@ __device__ __forceinline__ void tile_unit_vectors(const TileArgs &a, const Tile 
       w.x[q * ns + i] = cp * st;
       w.y[q * ns + i] = sp * st;
       w.z[q * ns + i] = ct;
+    }
+  }
+  __syncthreads();
+}
+
+// inclusive scan over the 64 lanes: the shift-and-add tree whose order is part of every position
+__device__ __forceinline__ double wave_scan(double v, const int lane) {
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const double up = __shfl_up(v, off, 64);
+    if (lane >= off) v += up;
+  }
+  return v;
+}
+
+// Phase 2 of the recorders that read positions (pstat_shape.hip, pstat_pdist.hip): the prefix sum, in place, from the unit
+// vectors to x_i = b (sum_{j <= i} n_j - n_i / 2).  A wavefront takes one (chain, component) sequence at a time: lane l sums its
+// segment of ceil(n / 64) consecutive monomers in order, the lanes' sums go through wave_scan, and the lane rewrites its segment
+// as b (running sum - n_i / 2).  The tree depends on n alone.  Ends in a barrier.
+template <bool PLANAR>
+__device__ __forceinline__ void tile_positions(const TileArgs &a, const Tile &w, const double b) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n = (int)a.n, tc = w.tc, ns = w.ns;
+  constexpr int COMPS = PLANAR ? 2 : 3;
+  const int seg = (n + 63) / 64;
+  for (int s = wave; s < COMPS * tc; s += TILE_THREADS / 64) {      // sequence s = (component, chain) of the tile
+    double *v = w.x + (int64_t)(s / tc) * a.tile_chains * ns + (s % tc) * ns;   // x, z, y lie one behind the other
+    const int i0 = lane * seg, i1 = i0 + seg < n ? i0 + seg : n;
+    double mine = 0.0;
+    for (int i = i0; i < i1; ++i) mine += v[i];
+    const double before = __shfl_up(wave_scan(mine, lane), 1, 64);
+    double run = lane ? before : 0.0;                               // what lies before this lane's segment
+    for (int i = i0; i < i1; ++i) {
+      const double u = v[i];
+      run += u;
+      v[i] = b * (run - 0.5 * u);
     }
   }
   __syncthreads();

@@ -165,6 +165,26 @@ class Ensemble:
         """advance(nsteps) with a record into `shape` after every `stepout`-th step (asynchronous)."""
         check(self._L.pstat_advance_shape(self._h, shape._g, int(nsteps), int(stepout)))
 
+    # --- per-case pair distances of the monomers' positions (pstat_pdist_*; DESIGN.md 3.18)
+    def open_pdist(self, max_sep: int = -1, min_sep: int = 1, bins=None, q=None, capacity_rows: int = 0) -> "Pdist":
+        """`max_sep`: R2(s) for s = 1 .. max_sep (-1: n - 1; 0: none); `min_sep`: the closest approach and the histogram count
+        the pairs with j - i >= min_sep; `bins`: None, or (nbins, rmax) with rmax in absolute units, or (nbins, [rmax per case]);
+        `q`: the Debye magnitudes, array-like [nq] >= 0 in absolute units (None: none).  `capacity_rows` > 0 also keeps one row
+        of case means per record, for Pdist.error_bars."""
+        nbins, rmax = _pdist_bins(bins, self.ncases)
+        qa = _pdist_q(q)
+        spec = _lib.PdistSpec(int(max_sep), int(min_sep), nbins, len(qa), float(rmax[0]) if len(rmax) == 1 else 0.0)
+        dp = C.POINTER(C.c_double)
+        g = C.c_void_p()
+        check(self._L.pstat_pdist_open(self._h, C.byref(spec), qa.ctypes.data_as(dp) if len(qa) else None,
+                                       rmax.ctypes.data_as(dp) if len(rmax) > 1 else None, int(capacity_rows), C.byref(g)))
+        per_case = np.broadcast_to(rmax, (self.ncases,)).copy() if nbins else np.zeros(self.ncases)
+        return Pdist(self, g, self.n - 1 if int(max_sep) < 0 else int(max_sep), int(min_sep), nbins, per_case, qa)
+
+    def advance_pdist(self, pdist: "Pdist", nsteps: int, stepout: int):
+        """advance(nsteps) with a record into `pdist` after every `stepout`-th step (asynchronous)."""
+        check(self._L.pstat_advance_pdist(self._h, pdist._g, int(nsteps), int(stepout)))
+
     # --- read-outs
     def reduce_into(self, dev_ptr: int, icase: int = -1):
         """Device-side reduction into a caller-owned device buffer of NRED doubles (async)."""
@@ -403,7 +423,7 @@ class CorrResult:
 
 
 class _Totals(_Recorder):
-    """What Corr and Shape share: per-case totals of `ncols` columns and, with capacity_rows > 0 at the open, one row of case
+    """What Corr, Shape and Pdist share: per-case totals of `ncols` columns and, with capacity_rows > 0 at the open, one row of case
     means per record."""
 
     def __init__(self, ensemble: Ensemble, g, ncols: int):
@@ -427,7 +447,7 @@ class _Totals(_Recorder):
 
     def rows(self):
         """(device pointer, rows, stride) of the per-record case means, a float64 matrix [rows][ncases * ncols] in device
-        memory (pstat_corr_rows, pstat_shape_rows).  Synchronises."""
+        memory (pstat_corr_rows, pstat_shape_rows, pstat_pdist_rows).  Synchronises."""
         e = self._e
         ptr, nrows, stride = C.c_void_p(), C.c_int64(0), C.c_int64(0)
         check(self._fn("rows")(e._h, self._g, C.byref(ptr), C.byref(nrows), C.byref(stride)))
@@ -435,7 +455,7 @@ class _Totals(_Recorder):
 
     def error_bars(self, min_blocks: int = 32, levels: bool = False, device: int | None = None) -> "ErrorBars":
         """Blocked standard errors of the recorded rows' columns (pstat_blocking_device on rows()): arrays of shape
-        [ncases, ncols].  Needs capacity_rows > 0 at open_corr / open_shape and at least `min_blocks` records.  Synchronises."""
+        [ncases, ncols].  Needs capacity_rows > 0 at open_corr / open_shape / open_pdist and at least `min_blocks` records.  Synchronises."""
         e = self._e
         ptr, nrows, stride = self.rows()
         dev = int(e.cases[0].device) if device is None else int(device)
@@ -515,6 +535,85 @@ class Shape(_Totals):
     def read(self) -> ShapeResult:
         """Synchronises."""
         return ShapeResult(self.q, self._e.num_chains, self._e.planar, *self._read())
+
+
+def _pdist_bins(bins, ncases: int):
+    """(nbins, rmax as float64 [1] or [ncases]) from None | (nbins, rmax) | (nbins, [rmax per case])."""
+    if bins is None:
+        return 0, np.ones(1)
+    try:
+        nbins, rmax = bins
+        nbins = int(nbins)
+        rmax = np.atleast_1d(np.asarray(rmax, dtype=np.float64))
+    except (TypeError, ValueError):
+        raise ValueError("bins must be None, (nbins, rmax) or (nbins, [rmax per case])")
+    if rmax.ndim != 1 or len(rmax) not in (1, ncases):
+        raise ValueError(f"bins: rmax must be one number or one per case ({ncases}), not {rmax.shape}")
+    if nbins == 0:
+        return 0, np.ones(1)
+    return nbins, np.ascontiguousarray(rmax)
+
+
+def _pdist_q(q) -> np.ndarray:
+    """The Debye magnitudes as the library takes them: float64 [nq]."""
+    if q is None:
+        return np.zeros(0)
+    a = np.asarray(q, dtype=np.float64)
+    if a.size == 0:
+        return np.zeros(0)
+    if a.ndim != 1:
+        raise ValueError(f"q must be [nq] magnitudes, not {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+class PdistResult:
+    """What Pdist.read returns.  `sum`, `sumsq`: the raw totals, float64 [ncases, ncols], the columns msd (s = 1 .. max_sep),
+    rmin, the nbins + 1 histogram columns (none without bins) and one per magnitude of `q`; `records`; `mean`: sum / (records *
+    chains per case); `chain_stderr`: the across-chain standard error of that mean, defined after exactly one record and NaN
+    otherwise.  Views of `mean`: `msd` [ncases, max_sep], `rmin` [ncases], `sq` [ncases, nq]; of `sum`: `counts` [ncases, nbins]
+    and `above` [ncases], the pairs counted over all records and chains (exact integers kept as doubles).  `pairs`: how many pairs
+    of one chain the histogram and rmin look at, (n - min_sep)(n - min_sep + 1) / 2."""
+
+    def __init__(self, n: int, max_sep: int, min_sep: int, nbins: int, rmax: np.ndarray, q: np.ndarray, num_chains: int,
+                 sum_: np.ndarray, sumsq: np.ndarray, records: int):
+        self.n, self.max_sep, self.min_sep, self.nbins, self.rmax, self.q = n, max_sep, min_sep, nbins, rmax, q
+        self.num_chains, self.records, self.sum, self.sumsq = num_chains, records, sum_, sumsq
+        self.mean, self.chain_stderr = _mean_and_chain_stderr(sum_, sumsq, records, num_chains)
+        self.pairs = (n - min_sep) * (n - min_sep + 1) // 2
+        h0 = max_sep + 1
+        h1 = h0 + (nbins + 1 if nbins else 0)
+        self.msd, self.rmin, self.sq = self.mean[:, :max_sep], self.mean[:, max_sep], self.mean[:, h1:]
+        self.counts = sum_[:, h0:h0 + nbins]
+        self.above = sum_[:, h1 - 1] if nbins else np.zeros(len(sum_))
+
+    def edges(self, k: int = 0) -> np.ndarray:
+        """The nbins + 1 bin edges of case k: rmax (0 .. nbins) / nbins."""
+        return float(self.rmax[k]) * np.arange(self.nbins + 1) / max(self.nbins, 1)
+
+    def centers(self, k: int = 0) -> np.ndarray:
+        e = self.edges(k)
+        return 0.5 * (e[:-1] + e[1:])
+
+    def density(self, k: int = 0) -> np.ndarray:
+        """P(r) of case k: counts / (pairs counted * bin width), so it integrates to the share of pairs below rmax."""
+        counted = self.records * self.num_chains * self.pairs
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return self.counts[k] / (counted * (float(self.rmax[k]) / max(self.nbins, 1)))
+
+
+class Pdist(_Totals):
+    """Pair distances recorded on the device (Ensemble.open_pdist, pstat_pdist_*)."""
+
+    _kind = "pdist"
+
+    def __init__(self, ensemble: Ensemble, g, max_sep: int, min_sep: int, nbins: int, rmax: np.ndarray, q: np.ndarray):
+        super().__init__(ensemble, g, max_sep + 1 + (nbins + 1 if nbins else 0) + len(q))
+        self.max_sep, self.min_sep, self.nbins, self.rmax, self.q = max_sep, min_sep, nbins, rmax, q
+
+    def read(self) -> PdistResult:
+        """Synchronises."""
+        e = self._e
+        return PdistResult(e.n, self.max_sep, self.min_sep, self.nbins, self.rmax, self.q, e.num_chains, *self._read())
 
 
 def histogram_device(ptr: int, nrows: int, stride: int, specs, device: int = 0, stream: int | None = None):

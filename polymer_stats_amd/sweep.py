@@ -42,7 +42,7 @@ from . import mcmc_clustering_eap_chain as cluster_main
 from . import mcmc_clustering_eap_chain_2d as planar_main
 from . import mcmc_eap_chain as fixed_main
 from ._host import RECORDINGS, Recording, ReferenceError_, arith, check_recording, fresh_seed, number
-from ._host import parse_corr, parse_hist, parse_shape      # (reached through this module too)
+from ._host import parse_corr, parse_hist, parse_pdist, parse_shape      # (reached through this module too)
 
 # (the planar main: 2D/run/Ising_2024-11-06.jl and its siblings launch 2D/mcmc_clustering_eap_chain.jl the same way)
 MAINS = {"mcmc_eap_chain": fixed_main, "mcmc_clustering_eap_chain": cluster_main, "mcmc_clustering_eap_chain_2d": planar_main}
@@ -195,14 +195,14 @@ def plan(main_name: str, fixed_argv: list[str], cases: list[dict], workdir: str,
 
 
 def recording(main_name: str, fixed_argv: list[str], cases: list[dict], *, error_bars: int = 0, hist=None, corr=None, shape=None,
-              write_csv: bool = False, world: int = 1) -> Recording | None:
-    """--error-bars N | --hist SPEC ... | --corr SPEC | --shape [SPEC] of tools/run_sweep.py (the texts as the command line gives
-    them; shape "" is the bare flag, None its absence) -> the Recording of the production run, or None where none is asked for.
-    Parses the flag that is given and refuses what it cannot be combined with -- another of the four, more than one rank, and
+              pdist=None, write_csv: bool = False, world: int = 1) -> Recording | None:
+    """--error-bars N | --hist SPEC ... | --corr SPEC | --shape [SPEC] | --pdist SPEC of tools/run_sweep.py (the texts as the
+    command line gives them; shape "" is the bare flag, None its absence) -> the Recording of the production run, or None where none is asked for.
+    Parses the flag that is given and refuses what it cannot be combined with -- another of the five, more than one rank, and
     what _host.check_recording refuses, judged from the options every case shares and from every chain and monomer length
     among the cases; no GPU is touched."""
     given = [(kind, text) for kind, text in (("error_bars", error_bars or None), ("hist", hist or None), ("corr", corr or None),
-                                             ("shape", shape)) if text is not None]
+                                             ("shape", shape), ("pdist", pdist or None)) if text is not None]
     if not given:
         return None
     row = RECORDINGS[given[0][0]]
@@ -230,19 +230,19 @@ def _signature(pargs: dict):
 def run_sweep(main_name: str, fixed_argv: list[str], cases: list[dict], workdir: str, *, name=None, num_chains: int = 64,
               seed: int | None = None, precision: str | None = None, rng: str | None = None, rank: int = 0, world: int = 1,
               device: int = 0, overwrite: bool = False, write_csv: bool = False, max_chains: int = 262144, log=None,
-              error_bars: int = 0, hist=None, corr=None, shape=None) -> dict:
+              error_bars: int = 0, hist=None, corr=None, shape=None, pdist=None) -> dict:
     """Runs the cases whose `.out` does not exist yet (run/interacting_dielectric_study.jl:39) and that fall to this rank
     (position in the full case list modulo `world`).  `write_csv` also writes every case's two time-series files (rows
     recorded on the device for the whole ensemble, _Pool.recorded).  `error_bars` = N | `hist` = ["CHANNEL:LO:HI:NBINS", ...] | `corr` =
-    "MAXLAG[:nn,zz,mm]" | `shape` = "[AXIS:QMAX:NQ,...]" ("" for the gyration block alone; None: no shape), the command line's four
-    options and at most one of them (recording): the production run is recorded that way (_Pool.record: N batches | every chain
-    histogrammed | the lag correlations | the gyration tensor and the form factor at those wave-vectors, every --stepout steps)
-    and every `<case>.out` gets a `<case>.err` | `.hist` | `.corr` | `.shape` beside it (_host.error_lines: blocked standard
-    errors under the .out's names | hist_lines | corr_lines | shape_lines); the .out files are those of a run without it, and a
+    "MAXLAG[:nn,zz,mm]" | `shape` = "[AXIS:QMAX:NQ,...]" ("" for the gyration block alone; None: no shape) | `pdist` =
+    "RMAX:NBINS[,sep=..][,min=..][,q=QMAX:NQ]", the command line's five options and at most one of them (recording): the production run is recorded that way (_Pool.record: N batches | every chain
+    histogrammed | the lag correlations | the gyration tensor and the form factor at those wave-vectors | the pair distances, every --stepout steps)
+    and every `<case>.out` gets a `<case>.err` | `.hist` | `.corr` | `.shape` | `.pdist` beside it (_host.error_lines: blocked standard
+    errors under the .out's names | hist_lines | corr_lines | shape_lines | pdist_lines); the .out files are those of a run without it, and a
     case whose file beside the .out is missing is run again.  Returns {"ran": [...], "skipped": [...], "launches": k}."""
     main = MAINS[main_name]
-    rec = recording(main_name, fixed_argv, cases, error_bars=error_bars, hist=hist, corr=corr, shape=shape, write_csv=write_csv,
-                    world=world)
+    rec = recording(main_name, fixed_argv, cases, error_bars=error_bars, hist=hist, corr=corr, shape=shape, pdist=pdist,
+                    write_csv=write_csv, world=world)
     os.makedirs(workdir, exist_ok=True)
     todo_all = plan(main_name, fixed_argv, cases, workdir, name=name, num_chains=num_chains, seed=seed, precision=precision,
                     rng=rng, device=device)

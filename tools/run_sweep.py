@@ -82,6 +82,14 @@ def main():
                          "the blocked standard errors of the records (at least 32 records).  A bare --shape records the gyration "
                          "block only.  Refused where --corr is, and with it; the .out files stay byte for byte a plain run's, at the "
                          "same doubled production time")
+    ap.add_argument("--pdist", default="", metavar="RMAX:NBINS[,sep=MAXSEP][,min=MINSEP][,q=QMAX:NQ]",
+                    help="record the distances between two monomers of EVERY chain every --stepout steps of the production run, on "
+                         "the device: the mean-square internal distance R2(s) for s = 1 .. MAXSEP (default n - 1), the closest "
+                         "approach and the distribution P(r) below RMAX in NBINS bins over the pairs at least MINSEP apart along the "
+                         "chain (default 1; NBINS 0: no histogram), and the Debye S(q) at NQ magnitudes QMAX (1 .. NQ) / NQ; write "
+                         "next to every <case>.out a <case>.pdist: CSV name,x,value,stderr with the blocked standard errors of the "
+                         "records (at least 32 records).  Refused where --shape is, and with it; the .out files stay byte for byte "
+                         "a plain run's, at the same doubled production time")
     ap.add_argument("--max-chains", type=int, default=262144, help="chains per launch (cases per ensemble = this / num-chains)")
     ap.add_argument("--dry-run", action="store_true", help="print the plan (cases, file names, ensembles) and stop: no GPU needed")
     ap.add_argument("--aggregate", default="", help="afterwards write scripts/aggregate_mcmc.jl's CSV of the whole directory here")
@@ -101,7 +109,7 @@ def main():
     if not cases:
         raise SystemExit("no cases: give --axis and/or --cases")
 
-    recording = dict(error_bars=args.error_bars, hist=args.hist, corr=args.corr, shape=args.shape)
+    recording = dict(error_bars=args.error_bars, hist=args.hist, corr=args.corr, shape=args.shape, pdist=args.pdist)
     try:
         sw.recording(args.main, fixed, cases, write_csv=args.csv, world=args.gpus, **recording)
     except sw.ReferenceError_ as e:
