@@ -1,8 +1,9 @@
 """GPU tests of the per-case histograms (pstat_hist_*, pstat_histogram_device, pstat_hist.hip) against the numpy
 twin of the binning formula (tests/hist_ref.py): counts equal AS INTEGERS to the twin on the microstates of an identical second
-ensemble, on every mapping of the kernel and on four homes; crafted edge values through a torch tensor; a closed-form density;
-recording between exchange rounds; refusals and lifetime; tools/run_sweep.py --hist and tools/free_energy.py end to end."""
-import ctypes as C
+ensemble, on every mapping of the kernel and on five homes; crafted edge values through a torch tensor; a closed-form density;
+recording between exchange rounds; refusals; tools/run_sweep.py --hist and tools/free_energy.py end to end.  The protocol of the
+comparison (run_hist_twin), the homes and the tool call are those of tests/recorder_cases.py; the lifecycle rules are asserted
+in tests/test_gpu_recorder_lifecycle.py."""
 import json
 import os
 import subprocess
@@ -12,91 +13,14 @@ import numpy as np
 import pytest
 
 import hist_ref as hr
+import recorder_cases as rc
+from recorder_cases import ps  # noqa: F401 (the fixture)
+from recorder_cases import run_hist_twin as run_exact
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def ps():
-    import polymer_stats_amd as ps
-    assert ps._lib.load().pstat_device_count() >= 1, "no HIP device visible"
-    return ps
-
-
-def bits(x):
-    return np.ascontiguousarray(x).tobytes()
-
-
-def micro_of_all(e):
-    return np.array([e.microstate(c) for c in range(e.ncases * e.num_chains)]).reshape(e.ncases, e.num_chains, 7)
-
-
-def twin_counts(micro_records, rows, ncases):
-    """What the twin makes of micro_records[record][case, chain, 7] under rows[case or 0][spec]: (counts per spec
-    [ncases, nbins], tails [ncases, nspecs, 3])."""
-    nspecs = len(rows[0])
-    counts = [np.zeros((ncases, rows[0][i].nbins), dtype=np.int64) for i in range(nspecs)]
-    tails = np.zeros((ncases, nspecs, 3), dtype=np.int64)
-    for k in range(ncases):
-        for i in range(nspecs):
-            sp = rows[k if len(rows) > 1 else 0][i]
-            x = np.concatenate([hr.channel_values(m[k], sp.channel) for m in micro_records])
-            counts[i][k], tails[k, i] = hr.bin_counts(x, sp.lo, sp.hi, sp.nbins)
-    return counts, tails
-
-
-def assert_same_chains(a, b, chains):
-    for c in chains:
-        ga, gb = a.chain_state(c), b.chain_state(c)
-        for k in ga:
-            assert bits(ga[k]) == bits(gb[k]) if isinstance(ga[k], np.ndarray) else ga[k] == gb[k], (c, k)
-        assert bits(a.microstate(c)) == bits(b.microstate(c)), c
-
-
-def run_exact(ps, cases, rows, per_case=False, planar=False, stepout=40, records=6):
-    """A records with advance_hist, B advances `stepout` at a time and reads every chain's microstate: the twin's counts on B's
-    values equal A's as integers on the component channels; on the magnitude channels they may differ only where a value is
-    within 2 ulp of an edge.  Returns A's result."""
-    with ps.Ensemble(cases, planar=planar) as A, ps.Ensemble(cases, planar=planar) as B:
-        h = A.open_hist(rows if per_case else rows[0], per_case=per_case)
-        A.advance_hist(h, records * stepout + 7, stepout)           # the remainder is advanced and not recorded
-        micro = []
-        for _ in range(records):
-            B.advance(stepout)
-            micro.append(micro_of_all(B))
-        B.advance(7)
-        got = h.read()
-        ncases, per = A.ncases, A.num_chains
-        assert got.records == records and got.samples == records * per
-        want, want_tails = twin_counts(micro, rows, ncases)
-        for i, sp in enumerate(rows[0]):
-            total = got.counts[i].sum(axis=1) + got.tails[:, i].sum(axis=1)
-            assert np.array_equal(total, np.full(ncases, records * per)), (i, total)
-            if sp.channel < 7:
-                assert got.counts[i].dtype == np.int64 and np.array_equal(got.counts[i], want[i]), f"spec {i}: counts differ"
-                assert np.array_equal(got.tails[:, i], want_tails[:, i]), f"spec {i}: tails differ"
-            else:       # the one place where the device's sqrt may differ from numpy's
-                near = 0
-                for k in range(ncases):
-                    s = rows[k if per_case else 0][i]
-                    x = np.concatenate([hr.channel_values(m[k], s.channel) for m in micro])
-                    near += int(hr.near_edge(x, s.lo, s.hi, s.nbins).sum())
-                diff = int(np.abs(got.counts[i] - want[i]).sum() + np.abs(got.tails[:, i] - want_tails[:, i]).sum())
-                print(f"magnitude channel {sp.channel}: |E| = {near} of {records * per * ncases} samples, sum |device - twin| = {diff}")
-                assert diff <= 2 * near and near <= 0.01 * records * per * ncases
-        C_ = ncases * per
-        # recording disturbed nothing: every chain where that is quick, else the lanes and chains at which the mapping changes
-        # (a wave's last lane and the next one, either side of a workgroup's 1 024 samples, a case's first and last chain)
-        edges = {c for k in range(ncases) for j in (0, 1, 63, 64, 65, 255, 256, 1023, 1024, 1025, per - 1) if j < per for c in [k * per + j]}
-        assert_same_chains(A, B, range(C_) if C_ <= 1000 else sorted(edges))
-        h.close()
-        return got
-
-
-BASE = dict(E0=1.0, K1=0.5, Fz=0.5, steps_per_adjust=150)
-CLUSTER = dict(move_set=1, cluster_prob=0.5, bend_mod=0.3, bend_angle=0.2)
+BASE = dict(E0=1.0, K1=0.5, Fz=0.5, steps_per_adjust=150)             # (no K2, unlike the other recorders' rc.BASE)
 
 
 def component_specs(ps, n, with_magnitudes=True):
@@ -143,25 +67,10 @@ def test_a_handle_with_exactly_the_most_bins(ps, ncases, per):
 
 
 # ------------------------------------------------------------------------------------------------ the homes
-# name: (parameters, precision, planar, the kernel's name has)
-HOMES = {
-    "f64 sweep": (dict(n=12), 1, False, "sweep_kernel<double>"),
-    "fixed-force all-pairs": (dict(n=16, energy_type=1), 1, False, "interacting_kernel"),
-    "clustering main": (dict(n=12, **CLUSTER), 1, False, "cluster"),
-    "planar": (dict(n=14, cluster_prob=0.5), 1, True, "planar_kernel"),
-    "f32 sweep": (dict(n=12), 0, False, "sweep_kernel<float>"),
-}
-
-
-@pytest.mark.parametrize("home", list(HOMES))
+@pytest.mark.parametrize("home", list(rc.HOMES)[:5])                 # the first five, all at 70 chains per case; with BASE above
 def test_every_home_and_a_per_case_range(ps, home):
-    kw, precision, planar, has = HOMES[home]
-    make = ps.default_planar_params if planar else ps.default_params
-    E0 = [0.5, 1.0, 1.5]
-    cases = [make(num_chains=70, precision=precision, kT=0.8 + 0.3 * k, seed=700 + k, **{**BASE, **kw, "E0": E0[k]}) for k in range(3)]
-    n = kw["n"]
-    with ps.Ensemble(cases, planar=planar) as e:
-        assert has in e.launch_info().kernel.decode(), e.launch_info().kernel.decode()
+    cases, planar = rc.home_cases(ps, home, seed=700, base=BASE)
+    n, E0 = int(cases[0].n), [c.E0 for c in cases]
     # U's range follows E0: only lo and hi differ between the cases
     rows = [component_specs(ps, n)[:6] + [ps.hist_spec("U", 64, -(0.4 + x * x) * n, 0.3 * n)] + component_specs(ps, n)[7:] for x in E0]
     got = run_exact(ps, cases, rows, per_case=True, planar=planar)
@@ -212,31 +121,18 @@ def test_closed_form_density_of_the_extension(ps):
 
 # ------------------------------------------------------------------------------------------------ with tempering
 def test_records_between_exchange_rounds(ps):
-    kTs = [0.25, 0.35, 0.5, 0.75, 1.2, 2.0, 4.0]                     # the ladder of the README's example
-    cases = [ps.default_params(n=8, E0=3.0, Fz=0.2, kT=kT, num_chains=64, seed=i) for i, kT in enumerate(kTs)]
+    cases = rc.ladder_cases(ps)
     rows = [[ps.hist_spec("r3", 32, -8.0, 8.0), ps.hist_spec("U", 64, -40.0, 0.0)]]
-    micro = []
-    with ps.Ensemble(cases) as A, ps.Ensemble(cases) as B:
-        ta, tb = (e.open_tempering(ps.ladders_by(cases), seed=9) for e in (A, B))
-        h = A.open_hist(rows[0])
-        for _ in range(5):
-            A.advance_tempered(ta, 200, 50)
-            h.record()
-            B.advance_tempered(tb, 200, 50)
-            micro.append(micro_of_all(B))
-        got = h.read()
-        att, acc, rounds = ta.stats()
-        assert rounds == 20 and acc.sum() > 0, "no exchange was accepted: the records would not show a swapped configuration"
-    want, want_tails = twin_counts(micro, rows, 7)
+    got, micro = rc.records_between_exchange_rounds(ps, cases, lambda e: e.open_hist(rows[0]), rc.micro_of_all)
+    want, want_tails = rc.twin_counts(micro, rows, 7)
     for i in range(2):
         assert np.array_equal(got.counts[i], want[i]) and np.array_equal(got.tails[:, i], want_tails[:, i])
         assert np.array_equal(got.counts[i].sum(axis=1) + got.tails[:, i].sum(axis=1), np.full(7, 5 * 64))
-    assert got.records == 5 and got.samples == 5 * 64
+    assert got.samples == 5 * 64
 
 
-# ------------------------------------------------------------------------------------------------ refusals and lifetime
+# ------------------------------------------------------------------------------------------------ refusals
 def test_refusals_leave_the_handle_usable(ps):
-    lib = ps._lib.load()
     spec = [ps.hist_spec("r3", 8, -6.0, 6.0)]
     with ps.Ensemble([ps.default_params(n=6, num_chains=4, kT=kT, umbrella=1) for kT in (1.0, 2.0)]) as e:
         with pytest.raises(ps.PstatError) as err:
@@ -258,13 +154,6 @@ def test_refusals_leave_the_handle_usable(ps):
         with pytest.raises(ValueError):
             e.open_hist([spec, spec], per_case=True)
         h = e.open_hist(spec)
-        with ps.Ensemble(cases[:2]) as other:                        # a histogram of another handle
-            assert lib.pstat_hist_record(other._h, h._g) == -1 and b"not an open histogram" in lib.pstat_last_error()
-            assert lib.pstat_advance_hist(other._h, h._g, 10, 5) == -1
-            assert lib.pstat_hist_read(other._h, h._g, None, None, None) == -1
-            assert lib.pstat_hist_clear(other._h, h._g) == -1
-            lib.pstat_hist_close(other._h, h._g)                     # ignored: it is not the other handle's to close
-        assert lib.pstat_advance_hist(e._h, h._g, 10, 0) == -1 and lib.pstat_advance_hist(e._h, h._g, -1, 5) == -1
         e.advance_hist(h, 25, 10)
         got = h.read()
         assert got.records == 2 and e.chain_state(0)["steps_recorded"] == 25
@@ -274,42 +163,19 @@ def test_refusals_leave_the_handle_usable(ps):
         assert got.records == 0 and got.counts[0].sum() == 0 and got.tails.sum() == 0
         h.record()
         assert h.read().counts[0].sum() + h.read().tails.sum() == 12
-        records = C.c_int64(-1)                                      # every output may be NULL
-        assert lib.pstat_hist_read(e._h, h._g, None, None, C.byref(records)) == 0 and records.value == 1
-        g = h._g
-        h.close()
-        assert lib.pstat_hist_read(e._h, g, None, None, None) == -1  # read after close
-        assert lib.pstat_hist_record(e._h, g) == -1
-        e.advance(5)
+        e.advance(5)                                                 # the handle still advances
         assert e.chain_state(0)["steps_recorded"] == 30
-        e.open_hist(spec).record()                                   # destroyed with a histogram open
-    with ps.Ensemble(cases) as e:
-        e.advance(3)
-        assert e.chain_state(0)["steps_recorded"] == 3
 
 
 # ------------------------------------------------------------------------------------------------ the tools
-def _sweep(tmp_path, name, *extra):
-    out = tmp_path / name
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "run_sweep.py"), str(out), "--axis", "n=8", "--axis", "Fz=0,0.5,1,1.5,2,2.5",
-                        "--num-chains", "64", "--seed", "11", *extra, "--", "--num-steps", "3000", "--stepout", "100", "-v", "0"],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return out
-
-
 def test_sweep_writes_hist_files_and_free_energy_reads_them(tmp_path):
-    with_hist = _sweep(tmp_path, "h", "--hist", "r3:-8:8:32", "--hist", "U:-10:2:16")
-    plain = _sweep(tmp_path, "p")
-    outs = sorted(f for f in os.listdir(plain) if f.endswith(".out"))
-    assert len(outs) == 6 and sorted(f for f in os.listdir(with_hist) if f.endswith(".out")) == outs
-    for f in outs:                                                   # the .out files are a plain run's, byte for byte
-        assert (with_hist / f).read_bytes() == (plain / f).read_bytes(), f
-    assert not [f for f in os.listdir(plain) if f.endswith(".hist")]
+    axes, fixed = [("n", "8"), ("Fz", "0,0.5,1,1.5,2,2.5")], ["--num-steps", "3000", "--stepout", "100", "-v", "0"]
+    with_hist = rc.sweep_tool(tmp_path, "h", "--hist", "r3:-8:8:32", "--hist", "U:-10:2:16", axes=axes, fixed=fixed)
+    plain = rc.sweep_tool(tmp_path, "p", axes=axes, fixed=fixed)
+    outs, hists = rc.assert_out_files_unchanged(with_hist, plain, ".hist")
+    assert len(outs) == 6
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import free_energy as fe
-    hists = sorted(f for f in os.listdir(with_hist) if f.endswith(".hist"))
-    assert hists == [f[:-len(".out")] + ".hist" for f in outs]
     for f in hists:
         r3, U = fe.read_hist(str(with_hist / f))
         assert (r3["channel"], r3["nbins"], r3["records"], r3["chains"], r3["lo"], r3["hi"]) == ("r3", 32, 30, 64, -8.0, 8.0)

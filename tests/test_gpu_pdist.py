@@ -1,63 +1,23 @@
 """GPU tests of the pair-distance recorder (pstat_pdist_*, pstat_pdist.hip) against the numpy twin of the
 contract (tests/pdist_ref.py): totals and rows equal to the twin's on the angles of an identical second ensemble, to the bound
 derived in the twin's docstring, the histogram's counts as integers; every edge of the kernel's mapping; the homes; a straight
-chain that sits on the bin edges; closed forms; the shape recorder's S(q) beside the Debye one; error bars, tempering, refusals,
-the lifecycle rules of DESIGN.md 3.17; tools/run_sweep.py --pdist end to end."""
-import ctypes as C
+chain that sits on the bin edges; closed forms; the shape recorder's S(q) beside the Debye one; error bars, tempering, refusals;
+tools/run_sweep.py --pdist end to end.  The protocol of the comparison, the case tables and the tool call are those of
+tests/recorder_cases.py, given pdist_kind below; the lifecycle rules are asserted in tests/test_gpu_recorder_lifecycle.py."""
 import json
 import os
 import struct
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import pdist_ref as pr
+import recorder_cases as rc
+from recorder_cases import AXES, BASE, FIXED, angles_of_all, assert_same_chains, bits, ps, sweep_cases  # noqa: F401 (ps is the fixture)
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def ps():
-    import polymer_stats_amd as ps
-    assert ps._lib.load().pstat_device_count() >= 1, "no HIP device visible"
-    return ps
-
-
-def bits(x):
-    return np.ascontiguousarray(x).tobytes()
-
-
-def angles_of_all(e):
-    return np.array([np.concatenate([s["theta"], s["phi"]]) for s in (e.chain_state(c) for c in range(e.ncases * e.num_chains))])
-
-
-def hip_runtime():
-    """The HIP runtime libpstat has loaded into this process (the rows of pstat_pdist_rows are device memory)."""
-    with open("/proc/self/maps") as f:
-        path = next(line.split()[-1] for line in f if "libamdhip64" in line)
-    hip = C.CDLL(path)
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    return hip
-
-
-def rows_of(g):
-    ptr, nrows, stride = g.rows()
-    rows = np.zeros((nrows, stride))
-    if nrows:
-        assert ptr and hip_runtime().hipMemcpy(rows.ctypes.data, ptr, rows.nbytes, 2) == 0      # 2: device to host
-    return rows
-
-
-def assert_same_chains(a, b, chains):
-    for c in chains:
-        ga, gb = a.chain_state(c), b.chain_state(c)
-        for k in ga:
-            assert bits(ga[k]) == bits(gb[k]) if isinstance(ga[k], np.ndarray) else ga[k] == gb[k], (c, k)
-        assert bits(a.microstate(c)) == bits(b.microstate(c)), c
 
 
 def magnitudes(nq, qmax, seed=1):
@@ -68,100 +28,59 @@ def magnitudes(nq, qmax, seed=1):
     return q
 
 
-def compare(n, per, cases, o, rmax, q, planar, values, got, rows):
-    """`values`: [record][case] -> (per-chain columns, undecided, rfloor) of the twin; `got`: the PdistResult; `rows`: [records,
-    ncases, ncols] or None.  Returns the largest |device - twin| / bound."""
-    records, ncases = len(values), len(cases)
-    max_sep = n - 1 if o["max_sep"] < 0 else o["max_sep"]
-    nbins, nq = o["nbins"], len(q)
-    msd, rmin, hist, sq = pr.columns(max_sep, nbins, nq)
-    smooth = np.r_[np.arange(msd.start, rmin.stop), np.arange(sq.start, sq.stop)].astype(int)
-    worst, M = 0.0, per * records
-    pairs = pr.pairs_counted(n, o["min_sep"])
-    for k in range(ncases):
-        assert sum(v[k][1].sum() for v in values) == 0, "the input has a pair on a bin edge: the condition of pdist_ref fails"
-        rfloor = min(v[k][2] for v in values)
-        want_s = sum(v[k][0].sum(axis=0) for v in values)
-        want_q = sum((v[k][0] * v[k][0]).sum(axis=0) for v in values)
-        b1, b2 = pr.bounds(n, cases[k].b, M, max_sep, nbins, q, rfloor)
-        r1 = pr.bounds(n, cases[k].b, per, max_sep, nbins, q, rfloor)[0] / per
-        e1, e2 = np.abs(got.sum[k] - want_s), np.abs(got.sumsq[k] - want_q)
-        worst = max(worst, float((e1[smooth] / b1[smooth]).max()), float((e2[smooth] / b2[smooth]).max()))
-        assert np.all(e1 <= b1), (k, e1, b1, int((e1 - b1).argmax()))
-        assert np.all(e2 <= b2), (k, e2, b2, int((e2 - b2).argmax()))
-        if nbins:                                                    # integers: equal, and every counted pair is in one column
-            assert bits(got.sum[k, hist]) == bits(want_s[hist]) and bits(got.sumsq[k, hist]) == bits(want_q[hist]), k
-            assert got.sum[k, hist].sum() == M * pairs and got.counts[k].sum() + got.above[k] == M * pairs
-        for j in np.flatnonzero(np.asarray(q) == 0.0):               # S(0) = n for every chain: n M and n^2 M, exactly
-            assert got.sum[k, sq.start + j] == float(n * M) and got.sumsq[k, sq.start + j] == float(n * n * M), (k, j)
-        for r in range(records if rows is not None else 0):
-            want_r = values[r][k][0].sum(axis=0) / per
-            er = np.abs(rows[r, k] - want_r)
-            worst = max(worst, float((er[smooth] / r1[smooth]).max()))
-            assert np.all(er <= r1), (k, r, er, r1)
-    return worst
-
-
-def run_exact(ps, cases, max_sep=-1, min_sep=1, nbins=24, rmax=None, q=None, planar=False, stepout=40, records=3):
-    """A records with advance_pdist (rows kept), B advances `stepout` at a time and reads every chain's angles: the twin on B's
-    angles gives A's sum, sumsq and rows within the derived bound (pdist_ref's docstring) and the histogram's integers exactly; a
-    second A gives the same bits; A's chains end as B's.  `rmax`: None (1.5 sqrt(n) b of case 0), a number, or one per case."""
+def pdist_kind(cases, max_sep=-1, min_sep=1, nbins=24, rmax=None, q=None, planar=False):
+    """The descriptor of rc.run_totals_twin.  `rmax`: None (1.5 sqrt(n) b of case 0), a number, or one per case.  The twin also
+    tells how many pairs it could not decide the bin of, and the smallest distance in the data, which the bounds depend on.  A row
+    is a mean of `per` values: the bound of a total of `per`, over `per`."""
     n, per, ncases = int(cases[0].n), int(cases[0].num_chains), len(cases)
     q = np.zeros(0) if q is None else np.asarray(q, dtype=np.float64)
     if rmax is None:
         rmax = 1.5 * np.sqrt(n) * cases[0].b
     rmaxes = np.broadcast_to(np.asarray(rmax, dtype=np.float64), (ncases,))
-    bins = (nbins, rmax) if nbins else None
-    o = dict(max_sep=max_sep, min_sep=min_sep, nbins=nbins)
-    with ps.Ensemble(cases, planar=planar) as A, ps.Ensemble(cases, planar=planar) as B, ps.Ensemble(cases, planar=planar) as A2:
-        g = A.open_pdist(max_sep, min_sep, bins, q, capacity_rows=records)
-        A.advance_pdist(g, records * stepout + 7, stepout)           # the remainder is advanced and not recorded
-        g2 = A2.open_pdist(max_sep, min_sep, bins, q, capacity_rows=records)
-        A2.advance_pdist(g2, records * stepout + 7, stepout)
-        values = []
-        for _ in range(records):
-            B.advance(stepout)
-            ang = angles_of_all(B).reshape(ncases, per, 2 * n)
-            values.append([pr.per_chain(ang[k], cases[k].b, max_sep, min_sep, nbins, rmaxes[k], q, planar) for k in range(ncases)])
-        B.advance(7)
-        got, again = g.read(), g2.read()
-        cols = pr.ncols(n - 1 if max_sep < 0 else max_sep, nbins, len(q))
-        assert got.records == records and got.sum.shape == (ncases, cols) == (ncases, g.ncols)
-        assert bits(got.sum) == bits(again.sum) and bits(got.sumsq) == bits(again.sumsq), "two identical runs differ"
-        rows, rows2 = rows_of(g), rows_of(g2)
-        assert rows.shape == (records, ncases * cols) and bits(rows) == bits(rows2), "two identical runs differ in their rows"
-        worst = compare(n, per, cases, o, rmaxes, q, planar, values, got, rows.reshape(records, ncases, cols))
-        print(f"n = {n}, {ncases} x {per} chains, max_sep {max_sep}, min_sep {min_sep}, nbins {nbins}, nq {len(q)}: largest "
-              f"|device - twin| / bound = {worst:.4f}")
-        C_ = ncases * per
-        edges = {c for k in range(ncases) for j in (0, 1, 15, 16, 17, 63, 64, 65, 1023, 1024, per - 1) if j < per for c in [k * per + j]}
-        assert_same_chains(A, B, range(C_) if C_ <= 700 else sorted(edges))
-        g.close()
-        return got, worst
+    sep = n - 1 if max_sep < 0 else max_sep
+    _, _, hist, sq = pr.columns(sep, nbins, len(q))
+    pairs = pr.pairs_counted(n, min_sep)
+
+    def bounds(k, M, twins):
+        return pr.bounds(n, cases[k].b, M, sep, nbins, q, min(t[2] for t in twins))
+
+    def exact(got, rows, values, per):
+        M = per * len(values)
+        for k in range(ncases):
+            assert sum(v[k][1].sum() for v in values) == 0, "the input has a pair on a bin edge: the condition of pdist_ref fails"
+            if nbins:                                                # integers: equal, and every counted pair is in one column
+                want_s = sum(v[k][0].sum(axis=0) for v in values)
+                want_q = sum((v[k][0] * v[k][0]).sum(axis=0) for v in values)
+                assert bits(got.sum[k, hist]) == bits(want_s[hist]) and bits(got.sumsq[k, hist]) == bits(want_q[hist]), k
+                assert got.sum[k, hist].sum() == M * pairs and got.counts[k].sum() + got.above[k] == M * pairs
+            for j in np.flatnonzero(q == 0.0):                       # S(0) = n for every chain: n M and n^2 M, exactly
+                assert got.sum[k, sq.start + j] == float(n * M) and got.sumsq[k, sq.start + j] == float(n * n * M), (k, j)
+
+    return rc.Totals(
+        name="pdist", ncols=pr.ncols(sep, nbins, len(q)),
+        open=lambda e, capacity: e.open_pdist(max_sep, min_sep, (nbins, rmax) if nbins else None, q, capacity_rows=capacity),
+        twin=lambda ang, k: pr.per_chain(ang, cases[k].b, max_sep, min_sep, nbins, rmaxes[k], q, planar),
+        bounds=bounds, row_bound=lambda k, per, M, twins: bounds(k, per, twins)[0] / per, exact=exact,
+        line=f"n = {n}, {ncases} x {per} chains, max_sep {max_sep}, min_sep {min_sep}, nbins {nbins}, nq {len(q)}: largest "
+             f"|device - twin| / bound = {{worst:.4f}}")
 
 
-BASE = dict(E0=1.0, K1=0.5, K2=0.2, Fz=0.5, steps_per_adjust=150)
-CLUSTER = dict(move_set=1, cluster_prob=0.5, bend_mod=0.3, bend_angle=0.2)
-
-
-def sweep_cases(ps, ncases, per, n, seed=1800, **kw):
-    return [ps.default_params(n=n, num_chains=per, precision=ps.F64, kT=0.7 + 0.2 * k, seed=seed + k, **{**BASE, **kw}) for k in range(ncases)]
+def run_exact(ps, cases, planar=False, records=3, **options):
+    return rc.run_totals_twin(ps, cases, pdist_kind(cases, planar=planar, **options), planar=planar, records=records)
 
 
 # ------------------------------------------------------------------------------------------------ every edge of the mapping
-# chains per case: 1, 5 (one tile, not full), 64 (four full tiles of 16), 65 (a last tile of one chain), 1100 (69 tiles: more
-# than the 64 lanes of the fold); 9 cases: the fold's last workgroup is not full
-@pytest.mark.parametrize("ncases,per", [(1, 1), (3, 5), (9, 64), (9, 65), (2, 1100)])
+@pytest.mark.parametrize("ncases,per", rc.TILE_SHAPES)
 def test_totals_and_rows_equal_the_twin(ps, ncases, per):
     big = per == 1100                                                # (fewer bins and q: 2200 chains through the twin)
-    run_exact(ps, sweep_cases(ps, ncases, per, 12), nbins=8 if big else 24, q=magnitudes(2 if big else 5, 6.0), records=2 if big else 3)
+    run_exact(ps, sweep_cases(ps, ncases, per, 12, seed=1800), nbins=8 if big else 24, q=magnitudes(2 if big else 5, 6.0), records=2 if big else 3)
 
 
 # two monomers (one pair, rows for one wavefront only); three; 63, 64, 65: the first row's pairs end one short of the 64 lanes,
 # fill all but one, fill them exactly; 130: rows of three lane strides, scan segments of 3
 @pytest.mark.parametrize("n", [2, 3, 63, 64, 65, 130])
 def test_chain_lengths(ps, n):
-    got, _ = run_exact(ps, sweep_cases(ps, 3, 5, n, seed=1820), q=magnitudes(5, 6.0, seed=n), records=2)
+    got = run_exact(ps, sweep_cases(ps, 3, 5, n, seed=1820), q=magnitudes(5, 6.0, seed=n), records=2)
     if n == 2:
         np.testing.assert_allclose(got.msd[:, 0], got.sumsq[:, 1] / (2 * 5), rtol=1e-14)    # one pair: R2(1) = rmin^2
 
@@ -169,7 +88,7 @@ def test_chain_lengths(ps, n):
 @pytest.mark.parametrize("min_sep", [1, 2, 11])
 @pytest.mark.parametrize("max_sep", [0, 1, 11])
 def test_separations_at_n_12(ps, max_sep, min_sep):
-    got, _ = run_exact(ps, sweep_cases(ps, 3, 5, 12, seed=1830), max_sep=max_sep, min_sep=min_sep, q=magnitudes(3, 6.0), records=2)
+    got = run_exact(ps, sweep_cases(ps, 3, 5, 12, seed=1830), max_sep=max_sep, min_sep=min_sep, q=magnitudes(3, 6.0), records=2)
     assert got.msd.shape == (3, max_sep) and got.pairs == (12 - min_sep) * (13 - min_sep) // 2
 
 
@@ -183,7 +102,7 @@ def test_bin_and_magnitude_counts_at_n_65(ps, nbins, nq):
 def test_cases_that_differ_in_b_with_their_own_rmax(ps):
     bs = (0.5, 1.0, 2.5)
     cases = [ps.default_params(n=12, num_chains=20, precision=ps.F64, kT=1.0, seed=1870 + k, b=b, **BASE) for k, b in enumerate(bs)]
-    got, _ = run_exact(ps, cases, rmax=[4.0 * b for b in bs], q=magnitudes(5, 6.0 / 2.5))
+    got = run_exact(ps, cases, rmax=[4.0 * b for b in bs], q=magnitudes(5, 6.0 / 2.5))
     assert got.rmin[0] < got.rmin[1] < got.rmin[2] and got.msd[2, 4] > 20 * got.msd[0, 4]     # lengths scale with b
     assert np.all(got.rmax == [2.0, 4.0, 10.0])
     share = got.counts / (got.counts.sum(axis=1, keepdims=True) + got.above[:, None])
@@ -192,29 +111,10 @@ def test_cases_that_differ_in_b_with_their_own_rmax(ps):
 
 
 # ------------------------------------------------------------------------------------------------ the homes
-# name: (parameters, precision, planar, chains per case, the kernel's name has), as tests/test_gpu_shape.py lists them
-HOMES = {
-    "f64 sweep": (dict(n=12), 1, False, 70, "sweep_kernel<double>"),
-    "fixed-force all-pairs": (dict(n=16, energy_type=1), 1, False, 70, "interacting_kernel"),
-    "clustering main": (dict(n=12, **CLUSTER), 1, False, 70, "cluster"),
-    "planar": (dict(n=14, cluster_prob=0.5), 1, True, 70, "planar_kernel"),
-    "f32 sweep": (dict(n=12), 0, False, 70, "sweep_kernel<float>"),
-    "q16 sweep": (dict(n=12), 2, False, 70, "q16 state"),
-    "f64 sweep in memory": (dict(n=65), 1, False, 70, "state in L2"),
-    "clustering main, chain per wavefront": (dict(n=12, **CLUSTER), 1, False, 16, "cluster_chain_wave_kernel"),
-    "polar": (dict(n=12, chain_type=1, mu=1.5), 1, False, 20, "sweep_kernel<double>"),
-}
-
-
-@pytest.mark.parametrize("home", list(HOMES))
+@pytest.mark.parametrize("home", list(rc.HOMES))
 def test_every_home(ps, home):
-    kw, precision, planar, per, has = HOMES[home]
-    make = ps.default_planar_params if planar else ps.default_params
-    E0 = [0.5, 1.0, 1.5]
-    cases = [make(num_chains=per, precision=precision, kT=0.8 + 0.3 * k, seed=1900 + k, **{**BASE, **kw, "E0": E0[k]}) for k in range(3)]
-    with ps.Ensemble(cases, planar=planar) as e:
-        assert has in e.launch_info().kernel.decode(), e.launch_info().kernel.decode()
-    got, _ = run_exact(ps, cases, q=magnitudes(5, 6.0, seed=3), planar=planar, records=2)
+    cases, planar = rc.home_cases(ps, home, seed=1900)
+    got = run_exact(ps, cases, q=magnitudes(5, 6.0, seed=3), planar=planar, records=2)
     assert np.all(got.rmin > 0) and np.all(got.sq[:, :4] > 0) and np.all(got.msd[:, 0] > 0)
 
 
@@ -363,31 +263,11 @@ def test_error_bars_are_the_blocking_transform_of_the_rows(ps):
 
 
 def test_records_between_exchange_rounds(ps):
-    kTs = [0.25, 0.35, 0.5, 0.75, 1.2, 2.0, 4.0]
-    cases = [ps.default_params(n=8, E0=3.0, Fz=0.2, kT=kT, num_chains=64, seed=i) for i, kT in enumerate(kTs)]
-    q = magnitudes(3, 4.0, seed=9)
-    o = dict(max_sep=-1, min_sep=1, nbins=12)
-    with ps.Ensemble(cases) as A, ps.Ensemble(cases) as B:
-        ta, tb = (e.open_tempering(ps.ladders_by(cases), seed=9) for e in (A, B))
-        g = A.open_pdist(-1, 1, (12, 5.0), q)
-        values = []
-        for _ in range(5):
-            A.advance_tempered(ta, 200, 50)
-            g.record()
-            B.advance_tempered(tb, 200, 50)
-            ang = angles_of_all(B).reshape(7, 64, 16)
-            values.append([pr.per_chain(ang[k], cases[k].b, -1, 1, 12, 5.0, q) for k in range(7)])
-        got = g.read()
-        sa, sb = ta.stats(), tb.stats()
-        assert sa[2] == sb[2] == 20 and sa[1].sum() > 0, "no exchange was accepted: the records would not show a swapped configuration"
-        assert np.array_equal(sa[0], sb[0]) and np.array_equal(sa[1], sb[1])
-        assert_same_chains(A, B, range(7 * 64))
-    assert got.records == 5
-    compare(8, 64, cases, o, np.full(7, 5.0), q, False, values, got, None)
+    cases = rc.ladder_cases(ps)
+    rc.totals_between_exchange_rounds(ps, cases, pdist_kind(cases, nbins=12, rmax=5.0, q=magnitudes(3, 4.0, seed=9)))
 
 
 def test_refusals_leave_the_handle_usable(ps):
-    lib = ps._lib.load()
     with ps.Ensemble([ps.default_params(n=6, num_chains=4, kT=kT, umbrella=1) for kT in (1.0, 2.0)]) as e:
         with pytest.raises(ps.PstatError) as err:
             e.open_pdist()
@@ -404,57 +284,9 @@ def test_refusals_leave_the_handle_usable(ps):
             with pytest.raises(ps.PstatError) as err:
                 e.open_pdist(**kw)
             assert err.value.code == code and needle in str(err.value), (kw, str(err.value))
-        g = e.open_pdist(q=[1.0], capacity_rows=2)
-        with ps.Ensemble(cases[:2]) as other:                        # an object of another handle
-            assert lib.pstat_pdist_record(other._h, g._g) == -1 and b"the pdist object is not an open one" in lib.pstat_last_error()
-            assert lib.pstat_advance_pdist(other._h, g._g, 10, 5) == -1
-            assert lib.pstat_advance_pdist(other._h, g._g, 10, 0) == -1 and b"not an open one" in lib.pstat_last_error()
-            assert lib.pstat_pdist_read(other._h, g._g, None, None, None) == -1
-            assert lib.pstat_pdist_clear(other._h, g._g) == -1
-            ptr, a, b = C.c_void_p(), C.c_int64(), C.c_int64()
-            assert lib.pstat_pdist_rows(other._h, g._g, C.byref(ptr), C.byref(a), C.byref(b)) == -1
-            lib.pstat_pdist_close(other._h, g._g)                    # ignored: it is not the other handle's to close
-            assert other.chain_state(0)["steps_recorded"] == 0
-        assert lib.pstat_advance_pdist(e._h, g._g, 10, 0) == -1 and b"stepout" in lib.pstat_last_error()
-        assert lib.pstat_advance_pdist(e._h, g._g, -1, 5) == -1 and b"nsteps" in lib.pstat_last_error()
-        assert e.chain_state(0)["steps_recorded"] == 0 and g.read().records == 0
-        e.advance_pdist(g, 25, 10)
-        assert g.read().records == 2 and e.chain_state(0)["steps_recorded"] == 25
-        # the row buffer is full: refused with nothing enqueued
-        assert lib.pstat_advance_pdist(e._h, g._g, 10, 10) == -7
-        assert b"the pdist object has 0 of 2 rows free, this call would record 1" in lib.pstat_last_error()
-        assert lib.pstat_advance_pdist(e._h, g._g, -1, 10) == -1     # an argument error comes before the full buffer
-        assert lib.pstat_pdist_record(e._h, g._g) == -7
-        assert e.chain_state(0)["steps_recorded"] == 25 and g.read().records == 2
-        e.advance_pdist(g, 9, 10)                                    # no record in this call: it fits
-        assert e.chain_state(0)["steps_recorded"] == 34
-        g.clear()
-        g.record()
-        records = C.c_int64(-1)                                      # every output may be NULL
-        assert lib.pstat_pdist_read(e._h, g._g, None, None, C.byref(records)) == 0 and records.value == 1
-        totals = e.open_pdist(max_sep=0)                             # rmin alone, no rows kept: no limit, and no rows to hand out
-        e.advance_pdist(totals, 50, 1)
-        assert totals.read().records == 50 and totals.rows() == (0, 0, 3 * 1) and totals.read().sq.shape == (3, 0)
-        with pytest.raises(ps.PstatError):
-            totals.error_bars()
-        keep = e.open_pdist()
-        raw = g._g
-        g.close()                                                    # with its last record still in flight
-        assert g._g is None
-        assert lib.pstat_pdist_read(e._h, raw, None, None, None) == -1 and b"not an open one" in lib.pstat_last_error()
-        assert lib.pstat_pdist_record(e._h, raw) == -1 and lib.pstat_advance_pdist(e._h, raw, 0, 1) == -1
-        assert lib.pstat_pdist_clear(e._h, raw) == -1
-        lib.pstat_pdist_close(e._h, raw)                             # a second close is harmless
-        e.advance_pdist(keep, 5, 5)                                  # the handle and its other objects go on
-        assert keep.read().records == 1 and e.chain_state(0)["steps_recorded"] == 89
-        blob = e.checkpoint()                                        # the object is not part of a checkpoint
-        e.restore(blob)
-        assert keep.read().records == 1
-        e.open_pdist(bins=(8, 3.0), q=[1.0]).record()                # destroyed with objects open, a record in flight
-    with ps.Ensemble(cases) as e:                                    # the next handle of the process works
-        g = e.open_pdist()
-        e.advance_pdist(g, 10, 3)
-        assert g.read().records == 3
+        e.advance(5)                                                 # the handle still advances
+        assert e.chain_state(0)["steps_recorded"] == 5
+        assert e.open_pdist(max_sep=0).read().sq.shape == (3, 0)     # rmin alone
     with ps.Ensemble(ps.default_params(n=2475, num_chains=1)) as e:  # beyond a workgroup's LDS with 512 bins; fits with none
         with pytest.raises(ps.PstatError) as err:
             e.open_pdist(bins=(512, 50.0))
@@ -476,30 +308,14 @@ def test_refusals_leave_the_handle_usable(ps):
 
 
 # ------------------------------------------------------------------------------------------------ the tool
-AXES = [("n", "8"), ("Fz", "0,1,2,3")]
-FIXED = ["--num-steps", "3200", "--stepout", "100", "-v", "0"]
 SPEC = "6:12,sep=5,min=2,q=6:4"
 
 
-def _sweep(tmp_path, name, *extra):
-    out = tmp_path / name
-    axes = [a for k, v in AXES for a in ("--axis", f"{k}={v}")]
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "run_sweep.py"), str(out), *axes,
-                        "--num-chains", "64", "--seed", "11", *extra, "--", *FIXED], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return out
-
-
 def test_sweep_writes_pdist_files(tmp_path):
-    with_pdist = _sweep(tmp_path, "s", "--pdist", SPEC)
-    plain = _sweep(tmp_path, "p")
-    outs = sorted(f for f in os.listdir(plain) if f.endswith(".out"))
-    assert len(outs) == 4 and sorted(f for f in os.listdir(with_pdist) if f.endswith(".out")) == outs
-    for f in outs:                                                   # the .out files are a plain run's, byte for byte
-        assert (with_pdist / f).read_bytes() == (plain / f).read_bytes(), f
-    assert not [f for f in os.listdir(plain) if f.endswith(".pdist")]
-    files = sorted(f for f in os.listdir(with_pdist) if f.endswith(".pdist"))
-    assert files == [f[:-len(".out")] + ".pdist" for f in outs]
+    with_pdist = rc.sweep_tool(tmp_path, "s", "--pdist", SPEC)
+    plain = rc.sweep_tool(tmp_path, "p")
+    outs, _ = rc.assert_out_files_unchanged(with_pdist, plain, ".pdist")
+    assert len(outs) == 4
     # the same sweep through the Python API: the hosts' run_cases with a Recording, every case of the ensemble at once
     from polymer_stats_amd import sweep as sw
     cases = sw.product_cases([(k, sw.axis_values(v)) for k, v in AXES])

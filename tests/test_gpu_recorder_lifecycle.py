@@ -1,29 +1,27 @@
-"""GPU tests of the recorder lifecycle: the rules that the five kinds of object a handle keeps open -- series,
-tempering, hist, corr, shape -- share, asserted for every kind alike through the raw entry points of the library: whose object
-it is, the order of the refusals of an advance, a full row buffer, the count of records, use after close, and a handle destroyed
-with objects open.  What a record holds is the business of each kind's own tests."""
+"""GPU tests of the recorder lifecycle: the rules that the six kinds of object a handle keeps open -- series,
+tempering, hist, corr, shape, pdist -- share, asserted for every kind alike through the raw entry points of the library: whose
+object it is, the order of the refusals of an advance, a full row buffer, the count of records, clearing, reading with no
+output, totals kept without rows, use after close, a checkpoint restored under open objects, and a handle destroyed with objects
+open.  What a record holds is the business of each kind's own tests."""
 import ctypes as C
 
 import numpy as np
 import pytest
+
+from recorder_cases import ps  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 
 NSTEPS, STEPOUT = 10, 3          # three records and a remainder of one step
 NOT_OPEN = {"series": b"not an open series", "tempering": b"the tempering object is not an open one",
             "hist": b"not an open histogram", "corr": b"the correlation object is not an open one",
-            "shape": b"the shape object is not an open one"}
+            "shape": b"the shape object is not an open one", "pdist": b"the pdist object is not an open one"}
 KINDS = tuple(NOT_OPEN)
-RECORDING = ("series", "hist", "corr", "shape")      # the kinds with a pstat_advance_X
-WITH_ROWS = ("series", "corr", "shape")              # the kinds with a row capacity
-NOUN = {"series": b"the series has", "corr": b"the correlation object has", "shape": b"the shape object has"}
-
-
-@pytest.fixture(scope="module")
-def ps():
-    import polymer_stats_amd as ps
-    assert ps._lib.load().pstat_device_count() >= 1, "no HIP device visible"
-    return ps
+TOTALS = ("corr", "shape", "pdist")                  # the kinds that keep column totals (a _Totals)
+RECORDING = ("series", "hist") + TOTALS              # the kinds with a pstat_advance_X and a pstat_X_clear
+WITH_ROWS = ("series",) + TOTALS                     # the kinds with a row capacity
+NOUN = {"series": b"the series has", "corr": b"the correlation object has", "shape": b"the shape object has",
+        "pdist": b"the pdist object has"}
 
 
 def ensemble(ps, planar):
@@ -42,7 +40,9 @@ def open_kind(ps, e, kind, capacity=8):
         return e.open_hist([ps._lib.hist_spec("r3", 8, -5.0, 5.0)])
     if kind == "corr":
         return e.open_corr(("nn",), capacity_rows=capacity)
-    return e.open_shape([[0.0, 0.0, 0.5]], capacity_rows=capacity)
+    if kind == "shape":
+        return e.open_shape([[0.0, 0.0, 0.5]], capacity_rows=capacity)
+    return e.open_pdist(q=[1.0], capacity_rows=capacity)
 
 
 def entry_points(lib, kind):
@@ -131,6 +131,24 @@ def test_advance_refuses_before_it_enqueues(ps, kind, planar):
             assert steps_recorded(e) == [NSTEPS, NSTEPS] and count(lib, e, kind, obj) == 3
         assert advance_raw(lib, kind, e._h, obj._g, STEPOUT - 1, STEPOUT) == 0      # a call that records nothing always fits
         assert steps_recorded(e) == [NSTEPS + STEPOUT - 1] * 2 and count(lib, e, kind, obj) == 3
+        obj.clear()                                                # no records, and every row free again
+        assert count(lib, e, kind, obj) == 0 and (kind not in TOTALS or obj.rows()[1] == 0)
+        assert advance_raw(lib, kind, e._h, obj._g, NSTEPS, STEPOUT) == 0, lib.pstat_last_error()
+        assert count(lib, e, kind, obj) == 3
+        if kind != "series":       # every output may be NULL
+            records = C.c_int64(-1)
+            assert getattr(lib, f"pstat_{kind}_read")(e._h, obj._g, None, None, C.byref(records)) == 0 and records.value == 3
+
+
+@pytest.mark.parametrize("planar", [False, True], ids=["3d", "planar"])
+@pytest.mark.parametrize("kind", TOTALS)
+def test_totals_without_rows_have_no_limit(ps, kind, planar):
+    with ensemble(ps, planar) as e:
+        obj = open_kind(ps, e, kind, capacity=0)                   # no rows kept: no limit, and no rows to hand out
+        advance(e, kind, obj, 50, 1)
+        assert obj.read().records == 50 and obj.rows() == (0, 0, e.ncases * obj.ncols)
+        with pytest.raises(ps.PstatError):
+            obj.error_bars()
 
 
 @pytest.mark.parametrize("planar", [False, True], ids=["3d", "planar"])
@@ -148,6 +166,8 @@ def test_a_closed_object_is_refused(ps, kind, planar):
         getattr(lib, f"pstat_{kind}_close")(e._h, raw)             # a second close is harmless
         obj.close()
         advance(e, kind, keep, NSTEPS, STEPOUT)                    # the handle and its other objects go on
+        assert count(lib, e, kind, keep) == 3 and steps_recorded(e) == [2 * NSTEPS, 2 * NSTEPS]
+        e.restore(e.checkpoint())                                  # no object is part of a checkpoint
         assert count(lib, e, kind, keep) == 3 and steps_recorded(e) == [2 * NSTEPS, 2 * NSTEPS]
 
 
