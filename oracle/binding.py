@@ -60,7 +60,7 @@ class EapStepOut(C.Structure):
                 ("flipped", C.c_int32), ("flip_bit", C.c_int32), ("accept", C.c_int32), ("pad_", C.c_int32),
                 ("ngrow", C.c_int64), ("phi_trial", C.c_double), ("theta_trial", C.c_double),
                 ("d", C.c_double), ("eps", C.c_double), ("mag", C.c_double), ("log_alpha", C.c_double),
-                ("U_cur", C.c_double), ("U_trial", C.c_double)]
+                ("U_cur", C.c_double), ("U_trial", C.c_double), ("usum_cur", C.c_double), ("usum_trial", C.c_double)]
 
 
 def build(force: bool = False) -> str:
@@ -301,6 +301,8 @@ class Step:
     log_alpha: float
     U_cur: float
     U_trial: float
+    usum_cur: float            # sum(us) of both chains
+    usum_trial: float
     trial_phi: np.ndarray      # [n] every angle of the trial chain
     trial_theta: np.ndarray
     grow: np.ndarray           # [ngrow, 3]: draw, link probability, draw - probability
@@ -333,7 +335,8 @@ def step_judge(params: EapParams, phi, theta, rng, phi_step: float, theta_step: 
     return Step(rng=np.array(out.rng[:], dtype=np.uint32), idx=out.idx, lower=out.lower, upper=out.upper,
                 flipped=bool(out.flipped), flip_bit=bool(out.flip_bit), accept=bool(out.accept),
                 phi_trial=out.phi_trial, theta_trial=out.theta_trial, d=out.d, eps=out.eps, mag=out.mag,
-                log_alpha=out.log_alpha, U_cur=out.U_cur, U_trial=out.U_trial, trial_phi=tphi, trial_theta=tth,
+                log_alpha=out.log_alpha, U_cur=out.U_cur, U_trial=out.U_trial, usum_cur=out.usum_cur,
+                usum_trial=out.usum_trial, trial_phi=tphi, trial_theta=tth,
                 grow=grow[:out.ngrow])
 
 

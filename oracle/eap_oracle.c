@@ -720,13 +720,20 @@ int eap_run_cluster(const eap_params *P0, uint64_t chain_id, eap_result *out, ea
 
 /* |t| over the terms t that d is the signed sum of, for a trial that changed the monomers [lo, hi] */
 static double judge_mag(const eap_params *P, const chain_t *cur, const chain_t *tri, int64_t lo, int64_t hi,
-                        double log_alpha) {
+                        double log_alpha, double wscale) {
   const int64_t n = cur->n;
   const chain_t *side[2] = {cur, tri};
-  double e = 0.0, jac = 0.0;                 /* energy terms (divided by kT below), Jacobian terms */
+  double e = 0.0, jac = 0.0, wt = 0.0;       /* energy terms (divided by kT below), Jacobian terms, umbrella weight terms */
   for (int s = 0; s < 2; ++s) {
     const chain_t *c = side[s];
     for (int64_t i = lo; i <= hi; ++i) jac += fabs(log(c->sth[i]));
+    /* umbrella sampling: scale |u_i| of every changed monomer, term by term (set_u: the field term of monomer i and the
+     * bending energy of bond (i, i + 1); the bond below the lowest changed monomer changes too) */
+    if (wscale != 0.0) {
+      for (int64_t i = lo; i <= hi; ++i) wt += fabs(wscale * 0.5 * P->E0 * c->mus[3 * i + 2]);
+      for (int64_t j = (lo > 0 ? lo - 1 : 0); j <= hi && j + 1 < n; ++j)
+        wt += fabs(wscale * (P->bend_mod / 2 * (c->psis[j] - P->bend_angle) * (c->psis[j] - P->bend_angle)));
+    }
     if (P->energy_type != EAP_CUTOFF) {      /* UCutoff is the pair sum alone, see chain_U */
       for (int64_t i = lo; i <= hi; ++i) {
         e += fabs(-0.5 * P->E0 * c->mus[3 * i + 2]);
@@ -751,13 +758,13 @@ static double judge_mag(const eap_params *P, const chain_t *cur, const chain_t *
         }
     }
   }
-  return 1.0 + e / fabs(P->kT) + jac + fabs(log_alpha);
+  return 1.0 + e / fabs(P->kT) + jac + fabs(log_alpha) + wt;
 }
 
 static int step_judge(const eap_params *P, int cluster, const double *phi, const double *theta, const uint32_t rng_in[4],
                       double phi_step, double theta_step, const double *moved_to, eap_step_out *out, double *trial_phi,
                       double *trial_theta, double *grow, int64_t max_grow) {
-  if (check_params(P) || P->umbrella || !out) return -1;
+  if (check_params(P) || !out) return -1;
   if (!cluster && P->energy_type == EAP_CUTOFF) return -1;
   uint32_t rng[5] = {rng_in[0], rng_in[1], rng_in[2], rng_in[3], (uint32_t)P->rng};
   chain_t cur, tri;
@@ -773,8 +780,12 @@ static int step_judge(const eap_params *P, int cluster, const double *phi, const
   double djac = 0.0;
   for (int64_t i = lo; i <= hi; ++i) djac += log(tri.sth[i]) - log(cur.sth[i]);
   const double log_alpha = log(pr.alpha);
+  /* umbrella sampling: the weight function of the run loops; its gauge constant cancels in the difference */
+  const weight_t wf = weight_make(P, cur.Omega);
+  out->usum_cur = sum_us(&cur); out->usum_trial = sum_us(&tri);
   out->d = -(tri.U - cur.U) / P->kT + djac + log_alpha;
-  out->mag = judge_mag(P, &cur, &tri, lo, hi, log_alpha);
+  if (wf.on) out->d += weight_eval(&wf, out->usum_trial) - weight_eval(&wf, out->usum_cur);
+  out->mag = judge_mag(P, &cur, &tri, lo, hi, log_alpha, wf.on ? wf.scale : 0.0);
   out->eps = pr.eps;
   out->log_alpha = log_alpha;
   out->accept = metropolis_ok(out->d, pr.eps);

@@ -128,7 +128,8 @@ int eap_run_cluster(const eap_params *P, uint64_t chain_id, eap_result *out, eap
  * The run loops above and these entry points share the functions that draw the step's words, build the trial chain
  * (move!, cluster_flip!) and apply acceptance.jl:29-39; what differs is where the density of the CURRENT chain comes
  * from: the run loops keep the acceptor's cached value, the judge computes both sides fresh from the angles it is given.
- * No umbrella sampling (returns -1). */
+ * Under P->umbrella d gains weight_eval(trial) - weight_eval(current) of the run loops' weight function (its gauge constant
+ * cancels) and mag gains scale |u_i| of every changed monomer, old and new. */
 typedef struct eap_step_out {
   uint32_t rng[4];              /* generator words after the step */
   int64_t idx;                  /* the monomer of the single move */
@@ -143,9 +144,11 @@ typedef struct eap_step_out {
   double eps;                   /* under P->uniform_bits */
   double mag;                   /* 1 + sum |t| over the terms t that d is the signed sum of: the field, force and bending terms
                                    of the changed monomers and every pair term that changes, old and new, over kT;
-                                   |log sin theta| and |log sin theta'| of the changed monomers; |log alpha| */
+                                   |log sin theta| and |log sin theta'| of the changed monomers; |log alpha|; under
+                                   umbrella sampling scale |u_i| of the changed monomers */
   double log_alpha;
   double U_cur, U_trial;        /* energy.jl:7-23 of both chains */
+  double usum_cur, usum_trial;  /* sum(us) of both chains: what the umbrella weight function is evaluated on */
 } eap_step_out;
 /* phi, theta: [n], radians.  rng: the four state words (the kind is P->rng).  trial_phi / trial_theta: [n] or NULL, every
  * angle of the trial chain.  grow: [max_grow][3] or NULL -- per growth test the draw, the link probability, draw - probability.

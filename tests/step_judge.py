@@ -57,12 +57,19 @@ F32_ANGLE_BOUND_TURNS = 8 * U
 #       kernels use, v_exp_f32 1.4 u relative, v_rcp_f32 0.86 ulp, v_rsq_f32 0.83 ulp -- on NORMAL results: v_exp_f32
 #       and v_rcp_f32 return 0 for every result below 2^-126.  No decision gets there: exp2 underflows for d < -87, where
 #       eps >= 2^-23 has long rejected, and alpha is a ratio of link probabilities nowhere near 2^126.)
+#   (d') umbrella sampling: the exponent gains (dw - lag) log2(e), dw = du * wscale, and goes through the same v_exp_f32.  dw is
+#       one more term of d: du is the SAME rounded number that enters dU (read in the kernels: `dw = du * wscale`,
+#       `dus * wscale`, `(tr.usum - cur.usum) * wscale`), so an error of its sines and cosines moves -du / kT + du wscale by the
+#       NET coefficient |1 / kT - wscale| A, which is below A / kT because 0 < wscale kT <= 1 (coefficient_over_kT; the CPU test
+#       asserts both): (b) and (c) stand as they are.  Its roundoff -- the product with wscale, the sum with -lag, the
+#       product with log2(e) -- is three more rounded operations on |dw|, which mag carries as scale |u_i| of every changed
+#       monomer, old and new (and du's own roundoff is already in (a)).                                     3
 #   (e) log sin.  The kernels never take it, they compare u sin0 against sin1 e; an absolute SINCOS_ABS on sin(theta) is a
 #       relative SINCOS_ABS / sin(theta) = the error of log sin, and (c) moves log sin(theta') by 31 u |cot theta'|.  mag grows
 #       only like 1 + |log sin|, so no constant covers the poles: these enter the margin as a term of their own,
 #           pole = sum over the changed monomers of SINCOS_ABS (1 / sin theta + 1 / sin theta') + 31 u |cot theta'| (moved one),
 #       m = C_VERDICT 2^-24 mag + pole.  Far from a pole it is ~1e-6; it only matters within ~1e-2 rad of one.
-# Sum of (a)-(d): ~522.  The next power of two:
+# Sum of (a)-(d'): ~525.  The next power of two:
 C_VERDICT = 1024.0
 SINCOS_ABS = 4 * U
 PROPOSAL_RAD = 31 * U          # (c): 5 * 2^-24 turns in radians
@@ -296,16 +303,21 @@ class Walk:
     decided: int = 0
     wrong: int = 0            # against `judge_op`, if one was given
     steps: list = field(default_factory=list)
+    recs: list = field(default_factory=list)       # with `rec_params`: the Rec of the chain after every step,
+    trials: list = field(default_factory=list)     #   of the step's trial where it was rejected (else None),
+    usum0: float = 0.0                             #   and usum of the start
+    start: object = None                           #   and the start's Rec
 
 
 def walk(ob, op, chain_id, nsteps, cluster, judge_op=None, keep=False, c=C_VERDICT, precision=None, probe=None,
-         probe_every=25) -> Walk:
+         probe_every=25, rec_params=None) -> Walk:
     """The oracle's chain stepped by the judge alone from the seeded start: state -> judge -> accept or not -> state.
     Counts the steps whose verdict lies within the margin.  With `judge_op` (another parameter set, e.g. E0 perturbed) that
     judge's verdicts on the same states are held against the true decisions: `wrong` counts its decided disagreements.
     precision = Q16: the chain lives on the lattice -- the start is quantised as the device quantises it (index = floor) and
     every single move goes where the integer rule puts it; an off-lattice theta' is rejected.
-    probe(phi, theta): called on the current configuration every `probe_every` steps and at the end."""
+    probe(phi, theta): called on the current configuration every `probe_every` steps and at the end.
+    rec_params: the configuration's option dict; the walk then keeps what record_twin needs (Walk.recs, trials, usum0)."""
     phi, th, rng = ob.seed_state(op, chain_id)
     q16 = precision == Q16
     if q16:
@@ -316,6 +328,10 @@ def walk(ob, op, chain_id, nsteps, cluster, judge_op=None, keep=False, c=C_VERDI
     lag = 0.0
     acc = np.zeros(nsteps, dtype=np.uint8)
     W = Walk(acc, phi, th, rng, ps, ts)
+    if rec_params is not None:
+        rec = rec_of(ob, op, rec_params, phi, th, cluster)
+        W.usum0 = rec.usum
+        W.start = rec
     for t in range(nsteps):
         pre = dict(phi=phi, theta=th, rng=rng, phi_step=ps, theta_step=ts)
         J, inside = judge(ob, op, pre, Q16, cluster) if q16 else (ob.step_judge(op, phi, th, rng, ps, ts, cluster=cluster), True)
@@ -338,6 +354,12 @@ def walk(ob, op, chain_id, nsteps, cluster, judge_op=None, keep=False, c=C_VERDI
         if ok:
             phi, th, lag = J.trial_phi, J.trial_theta, J.log_alpha
             nacc += 1
+        if rec_params is not None:
+            tri = rec_of(ob, op, rec_params, J.trial_phi, J.trial_theta, cluster, magnitudes=ok)
+            assert abs(tri.usum - J.usum_trial) <= 1e-12 * (1 + tri.lit_us) and abs(rec.usum - J.usum_cur) <= 1e-12 * (1 + rec.lit_us)
+            W.trials.append(None if ok else tri)
+            rec = tri if ok else rec
+            W.recs.append(rec)
         natt += 1
         rng = J.rng
         ps, ts, nacc, natt = ob.adapt(op, t + 1, ps, ts, nacc, natt)
@@ -488,8 +510,119 @@ def _allpairs_configs():
     return out
 
 
-CONFIGS = _sweep_configs() + _cluster_configs() + _allpairs_configs()
+# A gauge rise needs a chain whose later configurations outweigh its first by more than e^30: a cold polar chain started
+# AGAINST the field (--x0 with theta near pi), which the field and the force then turn round.  Its log-weight gauged on the
+# start, wscale E0 mu / 2 (sum cos theta - sum cos theta_0), cannot exceed wscale E0 mu n: the rows choose E0 mu n so that
+# this stays below RISE_MAX = 80 -- inside f32's range, so that the records before the rise still count -- and the
+# oracle's own walk of every judged chain reaches RISE_MIN = 35 within T (tests/test_step_judge_cpu.py asserts both): above
+# the f32 threshold of 30 by far more than any f32 error of w.
+RISE_MIN, RISE_MAX = 35.0, 80.0
+_AGAINST = dict(use_x0=1, x0_phi=0.0, x0_theta=2.84, dx0_phi=6.28, dx0_theta=0.2)      # theta in [2.84, 3.04]
+_COLD = dict(chain_type=POLAR, E0=24.0, mu=0.4, kT=0.5, Fz=0.7, Fx=0.0, b=0.7)           # wscale kT = 0.2 + 0.8 e^-0.98 = 0.5
+
+
+# The weight function takes wscale kT = 0.2 ... 1 of the field's pull away (that is its purpose), and an Ising chain that the
+# field no longer aligns visits the contact of two antiparallel neighbours far more often: on the oracle's walk of the n = 3 row
+# with the force of _DIEL_ISING, sum |pair terms| reaches 1e3 kT, and check (b) misses its bound there (measured: error / bound
+# 1.24 on U).  The umbrella Ising rows with bonds are therefore held along the field by a stronger force, Fz b / kT = 5.6 at
+# kT = 0.7: sum |pair terms| stays below 25 kT at n = 2, 3.
+_HELD_ISING = dict(_DIEL_ISING, Fz=3.0)
+
+
+def _umbrella_configs():
+    out = []
+    U1 = dict(umbrella=1)
+    # sweep_kernel<float>, <float, q16 state>: n = 1, 3, 20; NI and weak-coupling Ising, both chain types; both generators;
+    # adaptive and fixed (T by the rule of _sweep_configs)
+    # (A polar Ising chain with bonds -- n = 3, n = 20, either kT, any of the seeds tried, Fx up to 6 -- falls into the 1/r^3
+    #  contact of two antiparallel neighbours, |n_i + n_j| / 2 ~ 0.002, U ~ -1e3 ... -1e5 kT, where check (b)'s bound does not
+    #  hold (measured: error / bound 1.01 at U = -1799; cf. _cluster_configs).  So the polar Ising row is the one at n = 1, the
+    #  Ising rows with bonds are dielectric (_HELD_ISING), and the polar chain with neighbours is the NI row at n = 3.)
+    rows = [(1, NONINTERACTING, _DIEL, MWC, 0.7, True, 1000, 4001), (1, ISING, _POLAR_ISING, XOSHIRO, 2.0, False, 2000, 4001),
+            (3, NONINTERACTING, _POLAR, XOSHIRO, 2.0, False, 2000, 4003), (3, ISING, _HELD_ISING, MWC, 0.7, True, 2000, 4003),
+            (20, NONINTERACTING, _DIEL, MWC, 0.7, False, 1000, 4020), (20, ISING, _HELD_ISING, XOSHIRO, 0.7, True, 2000, 4020)]
+    for prec, pname, kern in ((F32, "f32", "sweep_kernel<float>"), (Q16, "q16", "sweep_kernel<float, q16 state>")):
+        for n, en, ct, g, kT, ad, T, seed in rows:
+            p = dict(n=n, energy_type=en, rng=g, kT=kT, seed=seed, **ct, **(_ADAPT if ad else _FIXED), **U1)
+            name = f"{pname}-umb-sweep-n{n}-{'ising' if en == ISING else 'ni'}-{'polar' if ct['chain_type'] == POLAR else 'diel'}"
+            out.append(Config(name, kern, prec, p, chains=70, T=T))
+    # cluster_kernel<float>, <float, q16 state>, <float, state in memory>: n = 2 and 20, with and without bending,
+    # cluster_prob 0.5, both chain types (the polar rows at E0 = 10, twice the field of _cluster_configs: the weight halves its net
+    # coefficient, and at E0 = 5 the q16 row at n = 20 did not meet the perturbed judge in 4800 steps of five chains)
+    D, P = DIELECTRIC, POLAR
+    # (the bending rows are the polar ones: where umbrella sampling lets a dielectric Ising chain at n = 20 put neighbours
+    #  antiparallel, psi -> pi, acos' slope 1 / sin psi carries the dot product's f32 error into the bending energy, which
+    #  check (b)'s bound does not count -- measured: error / bound 7.3 on U, every other column below 0.002)
+    rows = [(2, ISING, 0.0, True, D, 1200), (2, NONINTERACTING, 0.8, False, P, 1200),
+            (20, ISING, 0.0, False, D, 2400), (20, NONINTERACTING, 0.8, True, P, 2400)]
+    homes = ((F32, "f32lds", "cluster_kernel<float>", {"PSTAT_F32_STATE": "lds"}, "state in memory"),
+             (Q16, "q16lds", "cluster_kernel<float, q16 state>", {}, "state in memory"),
+             (F32, "f32mem", "cluster_kernel<float, state in memory>", {"PSTAT_F32_STATE": "global"}, ""))
+    for prec, pname, kern, env, notk in homes:
+        for i, (n, en, kappa, ad, chain, T) in enumerate(rows):
+            # (not _HELD_ISING: a cluster reflected out of a chain that the force holds along z leaves antiparallel neighbours at
+            #  both its ends, the contact itself)
+            ct = _DIEL_ISING if chain == D else dict(_POLAR, E0=10.0, do_flips=0)
+            # (seed 4402 starts chain 0 of the n = 20 Ising row inside a repulsive contact, U = 7.2e6: the first launch of check (b)
+            #  then carries the half ulp of that number for its 64 steps)
+            p = dict(n=n, energy_type=en, rng=MWC if i % 2 else XOSHIRO, kT=1.0 if i % 2 else 0.7,
+                     seed=4200 + 10 * n + i + (1000 if (n, en) == (20, ISING) else 0),
+                     bend_mod=kappa, bend_angle=0.3 if kappa else 0.0, cluster_prob=0.5, **ct, **(_ADAPT if ad else _FIXED), **U1)
+            name = f"{pname}-umb-cluster-n{n}-{'ising' if en == ISING else 'ni'}-{'polar' if chain == P else 'diel'}-{'bend' if kappa else 'nobend'}"
+            out.append(Config(name, kern, prec, p, chains=70, T=T, cluster=True, env=env, not_kernel=notk))
+    # interacting_kernel<float>: n = 23 (M = 1) and 130 (M = 4, partial ring); the extended start of _allpairs_configs
+    for i, (n, T, chains) in enumerate(((23, 400, 6), (130, 800, 3))):
+        ct = dict(chain_type=DIELECTRIC, E0=30.0, K1=0.0125, K2=0.0025, Fz=0.3, Fx=8.0, b=1.0) if i % 2 == 0 else \
+            dict(chain_type=POLAR, E0=100.0, mu=0.1, Fz=0.3, Fx=8.0, b=1.0, do_flips=1)
+        p = dict(n=n, energy_type=INTERACTING, rng=MWC if i % 2 else XOSHIRO, kT=1.0, seed=4300 + n, **ct, **_X0,
+                 **(_ADAPT if i % 2 else _FIXED), **U1)
+        out.append(Config(f"f32-umb-allpairs-n{n}", "interacting_kernel<float>", F32, p, chains=chains, T=T))
+    # cluster_wave_kernel<float>: n = 20 interacting, n = 64 cutoff, n = 130 interacting
+    inter = dict(E0=20.0, K1=0.02, K2=0.005, Fz=0.3, Fx=8.0, **_ADAPT)
+    cut = dict(E0=10.0, K1=0.4, K2=0.3, Fz=0.3, Fx=8.0, phi_step=0.15, theta_step=0.15, **_FIXED)
+    # (UCutoff has no field term, but the weight has: wscale |u_i| of the moved monomer enters mag, old and new, while the pair
+    #  terms decide.  With the recipe's E0 = 10 that is 7 and leaves 0.67 % of the steps undecided; the same dipoles
+    #  E0 (K1 - K2, K2) = (1, 3) from half the field make u_i half as large: 0.3 %.  The perturbed judge is caught about once
+    #  in 5000 steps of this row whatever its E0 -- the pair terms catch it -- hence T = 1200 and the seed: 4564 ... 4567, 4569 and
+    #  4571 do not meet it, 4572 does twice.  n = 130: 4630 and 4631 do not, 4632 does.)
+    cut = dict(cut, E0=5.0, K1=0.8, K2=0.6)
+    for n, en, phys, T, chains, seed in ((20, INTERACTING, inter, 600, 6, 4520), (64, CUTOFF, cut, 1200, 6, 4572),
+                                         (130, INTERACTING, inter, 1200, 4, 4632)):
+        p = dict(n=n, energy_type=en, rng=MWC, kT=1.0, seed=seed, chain_type=DIELECTRIC, b=1.0, cluster_prob=0.5,
+                 cutoff_radius=3.0, **_X0, **phys, **U1)
+        out.append(Config(f"f32-umb-allpairs-cluster-n{n}-{'cutoff' if en == CUTOFF else 'interacting'}",
+                          "cluster_wave_kernel<float>", F32, p, chains=chains, T=T, cluster=True))
+    # one gauge-rise row per kernel family
+    ni = dict(n=8, energy_type=NONINTERACTING, rng=MWC, **_COLD, **_AGAINST, **_ADAPT, **U1)
+    out.append(Config("f32-rise-sweep-n8", "sweep_kernel<float>", F32, dict(ni, seed=4700, do_flips=1), chains=70, T=2000))
+    out.append(Config("q16-rise-sweep-n8", "sweep_kernel<float, q16 state>", Q16, dict(ni, seed=4701, do_flips=1), chains=70, T=1000))
+    # The clustering main reflects the whole aligned chain at its first cluster attempt (measured on the oracle's walk: the
+    # rise then happens at step 1, before anything is recorded), so its rows start just below the equator, theta in
+    # [1.75, 1.95]: the reflection gains less than e^30 and the rise comes later, from the single moves, with records behind it.
+    below = dict(x0_theta=1.75)
+    cl = dict(ni, cluster_prob=0.5, **{k: v for k, v in _AGAINST.items() if k != "x0_theta"})
+    cl = dict({k: v for k, v in cl.items() if k != "x0_theta"}, **below)
+    out.append(Config("f32lds-rise-cluster-n8", "cluster_kernel<float>", F32, dict(cl, seed=4706), chains=70, T=1200, cluster=True,
+                      env={"PSTAT_F32_STATE": "lds"}, not_kernel="state in memory"))
+    out.append(Config("f32mem-rise-cluster-n8", "cluster_kernel<float, state in memory>", F32, dict(cl, seed=4703), chains=70,
+                      T=1200, cluster=True, env={"PSTAT_F32_STATE": "global"}))
+    # all-pairs: the rod of _X0 pointing down the field (theta in [2.1, 2.4], without --do-flips, which lands a monomer on its
+    # neighbour here; [1.6, 1.9] under cluster flips), held along x by
+    # Fx as in _allpairs_configs, so that turning round does not fold it onto itself (CONTACT_DISTANCE is asserted as there)
+    rod = dict(energy_type=INTERACTING, rng=MWC, kT=1.0, chain_type=POLAR, mu=0.1, Fz=0.3, Fx=8.0, b=1.0, use_x0=1, x0_phi=-0.25,
+               dx0_phi=0.5, dx0_theta=0.3, **_ADAPT, **U1)
+    out.append(Config("f32-rise-allpairs-n23", "interacting_kernel<float>", F32,
+                      dict(rod, n=23, E0=160.0, x0_theta=2.1, seed=4704), chains=6, T=800))
+    out.append(Config("f32-rise-allpairs-cluster-n20", "cluster_wave_kernel<float>", F32,
+                      dict(rod, n=20, E0=240.0, x0_theta=1.6, cluster_prob=0.5, cutoff_radius=3.0, seed=4705), chains=6, T=1200,
+                      cluster=True))
+    return out
+
+
+RISE_IDS = []          # filled below: the names of the gauge-rise rows
+CONFIGS = _sweep_configs() + _cluster_configs() + _allpairs_configs() + _umbrella_configs()
 CONFIG_IDS = [c.name for c in CONFIGS]
+RISE_IDS = [c.name for c in CONFIGS if "-rise-" in c.name]
 
 # the packed sweep: 13 cases x 5 chains of different E0, Fz, kT, n = 12
 PACKED_CASES = [dict(E0=3.0 + 0.25 * i, Fz=0.2 * (i % 5), kT=0.5 + 0.12 * i) for i in range(13)]
@@ -511,11 +644,13 @@ def perturbed(ob, cfg_params):
 
 # ------------------------------------------------------------------------------------------------- totals, term by term
 
-def term_sums(p: dict, phi, theta):
+def term_sums(p: dict, phi, theta, conditioning: bool = False):
     """For the bound on the carried totals, f64 numpy: (lit, c1) -- lit: the sum of |terms| of r (3), p (3) and U by their
     value; c1: the single-monomer coefficient of each of the seven (the term with every sine and cosine replaced by 1).
     p: the configuration's options.  (Only magnitudes are taken from here; the reference values of r, p, U themselves come
-    from the oracle's eap_chain_energy.)"""
+    from the oracle's eap_chain_energy.)
+    conditioning = True: also (cond_sum, cond_max), the sum and the largest of T0 (m + 1) / rho over the pair terms -- T0 =
+    |mu_i| |mu_j| / (4 pi r^3), m = j - i, rho = r / b: what PAIR CONDITIONING of the record bound multiplies."""
     phi, theta = np.asarray(phi), np.asarray(theta)
     n = len(phi)
     nh = np.stack([np.cos(phi) * np.sin(theta), np.sin(phi) * np.sin(theta), np.cos(theta)], axis=1)
@@ -531,7 +666,7 @@ def term_sums(p: dict, phi, theta):
     r_abs = np.abs(b * nh).sum(axis=0)
     p_abs = np.abs(mu).sum(axis=0)
     en = p["energy_type"]
-    u = u_c = 0.0
+    u = u_c = cond_sum = cond_max = 0.0
     if en != CUTOFF:
         u += np.abs(0.5 * E0 * mu[:, 2]).sum() + abs(p.get("Fx", 0.0)) * r_abs[0] + abs(p.get("Fz", 0.0)) * r_abs[2]
         u_c = 0.5 * abs(E0) * mu_c + (abs(p.get("Fx", 0.0)) + abs(p.get("Fz", 0.0))) * abs(b)
@@ -549,22 +684,324 @@ def term_sums(p: dict, phi, theta):
         rm = np.sqrt(r2)
         h = rv / rm[:, None]
         t = ((mu[ii] * mu[jj]).sum(axis=1) - 3 * (mu[ii] * h).sum(axis=1) * (mu[jj] * h).sum(axis=1)) / (4 * math.pi * r2 * rm)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            cond = np.sqrt((mu[ii] ** 2).sum(axis=1) * (mu[jj] ** 2).sum(axis=1)) / (4 * math.pi * r2 * rm) * (jj - ii + 1) * abs(b) / rm
         if en == CUTOFF:
-            t = t[r2 <= (p.get("cutoff_radius", 7.5) * b) ** 2]
+            inside = r2 <= (p.get("cutoff_radius", 7.5) * b) ** 2
+            t, cond = t[inside], cond[inside]
         u += np.abs(t).sum()
+        if len(cond):
+            cond_sum, cond_max = float(cond.sum()), float(cond.max())
     lit = np.concatenate([r_abs, p_abs, [u]])
     c1 = np.array([abs(b)] * 3 + [mu_c] * 3 + [u_c])
-    return lit, c1
+    return (lit, c1, cond_sum, cond_max) if conditioning else (lit, c1)
+
+
+def umbrella_scale(p: dict) -> float:
+    """The scale of AntiDipoleWeightFunction (inc/average.jl:104-124): w = sum(u) scale - gauge.  Restated, not imported."""
+    F2 = p.get("Fx", 0.0) ** 2 + p.get("Fz", 0.0) ** 2
+    return (0.2 + 0.8 * math.exp(-F2 / p["kT"])) / p["kT"]
 
 
 def coefficient_over_kT(p: dict) -> float:
-    """The largest single-monomer coefficient A / kT of a configuration: field, force."""
-    if p["energy_type"] == CUTOFF:
-        return 0.0          # UCutoff is the pair sum alone
+    """The largest single-monomer coefficient A / kT of a configuration: field, force.  Under umbrella sampling the field
+    term enters d as -du / kT + du wscale with one and the same du (see (d') above): its coefficient is the net one,
+    |1 / kT - wscale| A; UCutoff has no field term in U, so there the weight's wscale A stands alone."""
     E0 = abs(p["E0"])
     if p["chain_type"] == DIELECTRIC:
         field = 0.5 * E0 * E0 * (abs(p.get("K1", 1.0) - p.get("K2", 0.0)) + abs(p.get("K2", 0.0)))
     else:
         field = 0.5 * E0 * abs(p.get("mu", 1e-2))
+    ws = umbrella_scale(p) if p.get("umbrella") else 0.0
+    if p["energy_type"] == CUTOFF:
+        return ws * field       # UCutoff is the pair sum alone
     force = max(abs(p.get("Fx", 0.0)), abs(p.get("Fz", 0.0))) * abs(p.get("b", 1.0))
-    return max(field, force) / p["kT"]
+    return max(field * abs(1.0 / p["kT"] - ws), force / p["kT"])
+
+
+# ------------------------------------------------------------------------------------------------- the record, check (d)
+#
+# Every step, accepted or not, adds the current r, p, U and their squares (the clustering main also sum cos^2 theta and the
+# mean bond angle) to f32 block accumulators; the accumulators are folded into the f64 `sums` when a block of at most
+# FLUSH = 128 steps, an adaptation window or the launch ends.  Under umbrella sampling every record carries the weight
+# e^wrel, wrel = -(usum - uref) wscale, and the normaliser the sum of the weights; a configuration more than e^30 heavier than
+# the gauged one raises the gauge: the accumulators are multiplied by (float) e^-wrel, the f64 sums by the double.
+#
+# THE TWIN (record_twin) restates record! in numpy f64 on the states of one chain.  Plain: the 16 running sums in ABI order
+# (+ 2).  Umbrella: the gauge-free ratios  sum v e^L / sum e^L,  L = -s usum,  and N* = sum e^(L - max L), every prefix with ITS
+# maximum factored out, so nothing overflows; s is umbrella_scale (the oracle's weight_make(...).scale, restated).
+#
+# THE BOUND (record_bound), per prefix and column, in units of u = 2^-24; nothing in it is taken from a kernel's output.
+#   Per record, the error of wgt * v:
+#     the carried value: the CARRIED TOTALS bound above, e_v = (a + n) K_TOTALS u sum |terms| + (n + 2 a) K_ABS u c1, a = the
+#       steps accepted since the launch began (the all-pairs kernels re-derive more often: a bound all the same);
+#       a square v^2 errs by 2 |v| e_v + e_v^2, r.r and p.p by the sum of their three squares;
+#     PAIR CONDITIONING (found by check (d) on a polar Ising chain inside a 1/r^3 contact, |n_i + n_j| / 2 = 0.002, where U^2
+#       was off by 250 u relative against the 128 u of the line above; DESIGN.md 5.1 is the same thing seen in distribution):
+#       "by their value" counts a pair term's roundings but not the cancellation inside its separation.  The kernels
+#       form x_i - x_j from f32 n-hats -- `hb * (pnx + nix)` in refresh_totals and the step of pstat_kernels.hip, `bond()` of
+#       pstat_cluster.hip, the prefix sums behind ring_pair_sum of the all-pairs kernels -- m + 1 = j - i + 1 unit vectors whose
+#       components carry 9 u each (GROWTH TESTS), sqrt(3) 9 u < 16 u per vector: |d r| <= 16 (m + 1) u b.  A term
+#       (mu_i . mu_j - 3 (mu_i . h)(mu_j . h)) / (4 pi r^3) moves by at most 3 + 2 * 3 = 9 times T0 |d r| / r, T0 = |mu_i| |mu_j| /
+#       (4 pi r^3) (the r^-3, and the two projections on h = r / |r|).  So U gains
+#           K_COND u (sum over the pair terms of T0 (m + 1) / rho  +  4 a max T0 (m + 1) / rho),  rho = r / b,  K_COND = 9 * 16:
+#       the sum for the re-derivation (or the fresh pair sum of the all-pairs kernels), the maximum -- the largest any term
+#       has had so far -- for the at most two bonds, old and new, that a chain-per-lane kernel recomputes per accepted step.
+#       Away from contacts (rho >= CONTACT_DISTANCE, which the all-pairs rows assert) it is of the order of the line above.
+#     the extras: sum cos^2 theta like a total with unit coefficient; a bond angle psi = acos(n_i . n_j) errs by
+#       e_psi = min(sqrt(2 D), D / sin psi) + ACOS_ABS, D = 2 GROWTH_MARGIN the error of the dot product (see GROWTH TESTS;
+#       acos' slope is 1 / sin psi, and no worse than sqrt(2 D) at its ends), ACOS_ABS = 16 u: acos_r's stated truncation
+#       2e-8 (pstat_math.h) plus eight roundings of a number below 4; the sum of n - 1 angles is re-derived when a launch
+#       starts and then carries the differences of at most 4 bonds, old and new, per accepted step: sum e_psi + 8 a max e_psi;
+#       the same e_psi reaches U through the bending energy kappa / 2 (psi - psi0)^2: kappa |psi - psi0| e_psi per bond, summed for
+#       the re-derivation, and 4 a times the largest such sum so far for the carried differences (a bound on any 4 bonds);
+#     the weight: its relative error is the absolute error of wrel,
+#       e_w = wscale e_usum + 4 u |wrel| + 2 u:  e_usum the f32 sum(u), re-derived at launch start, then one f32 difference per
+#       accepted step: e_usum = (2 + a) K_TOTALS u sum |terms| + (n + 2 a) K_ABS u c1 on the terms of sum(u).  The CARRIED
+#       TOTALS form with its re-derivation counted as it is made (read in the kernels): <= 8 u on each f32 term, then an f64
+#       sum (refresh_totals of the chain-per-lane kernels) or an f32 wave sum of at most 8 partial sums per lane and 6
+#       butterfly levels (the all-pairs kernels), then the cast: <= 23 u sum |terms| < 2 K_TOTALS u sum |terms|, not n times
+#       that.  (The totals r, p, U keep the (a + n) of check (b): U's pair part is an f32 sum of n^2 / 2 terms.)
+#       The difference usum - uref, the product with wscale and the product with log2(e) inside __expf: one rounding each
+#       on |wrel|, with one in hand; v_exp_f32 1 ulp = 2 u.
+#       |wrel| <= the range of L over the prefix, since the gauge is the L of a configuration of the prefix (or the start);
+#     the product wgt * v [* v]: 2 u.
+#   Per block: up to `block` f32 additions on numbers no larger than the block's sum |wgt v|: block u sum |wgt v|
+#     (block = 128 in a long launch, 64 in launches of 64, 1 in the stepped handle).
+#   At the flush: f32 -> f64 is exact; the f64 addition 2^-52 per block; sweep_kernel<float> carries r in units of b and
+#     rescales its accumulators by (float) b and (float) b * (float) b: 2 u and 4 u.  Stated for every kernel: RESCALE = 4 u.
+#   A gauge rise multiplies what was recorded by e^-wrel: the (float) factor 1 u, the error 4 u |wrel| of its exponent, with
+#     one in hand; each rise lifts the gauge by more than 29, so a prefix has seen at most G = floor(range / 29) of them:
+#     G (4 u range + 2 u) on everything recorded before.
+#   v_exp_f32 returns 0 below 2^-126 (of the gauged weight), and an accumulator times (float) e^-wrel may fall there too:
+#     2^-126 e^(gauge - max L) per record, absolute.
+#   A ratio num / den with |d num| <= E_num, |d den| <= E_den:  |d (num / den)| <= (E_num + |num / den| E_den) / (den - E_den).
+FLUSH = 128
+K_COND = 144.0
+ACOS_ABS = 16 * U
+PSI_DOT = 2 * GROWTH_MARGIN
+RESCALE = 4 * U
+GAUGE_T = 30.0                # umbrella_logw's threshold for `float` (pstat_math.h)
+GAUGE_LIFT = 29.0             # every rise lifts the gauge by more than this
+# THE GAUGE CONTRACT: ln(device normaliser / N*) = (heaviest log-weight) - (gauge) <= GAUGE_T + margin.  The margin is derived,
+# per step: the error e_w of the wrel that the threshold test itself sees (a configuration may weigh e^(30 + e_w) without a
+# rise) plus the relative error of the normaliser, E_den / (den - E_den) of the bound above (ln(1 + x) <= x); record_bound returns
+# it.  It must stay far below 1 for the contract to say anything: the CPU test asserts GAUGE_MARGIN_MAX on every gauge-rise
+# row, the GPU test on every umbrella row.
+GAUGE_MARGIN_MAX = 0.125
+COLUMNS = ["r1", "r2", "r3", "r1sq", "r2sq", "r3sq", "rsq", "p1", "p2", "p3", "p1sq", "p2sq", "p3sq", "psq", "U", "Usq",
+           "cos2", "psi"]
+
+
+@dataclass
+class Rec:
+    """One recorded configuration of one chain: what record! adds, and the magnitudes the bound needs."""
+    v: np.ndarray              # r (3), p (3), U: oracle.chain_energy
+    ex: np.ndarray             # sum cos^2 theta, sum psi / (n - 1) (zeros for n = 1)
+    usum: float                # sum(us): the field terms, and in the clustering main the bending energies
+    lit: np.ndarray            # term_sums: sum |terms| of the seven
+    c1: np.ndarray             # term_sums: single-monomer coefficients of the seven
+    lit_us: float              # sum |terms| of usum
+    c1_us: float
+    cond_sum: float            # term_sums(conditioning=True)
+    cond_max: float
+    bend_pole: float           # sum over the bonds of kappa |psi - psi0| e_psi: what acos' slope does to the bending energy
+    psi_sum: float             # sum psi
+    epsi_sum: float            # sum over the bonds of e_psi
+    epsi_max: float
+
+
+def rec_of(ob, op, p: dict, phi, theta, cluster: bool, magnitudes: bool = True) -> Rec:
+    """One oracle.chain_energy call, the rest numpy f64 on the angles.  magnitudes = False leaves out term_sums (lit and c1 are
+    zero): enough for a configuration that only a wrong twin records."""
+    phi, theta = np.asarray(phi), np.asarray(theta)
+    n = len(phi)
+    Uv, r, pp = ob.chain_energy(op, phi, theta)
+    lit, c1, cond_sum, cond_max = term_sums(p, phi, theta, conditioning=True) if magnitudes else (np.zeros(7), np.zeros(7), 0.0, 0.0)
+    ct, st = np.cos(theta), np.sin(theta)
+    E0 = p["E0"]
+    if p["chain_type"] == DIELECTRIC:
+        K1, K2 = p.get("K1", 1.0), p.get("K2", 0.0)
+        muz = (K1 - K2) * E0 * ct * ct + K2 * E0
+        mu_c = abs((K1 - K2) * E0) + abs(K2 * E0)
+    else:
+        muz = p.get("mu", 1e-2) * ct
+        mu_c = abs(p.get("mu", 1e-2))
+    us = -0.5 * E0 * muz
+    usum, lit_us = float(us.sum()), float(np.abs(us).sum())
+    ex = np.zeros(2)
+    psi_sum = epsi_sum = epsi_max = bend_pole = 0.0
+    if cluster and n > 1:
+        nh = np.stack([np.cos(phi) * st, np.sin(phi) * st, ct], axis=1)
+        psi = np.arccos(np.clip((nh[:-1] * nh[1:]).sum(axis=1), -1, 1))
+        kappa = p.get("bend_mod", 0.0)
+        if kappa:
+            bend = kappa / 2 * (psi - p.get("bend_angle", 0.0)) ** 2
+            usum += float(bend.sum())
+            lit_us += float(np.abs(bend).sum())
+        ex[0], ex[1] = float((ct * ct).sum()), float(psi.sum() / (n - 1))
+        with np.errstate(divide="ignore"):
+            ep = np.minimum(math.sqrt(2 * PSI_DOT), PSI_DOT / np.sin(psi)) + ACOS_ABS
+        psi_sum, epsi_sum, epsi_max = float(psi.sum()), float(ep.sum()), float(ep.max())
+        bend_pole = float((abs(kappa) * np.abs(psi - p.get("bend_angle", 0.0)) * ep).sum())
+    return Rec(np.concatenate([r, pp, [Uv]]), ex, usum, lit, c1, lit_us, 0.5 * abs(E0) * mu_c, cond_sum, cond_max, bend_pole,
+               psi_sum, epsi_sum, epsi_max)
+
+
+def _columns(v7, ex):
+    """[T, 18]: the 16 observables in ABI order and the two extras, from [T, 7] and [T, 2]."""
+    r, pp, Uv = v7[:, 0:3], v7[:, 3:6], v7[:, 6:7]
+    return np.concatenate([r, r * r, (r * r).sum(axis=1, keepdims=True), pp, pp * pp, (pp * pp).sum(axis=1, keepdims=True),
+                           Uv, Uv * Uv, ex], axis=1)
+
+
+def _column_errors(v7, e7, eex):
+    sq = 2 * np.abs(v7) * e7 + e7 * e7
+    return np.concatenate([e7[:, 0:3], sq[:, 0:3], sq[:, 0:3].sum(axis=1, keepdims=True), e7[:, 3:6], sq[:, 3:6],
+                           sq[:, 3:6].sum(axis=1, keepdims=True), e7[:, 6:7], sq[:, 6:7], eex], axis=1)
+
+
+def _weighted_prefix(L, X):
+    """P[t] = sum over tau <= t of X[tau] e^(L[tau] - M[t]), M the running maximum of L: carried with the maximum factored out."""
+    out = np.empty_like(X, dtype=np.float64)
+    acc = np.zeros(X.shape[1])
+    m = -math.inf
+    for t in range(len(L)):
+        if L[t] > m:
+            acc *= math.exp(m - L[t]) if m > -math.inf else 0.0
+            m = L[t]
+        acc = acc + X[t] * math.exp(L[t] - m)
+        out[t] = acc
+    return out
+
+
+def _gauge(L, L0):
+    """The rising gauge restated on f64 log-weights: g[t] after record t, starting on the start configuration's L0."""
+    g = np.empty(len(L))
+    cur = L0
+    for t in range(len(L)):
+        if L[t] - cur > GAUGE_T:
+            cur = L[t]
+        g[t] = cur
+    return g
+
+
+@dataclass
+class Twin:
+    cols: np.ndarray           # [T, 18]: plain the running sums, umbrella the gauge-free ratios
+    nstar: np.ndarray | None   # umbrella, [T]: the normaliser over its heaviest record's weight
+    top: np.ndarray | None     # umbrella, [T]: the heaviest record's log-weight so far, gauged on the start configuration
+    rises: np.ndarray | None   # umbrella, [T]: how often the restated gauge has risen
+
+
+def record_twin(recs, s=None, usum0=None, wrong=None, trial=None, accepted=None) -> Twin:
+    """record! restated on `recs`, the configurations of one chain after each of its steps.  s: None (plain) or the umbrella
+    scale; usum0: usum of the start configuration (the device gauges a chain on it).
+    wrong: None, or one of the wrong twins that the bound must tell from the right one --
+      "W1"  the scale is s (1 + 2^-8);
+      "W2"  on a rejected step the trial is recorded (trial[t]: its Rec, accepted[t]: the step's outcome);
+      "W3"  the first record of every 128-step block is dropped;
+      "W4"  umbrella, clustering main: the two extra columns are not rescaled when the gauge rises."""
+    if wrong == "W2":
+        recs = [r if accepted[t] else trial[t] for t, r in enumerate(recs)]
+    V = _columns(np.array([r.v for r in recs]), np.array([r.ex for r in recs]))
+    keep = np.ones(len(recs))
+    if wrong == "W3":
+        keep[::FLUSH] = 0.0
+    if s is None:
+        return Twin(np.cumsum(V * keep[:, None], axis=0), None, None, None)
+    if wrong == "W1":
+        s = s * (1 + 2.0 ** -8)
+    L = -s * np.array([r.usum for r in recs])
+    P = _weighted_prefix(L, np.concatenate([V, np.ones((len(L), 1))], axis=1) * keep[:, None])
+    with np.errstate(invalid="ignore", divide="ignore"):
+        cols = P[:, :-1] / P[:, -1:]
+    L0 = -s * usum0
+    g = _gauge(L, L0)
+    M = np.maximum.accumulate(L)
+    if wrong == "W4":
+        # each record of the extras keeps the weight it had under the gauge of ITS time; the normaliser follows the gauge
+        ex = np.cumsum(V[:, 16:18] * np.exp(L - g)[:, None], axis=0)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            cols[:, 16:18] = ex / (P[:, -1:] * np.exp(M - g)[:, None])
+    rises = np.cumsum(np.diff(np.concatenate([[L0], g])) != 0)
+    return Twin(cols, P[:, -1], M - L0, rises)
+
+
+def _launch_max(x0, x, launch):
+    """Per step, the largest of x over the states its launch has passed through: the state the launch started from (x0 for the
+    first launch) and every state up to the step's own.  x: [T] or [T, k]; launch: steps per launch."""
+    x = np.asarray(x, dtype=np.float64)
+    full = np.concatenate([np.asarray(x0, dtype=np.float64)[None], x], axis=0)
+    out = np.empty_like(x)
+    for lo in range(0, len(x), launch):
+        hi = min(lo + launch, len(x))
+        out[lo:hi] = np.maximum.accumulate(full[lo:hi + 1], axis=0)[1:]
+    return out
+
+
+def record_bound(recs, n: int, acc_since_launch, block: int, s=None, usum0=None, start=None, launch=1):
+    """The bound of the derivation above on every prefix and column of record_twin(recs, s, usum0): [T, 18]; under
+    umbrella sampling also the margin [T] of the gauge contract (see GAUGE_MARGIN_MAX).  acc_since_launch[t]: the steps
+    accepted since the launch that recorded t began, t's own included.  start: the Rec of the configuration before the first
+    step; launch: steps per launch.  A carried difference passes through the totals and terms of the states it leaves as well
+    as of the state it reaches, so every magnitude of a carried term is the largest its launch has seen, the launch's starting
+    state included (found by check (d): a random start inside a repulsive contact, U = 7.2e6, left at step 1 -- the f32 U of
+    the next state carries the half ulp of 7.2e6)."""
+    start = recs[0] if start is None else start
+    a = np.asarray(acc_since_launch, dtype=np.float64)
+    T = len(recs)
+    v7 = np.array([r.v for r in recs])
+    V = _columns(v7, np.array([r.ex for r in recs]))
+    A = np.abs(V)
+    lit = np.array([r.lit for r in recs])
+    e7 = n * K_TOTALS * U * lit + a[:, None] * K_TOTALS * U * _launch_max(start.lit, lit, launch) + \
+        (n + 2 * a[:, None]) * K_ABS * U * np.array([r.c1 for r in recs])
+    cmax = _launch_max(max(start.cond_max, start.cond_sum), np.array([max(r.cond_max, r.cond_sum) for r in recs]), launch)
+    e7[:, 6] += K_COND * U * (np.array([r.cond_sum for r in recs]) + 4 * a * cmax)      # PAIR CONDITIONING
+    bp = np.array([r.bend_pole for r in recs])
+    e7[:, 6] += bp + 4 * a * _launch_max(start.bend_pole, bp, launch)      # the bending energy through acos (see the extras)
+    e_c2 = (a + n) * K_TOTALS * U * V[:, 16] + (n + 2 * a) * K_ABS * U
+    emax = _launch_max(start.epsi_max, np.array([r.epsi_max for r in recs]), launch)   # a difference takes the old bond and the new
+    e_psi = (np.array([r.epsi_sum for r in recs]) + 8 * a * emax +
+             (a + n) * K_TOTALS * U * _launch_max(start.psi_sum, np.array([r.psi_sum for r in recs]), launch)) / max(n - 1, 1)
+    EV = _column_errors(v7, e7, np.stack([e_c2, e_psi], axis=1))
+    common = block * U + RESCALE + 2.0 ** -52
+    if s is None:
+        return np.cumsum(EV + 2 * U * A, axis=0) + common * np.cumsum(A, axis=0), None
+    L = -s * np.array([r.usum for r in recs])
+    L0 = -s * usum0
+    M = np.maximum.accumulate(np.maximum(L, -math.inf))
+    span = np.maximum(M, L0) - np.minimum(np.minimum.accumulate(L), L0)
+    lit_us = np.array([r.lit_us for r in recs])
+    e_us = 2 * K_TOTALS * U * lit_us + a * K_TOTALS * U * _launch_max(start.lit_us, lit_us, launch) + \
+        (n + 2 * a) * K_ABS * U * np.array([r.c1_us for r in recs])
+    ew = s * e_us + 4 * U * span + 2 * U
+    X = np.concatenate([A, EV + A * (ew[:, None] + 2 * U), np.ones((T, 1)), (ew + U)[:, None]], axis=1)
+    P = _weighted_prefix(L, X)
+    Pabs, Perr, den, Pew = P[:, :18], P[:, 18:36], P[:, 36], P[:, 37]
+    rises = np.floor(span / GAUGE_LIFT)
+    shared = (common + rises * (4 * U * span + 2 * U))[:, None]
+    tiny = 2.0 ** -126 * np.exp(np.minimum(_gauge(L, L0) - M, 600.0))
+    E_num = Perr + shared * Pabs + (tiny * np.arange(1, T + 1))[:, None] * np.maximum.accumulate(A, axis=0)
+    E_den = Pew + shared[:, 0] * den + tiny * np.arange(1, T + 1)
+    ratio = record_twin(recs, s, usum0).cols
+    with np.errstate(invalid="ignore", divide="ignore"):
+        B = (E_num + np.abs(ratio) * E_den[:, None]) / (den - E_den)[:, None]
+    return B, E_den / (den - E_den) + np.maximum.accumulate(ew)
+
+
+def first_violation(got, want, bound, steps=None, first_column=0):
+    """(worst error / bound, message or None): the first row at which a column leaves its bound.  steps: the 1-based step of
+    every row (default: row + 1); first_column: COLUMNS index of column 0."""
+    err = np.abs(got - want)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        q = np.where(bound > 0, err / bound, np.where(err > 0, np.inf, 0.0))
+    q = np.where(np.isfinite(got) & np.isfinite(want), q, np.inf)
+    bad = np.argwhere(q > 1.0)
+    if len(bad) == 0:
+        return float(q.max()) if q.size else 0.0, None
+    t, k = bad[0]
+    step = t + 1 if steps is None else steps[t]
+    return float(q.max()), (f"step {step}, column {COLUMNS[first_column + k]}: got {got[t, k]!r}, twin {want[t, k]!r}, "
+                            f"error / bound {q[t, k]:.3g}")

@@ -23,6 +23,24 @@ Per configuration, besides the per-step comparison:
           that derivation, not a carried difference.
   (c) the tally agree / undecided / wrong; any wrong step fails, and so does an undecided share above 0.5 %;
   the same recorded steps judged by a judge whose E0 is multiplied by 1 + 2^-8 must show at least one wrong step.
+  (d) THE RECORD.  Every step, accepted or not, adds the current r, p, U and their squares (the clustering main also
+      sum cos^2 theta and <psi>) to f32 block accumulators that are folded into the f64 `sums`.  step_judge.record_twin restates
+      record! in numpy f64 on the stepped handle's own states (one oracle.chain_energy call per judged chain and step);
+      step_judge.record_bound is the derived bound (carried-value error, the weight's error, the block's f32 additions, the
+      flush and its rescale by b, the gauge rises).  Compared, for every judged chain:
+        the stepped handle after every step: `sums` (and chain_extras) against the twin's prefix, normalizer == steps_recorded;
+        the long launch of (a), T steps in one launch across FLUSH blocks and adaptation windows: its final sums, under the
+          bound with 128-record blocks and every acceptance of the launch carried;
+        the handle of (b) after each launch of 64.
+      The first step at which a column leaves its bound is reported: chain, step, column, error / bound.
+The configurations with umbrella=1 (step_judge._umbrella_configs) go through all of it.  (a) still demands bit-equal angles,
+generator words, nacc_total and step sizes: the weight enters a decision through du of the step, not through the carried
+usum.  Under (d) the gauge-free ratios sums / normalizer are compared with the twin's, and THE GAUGE CONTRACT is asserted at
+every step of the stepped handle: ln(normalizer / N*) <= 30 + margin, N* the twin's normaliser over its heaviest record's
+weight, 30 umbrella_logw's threshold for `float`, the margin derived (step_judge.GAUGE_MARGIN_MAX); averages and
+normaliser finite and positive throughout.  On the gauge-rise rows the twin's heaviest record, gauged on the start, exceeds
+e^35: the contract can only hold there if the kernel raised the gauge, and that the twin says so is asserted too.
+Each configuration prints one line with the worst error / bound of (d): profiles/step_judge/record_judge.txt.
 The all-pairs configurations start extended (--x0) and must stay out of 1/r^3 contacts: every 25 steps the judged chains'
 smallest |x_i - x_j| is asserted to be at least CONTACT_DISTANCE b.
 """
@@ -62,8 +80,47 @@ def _check_adaptation(oracle, op, pre, post, t1, adaptive):
     assert got == (ps_, ts_, nacc, natt), (t1, got, (ps_, ts_, nacc, natt))
 
 
-def _judge_run(ps, oracle, cases, chains, precision, cluster, T, judged, kernel, not_kernel="", packed=None):
-    """cases: the option dicts of the handle's cases.  Returns the stepped handle's final per-chain states and the tally."""
+def _scale(p):
+    return sj.umbrella_scale(p) if p.get("umbrella") else None
+
+
+def _record_check(who, D, p, acc, block, launch, at, dev_sums, dev_norm, ncol, rise=False):
+    """(d) for one chain: the device's sums read after the steps `at` (0-based) against the twin's prefixes.  D: the stepped
+    handle's record of the chain (recs, usum0, start); acc, launch: record_bound's acc_since_launch and steps per launch.  Returns the worst error / bound of the
+    16 columns and of the extras."""
+    s = _scale(p)
+    at = np.asarray(at)
+    tw = sj.record_twin(D["recs"], s, D["usum0"])
+    B, margin = sj.record_bound(D["recs"], p["n"], acc, block, s, D["usum0"], D["start"], launch)
+    dev_sums, dev_norm = np.asarray(dev_sums)[:, :ncol], np.asarray(dev_norm)
+    if s is None:
+        assert np.array_equal(dev_norm, at + 1.0), f"{who}: normalizer {dev_norm[:4]} is not the number of steps recorded"
+        got = dev_sums
+    else:
+        assert np.all(np.isfinite(dev_norm) & (dev_norm > 0)) and np.all(np.isfinite(dev_sums)), f"{who}: sums or normalizer not finite"
+        got = dev_sums / dev_norm[:, None]
+        assert launch > 1 or margin[at].max() <= sj.GAUGE_MARGIN_MAX, (who, margin[at].max())      # (the stepped handle's margin)
+        over = np.log(dev_norm / tw.nstar[at]) - (sj.GAUGE_T + margin[at])
+        assert np.all(over <= 0), (f"{who}: step {at[np.argmax(over > 0)] + 1}: the heaviest record weighs e^"
+                                   f"{sj.GAUGE_T + margin[at][np.argmax(over > 0)] + over.max():.3f} of the gauge")
+        if rise:
+            assert tw.top.max() >= sj.RISE_MIN and tw.rises[-1] >= 1, (who, tw.top.max())
+    worst = []
+    for lo, hi in ((0, 16), (16, ncol)):
+        q, msg = sj.first_violation(got[:, lo:hi], tw.cols[at][:, lo:hi], B[at][:, lo:hi], at + 1, lo) if hi > lo else (0.0, None)
+        assert msg is None, f"{who}: {msg}"
+        worst.append(q)
+    return worst
+
+
+def _launch_accepts(accepted, every):
+    ca = np.cumsum(accepted)
+    return ca - np.concatenate([[0], ca])[(np.arange(len(ca)) // every) * every]
+
+
+def _judge_run(ps, oracle, cases, chains, precision, cluster, T, judged, kernel, not_kernel="", packed=None, rise=False):
+    """cases: the option dicts of the handle's cases.  Returns the handle's parameters, the stepped handle's final per-chain
+    states, its record per judged chain (for (d) on the other handles) and the worst error / bound of (d)."""
     pps = [_device_params(ps, p, chains, precision, cluster) for p in cases]
     ops = [sj.oracle_params(oracle, p) for p in cases]
     pert = [sj.perturbed(oracle, p) for p in cases]
@@ -79,6 +136,12 @@ def _judge_run(ps, oracle, cases, chains, precision, cluster, T, judged, kernel,
             assert info.packed_cases == packed, name
         pre = {c: e.chain_state(c) for c in judged}
         lag = {c: 0.0 for c in judged}
+        ncol = 18 if cluster else 16
+        data = {}
+        for c in judged:
+            k = c // chains
+            cur = sj.rec_of(oracle, ops[k], cases[k], pre[c]["phi"], pre[c]["theta"], cluster)
+            data[c] = dict(recs=[], acc=[], sums=[], norm=[], usum0=cur.usum, cur=cur, start=cur)
         for t in range(T):
             e.advance(1)
             for c in judged:
@@ -98,6 +161,13 @@ def _judge_run(ps, oracle, cases, chains, precision, cluster, T, judged, kernel,
                     if Vp.kind != "undecided" and (Vp.kind == "accept") != R.moved:
                         tally["wrong_perturbed"] += 1
                 _check_adaptation(oracle, ops[k], pre[c], post, t + 1, adaptive)
+                D = data[c]
+                if R.moved:
+                    D["cur"] = sj.rec_of(oracle, ops[k], cases[k], post["phi"], post["theta"], cluster)
+                D["recs"].append(D["cur"])
+                D["acc"].append(R.moved)
+                D["sums"].append(np.concatenate([post["sums"], e.chain_extras(c)["sums"]]) if cluster else post["sums"])
+                D["norm"].append(post["normalizer"])
                 tally["adapted"] += post["phi_step"] != pre[c]["phi_step"]
                 if R.moved:
                     # what the device's acceptor caches.  After a growth test within its margin the device may have grown
@@ -122,11 +192,18 @@ def _judge_run(ps, oracle, cases, chains, precision, cluster, T, judged, kernel,
     assert share <= 0.005, share
     assert tally["wrong_perturbed"] >= 1
     assert adaptive or tally["adapted"] == 0      # (the rule itself is asserted at every window end, above)
-    return pps, final
+    worst = np.zeros(2)
+    for c in judged:       # (d), the stepped handle: every launch is one step, one record, at most one acceptance
+        D = data[c]
+        D["acc"] = np.array(D["acc"], dtype=np.int64)
+        worst = np.maximum(worst, _record_check(f"stepped handle, chain {c}", D, cases[c // chains], np.ones(T), 1, 1, np.arange(T),
+                                                D["sums"], D["norm"], ncol, rise))
+    return pps, final, data, worst
 
 
-def _long_launch_equals_stepped(ps, pps, final, T):
-    """(a)"""
+def _long_launch_equals_stepped(ps, pps, final, T, data, cases, chains, cluster):
+    """(a), and (d) on the long launch: its final sums against the twin on the stepped handle's states."""
+    worst = np.zeros(2)
     with ps.Ensemble(pps if len(pps) > 1 else pps[0]) as e:
         e.advance(T)
         for c, want in enumerate(final):
@@ -134,12 +211,19 @@ def _long_launch_equals_stepped(ps, pps, final, T):
             assert np.array_equal(got["theta"], want["theta"]) and np.array_equal(got["phi"], want["phi"]), c
             assert np.array_equal(got["rng"], want["rng"]) and got["nacc_total"] == want["nacc_total"], c
             assert got["phi_step"] == want["phi_step"] and got["theta_step"] == want["theta_step"], c
+            if c in data:
+                D = data[c]
+                sums = np.concatenate([got["sums"], e.chain_extras(c)["sums"]]) if cluster else got["sums"]
+                worst = np.maximum(worst, _record_check(f"long launch, chain {c}", D, cases[c // chains], np.cumsum(D["acc"]), sj.FLUSH, T,
+                                                        [T - 1], [sums], [got["normalizer"]], 18 if cluster else 16))
+    return worst
 
 
-def _carried_totals(ps, oracle, pps, cases, chains, T, judged):
-    """(b)"""
+def _carried_totals(ps, oracle, pps, cases, chains, T, judged, data, cluster):
+    """(b), and (d) after each of its launches of 64"""
     ops = [sj.oracle_params(oracle, p) for p in cases]
     worst = 0.0
+    read = {c: dict(sums=[], norm=[]) for c in judged}
     with ps.Ensemble(pps if len(pps) > 1 else pps[0]) as e:
         nacc = {c: 0 for c in judged}
         for _ in range(max(1, T // 64)):
@@ -147,6 +231,8 @@ def _carried_totals(ps, oracle, pps, cases, chains, T, judged):
             for c in judged:
                 k = c // chains
                 st = e.chain_state(c)
+                read[c]["sums"].append(np.concatenate([st["sums"], e.chain_extras(c)["sums"]]) if cluster else st["sums"])
+                read[c]["norm"].append(st["normalizer"])
                 got = e.microstate(c)
                 U, r, p = oracle.chain_energy(ops[k], st["phi"], st["theta"])
                 lit, c1 = sj.term_sums(cases[k], st["phi"], st["theta"])
@@ -158,6 +244,20 @@ def _carried_totals(ps, oracle, pps, cases, chains, T, judged):
                 worst = max(worst, float((err / np.maximum(bound, 1e-300)).max()))
                 assert np.all(err <= bound), (c, got, want, err / bound)
     print(f"carried totals: worst error / bound {worst:.3f}")
+    wd = np.zeros(2)
+    for c in judged:
+        D = data[c]
+        at = 64 * np.arange(1, len(read[c]["norm"]) + 1) - 1
+        wd = np.maximum(wd, _record_check(f"launches of 64, chain {c}", D, cases[c // chains], _launch_accepts(D["acc"], 64), 64, 64, at,
+                                          read[c]["sums"], read[c]["norm"], 18 if cluster else 16))
+    return wd
+
+
+def _report(name, umbrella, stepped, long, by64):
+    what = "ratios" if umbrella else "sums"
+    print(f"\nrecord judge {name}: worst error / bound of the {what} -- stepped {stepped[0]:.3g}, long launch {long[0]:.3g}, "
+          f"launches of 64 {by64[0]:.3g}; of the extras -- stepped {stepped[1]:.3g}, long launch {long[1]:.3g}, "
+          f"launches of 64 {by64[1]:.3g}")
 
 
 @pytest.mark.parametrize("cfg", sj.CONFIGS, ids=sj.CONFIG_IDS)
@@ -165,20 +265,24 @@ def test_every_step_against_the_judge(ps, oracle, cfg, monkeypatch):
     for k, v in cfg.env.items():
         monkeypatch.setenv(k, v)
     judged = cfg.judged()
-    pps, final = _judge_run(ps, oracle, [cfg.params], cfg.chains, cfg.precision, cfg.cluster, cfg.T, judged, cfg.kernel,
-                            cfg.not_kernel)
-    _long_launch_equals_stepped(ps, pps, final, cfg.T)
-    _carried_totals(ps, oracle, pps, [cfg.params], cfg.chains, cfg.T, judged)
+    pps, final, data, w1 = _judge_run(ps, oracle, [cfg.params], cfg.chains, cfg.precision, cfg.cluster, cfg.T, judged, cfg.kernel,
+                                      cfg.not_kernel, rise=cfg.name in sj.RISE_IDS)
+    wl = _long_launch_equals_stepped(ps, pps, final, cfg.T, data, [cfg.params], cfg.chains, cfg.cluster)
+    w64 = _carried_totals(ps, oracle, pps, [cfg.params], cfg.chains, cfg.T, judged, data, cfg.cluster)
+    _report(cfg.name, cfg.params.get("umbrella"), w1, wl, w64)
 
 
-@pytest.mark.parametrize("precision,kernel", [(sj.F32, "sweep_kernel<float> [packed cases]"),
-                                              (sj.Q16, "sweep_kernel<float, q16 state> [packed cases]")], ids=["f32", "q16"])
-def test_every_step_against_the_judge_packed(ps, oracle, precision, kernel, monkeypatch):
+@pytest.mark.parametrize("precision,kernel,umbrella", [(sj.F32, "sweep_kernel<float> [packed cases]", 0),
+                                                       (sj.Q16, "sweep_kernel<float, q16 state> [packed cases]", 0),
+                                                       (sj.F32, "sweep_kernel<float> [packed cases]", 1)],
+                         ids=["f32", "q16", "f32-umbrella"])
+def test_every_step_against_the_judge_packed(ps, oracle, precision, kernel, umbrella, monkeypatch):
     """13 cases x 5 chains of different E0, Fz, kT in one packed handle: chains 63 and 64 sit in different workgroups and
     cases, chain 64 in a partial wave."""
     monkeypatch.setenv("PSTAT_PACK", "1")
-    cases = [dict(sj.PACKED_COMMON, seed=500 + i, **c) for i, c in enumerate(sj.PACKED_CASES)]
+    cases = [dict(sj.PACKED_COMMON, seed=500 + i, **c, **(dict(umbrella=1) if umbrella else {})) for i, c in enumerate(sj.PACKED_CASES)]
     judged = [0, 1, 63, 64]
-    pps, final = _judge_run(ps, oracle, cases, 5, precision, False, sj.PACKED_T, judged, kernel, packed=1)
-    _long_launch_equals_stepped(ps, pps, final, sj.PACKED_T)
-    _carried_totals(ps, oracle, pps, cases, 5, sj.PACKED_T, judged)
+    pps, final, data, w1 = _judge_run(ps, oracle, cases, 5, precision, False, sj.PACKED_T, judged, kernel, packed=1)
+    wl = _long_launch_equals_stepped(ps, pps, final, sj.PACKED_T, data, cases, 5, False)
+    w64 = _carried_totals(ps, oracle, pps, cases, 5, sj.PACKED_T, judged, data, False)
+    _report("packed-" + ("q16" if precision == sj.Q16 else "f32") + ("-umbrella" if umbrella else ""), umbrella, w1, wl, w64)
