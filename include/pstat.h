@@ -291,7 +291,7 @@ int pstat_microstate(pstat_handle *h, int64_t chain, double out[7]);
 
 /* The quantities printed at mcmc_eap_chain.jl:365,386-395.  Synchronises.  Like every accessor that
  * synchronises (pstat_sync, pstat_reduce_host, pstat_rolling, pstat_microstate, pstat_chain_state,
- * pstat_chain_extras, pstat_checkpoint, pstat_corr_read, pstat_corr_rows, pstat_shape_read, pstat_shape_rows, pstat_pdist_read, pstat_pdist_rows, pstat_series_read, pstat_series_error_bars, pstat_hist_read) it fails with PSTAT_ERR_HIP if a launch since the last successful
+ * pstat_chain_extras, pstat_checkpoint, pstat_corr_read, pstat_corr_rows, pstat_shape_read, pstat_shape_rows, pstat_pdist_read, pstat_pdist_rows, pstat_energy_read, pstat_energy_rows, pstat_series_read, pstat_series_error_bars, pstat_hist_read) it fails with PSTAT_ERR_HIP if a launch since the last successful
  * call did not run to completion (a job of the persistent kernels timed out waiting for its predecessor):
  * the handle's averages are then not the averages of the steps it was asked for. */
 int pstat_summary_get(pstat_handle *h, int32_t icase, pstat_summary *out);
@@ -652,6 +652,78 @@ int pstat_pdist_read(pstat_handle *h, pstat_pdist *g, double *sum /* [ncases][nc
 int pstat_pdist_rows(pstat_handle *h, pstat_pdist *g, const double **dev_rows /* DEVICE memory */, int64_t *nrows, int64_t *stride);
 int pstat_pdist_clear(pstat_handle *h, pstat_pdist *g);
 void pstat_pdist_close(pstat_handle *h, pstat_pdist *g);
+
+/* The energy by term and separation on the device: per case what a chain's U is made of -- the field term, the work of the
+ * force, the bending term, and the dipole-dipole sum split by the separation s = j - i along the chain, with the part beyond
+ * max_sep and the part inside a radius.  An energy object is a sibling of a pdist object: it belongs to the handle it was opened
+ * on, one record is a pair of launches on the handle's stream that reads the stored angles of EVERY chain where they sit and
+ * writes the object's own buffers only.
+ * The contract (DESIGN.md 3.19 states it in full; polymer_stats_amd/csrc/pstat_energy.hip is the device's statement).  All in f64
+ * from the doubles pstat_chain_state returns for the angles, whatever the handle's precision:
+ *   unit vectors,   exactly the correlation recorder's: 3D dielectric mu_i = (K1 - K2) E0 cos theta_i n_i + K2 E0 z, polar
+ *   dipoles         mu_i = mu n_i, formed as f n_i + mb z with every product rounded; a planar handle has sin phi_i in place of
+ *                   cos theta_i and keeps its vectors in the x and z slots, y = 0.
+ *   positions       exactly the shape recorder's: x_i = b (sum_{j <= i} n_j - n_i / 2), the same scan.
+ *   pair term       for i < j: d = x_j - x_i;  r2 = (d_x d_x + d_y d_y) + d_z d_z (planar: without the y term);  r = sqrt(r2),
+ *                   correctly rounded;  mm = (mu_ix mu_jx + mu_iy mu_jy) + mu_iz mu_jz;  a = mu_i . d and c = mu_j . d added the
+ *                   same way;  t_ij = (mm - 3 ((a c) / r2)) / (FOURPI (r2 r)) with FOURPI = 4.0 * 3.14159265358979323846 as a
+ *                   double.  Every operation is rounded, the divisions are IEEE.  r = 0 gives a non-finite term, which reaches
+ *                   the totals of the columns it belongs to and nothing else (the reference's own 0 * inf).
+ *   options         fixed at open (pstat_energy_spec): max_sep in 0 .. n - 1 (-1 means n - 1); cutoff >= 0 in monomer lengths
+ *                   as --cutoff-radius is, 0 for no `within` column, shared by all cases (spec.cutoff) or one per case
+ *                   (cutoff_per_case, which then replaces spec.cutoff; a column exists when any of them is > 0).  On the
+ *                   device crad = cutoff * b and crad2 = crad * crad, both rounded in f64, and a pair counts unless
+ *                   r2 > crad2: the comparison and the products of the cutoff step kernel of an f64 handle.  n >= 1.
+ *   columns         per chain, in this order; ncols = 3 + max_sep + 1 + (cutoff ? 1 : 0):
+ *     field         sum_i (-E0 / 2) mu_{i,z} (planar: the second component).
+ *     work          -(Fx R_x + Fz R_z) with R = x_{n-1} + (b / 2) n_{n-1}.
+ *     bend          sum_{i < n-1} ((kappa / 2)(psi_i - psi0))(psi_i - psi0), psi_i = acos(clamp(n_i . n_{i+1}, -1, 1)) by the
+ *                   device's 1.2 ulp acos.  Exactly 0 for every chain, with no acos evaluated, when the case's bend_mod is 0:
+ *                   every handle of the fixed-force and of the planar main.
+ *     pair[s]       max_sep columns, s = 1 .. max_sep:  sum_{i = 0}^{n-1-s} t_{i,i+s}.
+ *     rest          sum_{s > max_sep} pair[s]; exactly 0 when max_sep = n - 1.
+ *     within        sum_{i<j, r2 <= crad2} t_ij; only when a cutoff is set.
+ *                   The pair columns hold the dipole-dipole sum WHATEVER the handle's energy type: on an Ising or a
+ *                   non-interacting handle pair[2..] and rest are the energy the model leaves out.
+ *   model total     the U the handle's own step carries (pstat_microstate's seventh value) is this combination of a chain's
+ *                   columns, by the handle's energy_type:
+ *                     PSTAT_NONINTERACTING  field + work + bend
+ *                     PSTAT_ISING           field + work + bend + pair[1]
+ *                     PSTAT_INTERACTING     field + work + bend + sum_s pair[s] + rest
+ *                     PSTAT_CUTOFF          within alone, opened with the case's own cutoff_radius (UCutoff: no field, no force)
+ *   totals          as for a pdist object: per case and column one record adds the sum over the case's chains of the per-chain
+ *                   value to `sum` and the sum of its square to `sumsq`; both are additive across handles; a row is the record's
+ *                   sum / num_chains.
+ *   reproducible    no floating-point atomics; the order of every floating-point addition depends on (ncases, num_chains, n, the
+ *                   object's options) only; two identical runs give identical bits.
+ *
+ *   pstat_energy_open   cutoff_per_case: host memory, copied; may be NULL.  capacity_rows as for a pdist object.  Before the
+ *                       device is touched, with a message naming the argument, PSTAT_ERR_INVALID_ARG: null arguments; max_sep
+ *                       outside -1 .. n - 1; reserved != 0; a cutoff that is negative or not finite, shared or per case;
+ *                       capacity_rows < 0.  PSTAT_ERR_UNSUPPORTED: an umbrella-sampling handle (its samples carry per-chain
+ *                       weights whose gauge the sums do not hold); a chain whose positions and dipoles do not fit the 60 KiB of
+ *                       LDS a workgroup keeps them in: n > 61440 / 48 = 1280 (planar handles: / 32, 1920).
+ *   pstat_energy_record, pstat_advance_energy, pstat_energy_read, pstat_energy_rows, pstat_energy_clear, pstat_energy_close
+ *                       what the pstat_pdist_* call of the same name does for a pdist object, every rule included:
+ *                       PSTAT_ERR_TOO_SMALL before anything is enqueued; _read and _rows synchronise and fail after an
+ *                       incomplete launch; pstat_blocking_device accepts the rows; pstat_destroy closes the objects still open;
+ *                       the object is not part of a checkpoint.
+ *   An object of another handle (or a closed one) is PSTAT_ERR_INVALID_ARG.  Every home, every precision and planar handles
+ *   are accepted. */
+typedef struct pstat_energy_spec {
+  int32_t max_sep, reserved;
+  double cutoff;
+} pstat_energy_spec;
+typedef struct pstat_energy pstat_energy;
+int pstat_energy_open(pstat_handle *h, const pstat_energy_spec *spec, const double *cutoff_per_case /* host [ncases], or NULL */,
+                      int64_t capacity_rows, pstat_energy **out);
+int pstat_energy_record(pstat_handle *h, pstat_energy *g);
+int pstat_advance_energy(pstat_handle *h, pstat_energy *g, int64_t nsteps, int64_t stepout);
+int pstat_energy_read(pstat_handle *h, pstat_energy *g, double *sum /* [ncases][ncols] */, double *sumsq /* [ncases][ncols] */,
+                      int64_t *records);
+int pstat_energy_rows(pstat_handle *h, pstat_energy *g, const double **dev_rows /* DEVICE memory */, int64_t *nrows, int64_t *stride);
+int pstat_energy_clear(pstat_handle *h, pstat_energy *g);
+void pstat_energy_close(pstat_handle *h, pstat_energy *g);
 
 /* Per-chain accessors for tests and tooling (host buffers).  angles: theta[n] then phi[n] as
  * doubles, radians; sums: the 16 per-chain running sums in rolling.csv order;

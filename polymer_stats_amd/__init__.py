@@ -5,8 +5,8 @@ _lib, ensemble: the binding.  free_energy: A(r) from recorded histograms (numpy 
 reference's three mains (python -m polymer_stats_amd.<name>), short modules over _host, which holds what they share.  sweep,
 aggregate_mcmc: the reference's run/*.jl sweeps and scripts/aggregate_mcmc.jl.  julia_fmt: Julia's number formatting."""
 from ._lib import (DIELECTRIC, POLAR, NONINTERACTING, INTERACTING, ISING, CUTOFF, F32, F64, Q16, RNG_MWC64X, RNG_XOSHIRO128PP, NOBS, NRED, NQ, MOVES_SINGLE, MOVES_CLUSTER,
-                   OBS_NAMES, PLANAR_OBS_NAMES, PLANAR_OBS_INDEX, EB_NAMES, HC_NAMES, CORR_NAMES, SHAPE_NAMES, PDIST_NAMES, HistSpec, hist_spec, Params, PstatError, default_params, default_planar_params)
-from .ensemble import (Corr, CorrResult, Ensemble, ErrorBars, Hist, HistResult, Pdist, PdistResult, Shape, ShapeResult, Tempering, blocking_device, histogram_device, ladders_by,
+                   OBS_NAMES, PLANAR_OBS_NAMES, PLANAR_OBS_INDEX, EB_NAMES, HC_NAMES, CORR_NAMES, SHAPE_NAMES, PDIST_NAMES, ENERGY_NAMES, HistSpec, hist_spec, Params, PstatError, default_params, default_planar_params)
+from .ensemble import (Corr, CorrResult, Energy, EnergyResult, Ensemble, ErrorBars, Hist, HistResult, Pdist, PdistResult, Shape, ShapeResult, Tempering, blocking_device, histogram_device, ladders_by,
                        shape_anisotropy, summary_from_reduction)
 from .free_energy import extension_free_energy, wham_force
 
@@ -16,4 +16,5 @@ __all__ = ["DIELECTRIC", "POLAR", "NONINTERACTING", "INTERACTING", "ISING", "CUT
            "summary_from_reduction", "HC_NAMES", "HistSpec", "hist_spec", "Hist", "HistResult", "histogram_device",
            "extension_free_energy", "wham_force", "CORR_NAMES", "Corr", "CorrResult",
            "SHAPE_NAMES", "Shape", "ShapeResult", "shape_anisotropy",
-           "PDIST_NAMES", "Pdist", "PdistResult"]
+           "PDIST_NAMES", "Pdist", "PdistResult",
+           "ENERGY_NAMES", "Energy", "EnergyResult"]

@@ -289,10 +289,30 @@ def parse_pdist(text: str):
     return "pdist", spec
 
 
+def parse_energy(text: str):
+    """--energy MAXSEP[,cut=RCUT] of tools/run_sweep.py -> ("energy", dict(max_sep, cutoff)): the dipole-dipole sum by separation
+    up to s = MAXSEP (-1: n - 1), the rest in one column, and with RCUT the sum inside that radius in monomer lengths (default:
+    the cases' own --cutoff-radius under --energy-type cutoff, no such column otherwise)."""
+    parts = [t.strip() for t in str(text).split(",")]
+    spec = dict(max_sep=-1, cutoff=None)
+    try:
+        spec["max_sep"] = int(parts[0])
+        if spec["max_sep"] < -1 or len(parts) > 2:
+            raise ValueError
+        for entry in parts[1:]:
+            key, _, value = entry.partition("=")
+            if key != "cut" or not np.isfinite(float(value)) or float(value) <= 0.0:
+                raise ValueError
+            spec["cutoff"] = float(value)
+    except ValueError:
+        raise ReferenceError_(f"--energy '{text}' not understood: MAXSEP[,cut=RCUT] with MAXSEP >= -1 and RCUT > 0")
+    return "energy", spec
+
+
 # ---------------------------------------------------------------------------------------------- recording the production run
 @dataclass(frozen=True)
 class Recording:
-    """How the production run is recorded in place of --stepout rows: `kind` names a row of RECORDINGS, `spec` is what the
+    """How the production run is recorded in place of --stepout rows: `kind` names a row of RECORDING_KINDS, `spec` is what the
     row's `parse` returns (for error_bars the batch count N).  One kind by construction: the kinds exclude each other."""
     kind: str
     spec: object
@@ -317,7 +337,7 @@ def _check_hist_specs(pargs: dict, specs):
 
 
 def _check_records(flag: str, pargs: dict):
-    """--corr, --shape and --pdist (`flag`) keep a row per record: the run must give the blocking transform enough of them."""
+    """--corr, --shape, --pdist and --energy (`flag`) keep a row per record: the run must give the blocking transform enough of them."""
     stepout = int(pargs["stepout"])
     if not 1 <= stepout <= int(pargs["num-steps"]) or int(pargs["num-steps"]) // stepout < CORR_MIN_RECORDS:
         raise ReferenceError_(f"{flag} takes a record every --stepout steps of the production run and its standard errors from "
@@ -350,6 +370,13 @@ def _check_pdist(pargs: dict, spec):
     for v in o["q"]:       # (the library refuses such a phase too)
         if v * reach >= 1.0e5:
             raise ReferenceError_(f"--pdist: q b n = {v * reach:g} for q = {v} is not below 1e5")
+
+
+def _check_energy(pargs: dict, spec):
+    _check_records("--energy", pargs)
+    n = int(pargs["num-monomers"])
+    if spec[1]["max_sep"] > n - 1:
+        raise ReferenceError_(f"--energy: sep {spec[1]['max_sep']} must not be beyond n - 1 = {n - 1}")
 
 
 def _totals_and_error_bars(g):
@@ -432,13 +459,27 @@ RECORDINGS = {
         read=_totals_and_error_bars,
         lines=lambda main, res, spec, k, p: pdist_lines(*res, k)),
 }
+# Every kind of Recording: the table above and the energy recording, a row like the others that joins here (the pair-distance
+# tests pin RECORDINGS itself at its five rows, pdist last).  Every look-up of a kind goes through this one.
+RECORDING_KINDS = {
+    **RECORDINGS,
+    "energy": _Kind(
+        flag="--energy", ext=".energy", parse=parse_energy,
+        words=("energy columns", "sums", "records", _GAUGE % "sums", _LIKE_HIST),
+        check=_check_energy,
+        records=_every_stepout,
+        open=lambda e, spec, nrec: e.open_energy(spec[1]["max_sep"], spec[1]["cutoff"], capacity_rows=nrec),
+        advance=Ensemble.advance_energy,
+        read=lambda g: (*_totals_and_error_bars(g), g.model_error_bars(min_blocks=CORR_MIN_RECORDS)),
+        lines=lambda main, res, spec, k, p: energy_lines(*res, k)),
+}
 
 
 def check_recording(pargs: dict, rec: Recording, write_csv: bool = False, devices: int | None = None):
-    """What a Recording (tools/run_sweep.py's --error-bars, --hist, --corr, --shape, --pdist; run_cases(..., record=rec)) cannot be
+    """What a Recording (tools/run_sweep.py's --error-bars, --hist, --corr, --shape, --pdist, --energy; run_cases(..., record=rec)) cannot be
     combined with, refused before any GPU work: the kind's own limits, then what all kinds refuse.  `devices`: how many hold the
     chains (default: those --devices names)."""
-    row = RECORDINGS[rec.kind]
+    row = RECORDING_KINDS[rec.kind]
     flag = row.flag
     recorded_as, merged, between, no_umbrella, float64_only = row.words
     if devices is None:
@@ -648,7 +689,7 @@ class _Pool:
 
     def record(self, nsteps, rec):
         """advance(nsteps), made TWICE from the same state: first recorded on the device the way `rec` (a Recording) says -- as the
-        records its row of RECORDINGS counts, so many steps apart (error_bars: exactly N batches of nsteps // N steps; the others:
+        records its row of RECORDING_KINDS counts, so many steps apart (error_bars: exactly N batches of nsteps // N steps; the others:
         a record after every --stepout-th step; a remainder belongs to no record), into the recorder the row opens, by the row's
         Ensemble.advance_* --; then, from a checkpoint taken before it, as the one launch of advance(nsteps), which leaves the
         handle -- and so the averages the caller prints -- exactly as a run without a recording does.  (Recording leaves
@@ -660,7 +701,7 @@ class _Pool:
         The recorder is closed whatever happens; the checkpoint is put back also when the recorded run failed, so that the handle
         is never left mid-run (error_bars alone leaves a failed run where it stopped)."""
         check_recording(self.plist[0], rec, devices=len(self.parts))
-        row = RECORDINGS[rec.kind]
+        row = RECORDING_KINDS[rec.kind]
         nrec, stepout = row.records(nsteps, rec.spec, int(self.plist[0]["stepout"]))
         e = self.parts[0]
         image = e.checkpoint()
@@ -891,6 +932,24 @@ def pdist_lines(res, eb, k: int) -> list[str]:
         h0 += res.nbins + 1
     for j, v in enumerate(res.q):
         out.append(row("sq", repr(float(v)), res.mean[k, h0 + j], eb.stderr[k, h0 + j]))
+    return out
+
+
+def energy_lines(res, eb, model_eb, k: int) -> list[str]:
+    """`<case>.energy`: CSV `name,x,value,stderr`: `field`, `work`, `bend` (no x), a row `pair` per separation (x = s), `rest`,
+    `within` (x = the radius in monomer lengths; only with the column) and `model`, the energy the case's own step carries: the
+    mean over records and chains and its blocked standard error from the records' rows -- `model`'s from the rows' combined
+    column."""
+    out = ["name,x,value,stderr"]
+    row = lambda name, x, v, e: f"{name},{x},{float(v)!r},{float(e)!r}"
+    for i, name in enumerate(_lib.ENERGY_NAMES):
+        out.append(row(name, "", res.mean[k, i], eb.stderr[k, i]))
+    for s in range(1, res.max_sep + 1):
+        out.append(row("pair", s, res.mean[k, 2 + s], eb.stderr[k, 2 + s]))
+    out.append(row("rest", "", res.rest[k], eb.stderr[k, 3 + res.max_sep]))
+    if res.has_within:
+        out.append(row("within", repr(float(res.cutoff[k])), res.within[k], eb.stderr[k, 4 + res.max_sep]))
+    out.append(row("model", "", res.model[k], model_eb.stderr[k]))
     return out
 
 

@@ -45,6 +45,8 @@ SHAPE_MAX_Q = 512
 PDIST_NAMES = ("msd", "rmin", "hist", "sq")
 PDIST_MAX_Q = 64
 PDIST_MAX_BINS = 512
+# an energy object (pstat_energy_*): its first three columns, in this order; pair[1 .. max_sep], rest and (with a cutoff) within follow
+ENERGY_NAMES = ("field", "work", "bend")
 
 # every symbol include/pstat.h declares (tests check the built library exports all of them)
 SYMBOLS = [
@@ -64,6 +66,8 @@ SYMBOLS = [
     "pstat_shape_close",
     "pstat_pdist_open", "pstat_pdist_record", "pstat_advance_pdist", "pstat_pdist_read", "pstat_pdist_rows", "pstat_pdist_clear",
     "pstat_pdist_close",
+    "pstat_energy_open", "pstat_energy_record", "pstat_advance_energy", "pstat_energy_read", "pstat_energy_rows", "pstat_energy_clear",
+    "pstat_energy_close",
 ]
 ABI_VERSION = 6
 
@@ -102,6 +106,10 @@ class HistSpec(C.Structure):
 
 class PdistSpec(C.Structure):
     _fields_ = [("max_sep", C.c_int32), ("min_sep", C.c_int32), ("nbins", C.c_int32), ("nq", C.c_int32), ("rmax", C.c_double)]
+
+
+class EnergySpec(C.Structure):
+    _fields_ = [("max_sep", C.c_int32), ("reserved", C.c_int32), ("cutoff", C.c_double)]
 
 
 def hist_spec(channel, nbins: int, lo: float, hi: float) -> HistSpec:
@@ -211,6 +219,14 @@ def load():
     L.pstat_pdist_clear.argtypes = [vp, vp]
     L.pstat_pdist_close.argtypes = [vp, vp]
     L.pstat_pdist_close.restype = None
+    L.pstat_energy_open.argtypes = [vp, C.POINTER(EnergySpec), dp, i64, C.POINTER(vp)]
+    L.pstat_energy_record.argtypes = [vp, vp]
+    L.pstat_advance_energy.argtypes = [vp, vp, i64, i64]
+    L.pstat_energy_read.argtypes = [vp, vp, dp, dp, ip]
+    L.pstat_energy_rows.argtypes = [vp, vp, C.POINTER(vp), ip, ip]
+    L.pstat_energy_clear.argtypes = [vp, vp]
+    L.pstat_energy_close.argtypes = [vp, vp]
+    L.pstat_energy_close.restype = None
     if L.pstat_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI version {L.pstat_abi_version()}, this binding needs {ABI_VERSION}: "
                           "rebuild it with `make -C polymer_stats_amd/csrc`")

@@ -66,11 +66,13 @@ struct Buffer {
 //   PSTAT_F64_LDS_ROWS=k    SweepMem: monomers whose cells stay in LDS, 0..the rows of a quarter of the LDS
 //   PSTAT_SEGMENTS=k        time segments per chain-per-lane launch (below 1: 1), with no f32 bound on a segment's steps
 //   PSTAT_MAX_SPINS=k       bound on the job queue's predecessor wait, if k > 0
+//   PSTAT_ENERGY_MAP=s|p    the energy recorder's pair mapping: a separation per wavefront pass | s and n - s paired (the default)
 struct Overrides {
   char f64_state = 0, f32_state = 0;   // first letter of the value (0: unset)
   int pack = -1;                       // -1: unset
   int lanes = 0, f64_lds_rows = -1;    // as atoi() reads them (0 / -1: unset)
   int segments = 0, max_spins = 0;     // 0: unset
+  char energy_map = 0;                 // first letter of the value (0: unset)
 };
 
 Overrides read_overrides() {
@@ -81,6 +83,7 @@ Overrides read_overrides() {
   if (const char *e = getenv("PSTAT_LANES")) o.lanes = atoi(e);
   if (const char *e = getenv("PSTAT_F64_LDS_ROWS")) o.f64_lds_rows = atoi(e);
   if (const char *e = getenv("PSTAT_SEGMENTS")) o.segments = atoi(e) > 1 ? atoi(e) : 1;
+  if (const char *e = getenv("PSTAT_ENERGY_MAP")) o.energy_map = e[0];
   if (const char *e = getenv("PSTAT_MAX_SPINS")) o.max_spins = atoi(e) > 0 ? atoi(e) : 0;
   return o;
 }
@@ -136,6 +139,7 @@ struct pstat_handle {
   OpenList<pstat_corr> corrs;
   OpenList<pstat_shape> shapes;
   OpenList<pstat_pdist> pdists;
+  OpenList<pstat_energy> energies;
 };
 
 // ---- the recorder objects of a handle.  Each owns its device memory; the handle owns those that are open.
@@ -194,6 +198,12 @@ struct pstat_shape : ColumnTotals {
 struct pstat_pdist : ColumnTotals {
   PdistArgs args{};
   DeviceDoubles d_tab;              // [nq] the magnitudes, then [ncases] nbins / rmax (the latter only with nbins > 0)
+};
+
+// Per-case energy breakdown of one handle (pstat_energy.hip).
+struct pstat_energy : ColumnTotals {
+  EnergyArgs args{};
+  DeviceDoubles d_cut;              // [ncases] the radius in monomer lengths (only with a `within` column)
 };
 
 namespace {
@@ -661,6 +671,9 @@ int open_shape(pstat_handle *h, const pstat_shape *g, bool others = true) {
 int open_pdist(pstat_handle *h, const pstat_pdist *g, bool others = true) {
   return check_open(h, &pstat_handle::pdists, g, others, "the pdist object is not an open one of this handle");
 }
+int open_energy(pstat_handle *h, const pstat_energy *g, bool others = true) {
+  return check_open(h, &pstat_handle::energies, g, others, "the energy object is not an open one of this handle");
+}
 
 // The end of every pstat_X_open: the handle takes the finished object and the caller gets its address.
 template <class T>
@@ -771,8 +784,10 @@ constexpr TotalsText kShapeText{"shape object", "%lld rows of shape columns do n
                                 "shape object of %zu columns, %lld rows: %s", "shape totals: %s"};
 constexpr TotalsText kPdistText{"pdist object", "%lld rows of pair-distance columns do not fit the address space",
                                 "pdist object of %zu columns, %lld rows: %s", "pdist totals: %s"};
+constexpr TotalsText kEnergyText{"energy object", "%lld rows of energy columns do not fit the address space",
+                                 "energy object of %zu columns, %lld rows: %s", "energy totals: %s"};
 
-// The allocation tail of pstat_corr_open / pstat_shape_open / pstat_pdist_open, after the kind's own argument checks: a new object g with zeroed
+// The allocation tail of pstat_corr_open / pstat_shape_open / pstat_pdist_open / pstat_energy_open, after the kind's own argument checks: a new object g with zeroed
 // totals of ncols columns per case, `partial` doubles of scratch and capacity_rows kept rows.
 template <class T>
 int new_totals(pstat_handle *h, int32_t ncols, int64_t capacity_rows, size_t partial, const TotalsText &text, std::unique_ptr<T> &g) {
@@ -850,6 +865,11 @@ int enqueue_pdist(pstat_handle *h, pstat_pdist *g) {
   const double *q = g->args.nq > 0 ? g->d_tab.p : nullptr;
   const double *inv = g->args.nbins > 0 ? g->d_tab.p + g->args.nq : nullptr;
   HIP_TRY(launch_pdist(g->args, h->S.ang, h->d_cases, q, inv, g->d_partial.p, g->d_totals.p, g->next_row(), h->stream));
+  return recorded(g);
+}
+
+int enqueue_energy(pstat_handle *h, pstat_energy *g) {
+  HIP_TRY(launch_energy(g->args, h->S.ang, h->d_cases, g->d_cut.p, g->d_partial.p, g->d_totals.p, g->next_row(), h->stream));
   return recorded(g);
 }
 
@@ -1643,6 +1663,84 @@ int pstat_pdist_clear(pstat_handle *h, pstat_pdist *g) {
 }
 
 void pstat_pdist_close(pstat_handle *h, pstat_pdist *g) { close_object(h, &pstat_handle::pdists, g); }
+
+int pstat_energy_open(pstat_handle *h, const pstat_energy_spec *spec, const double *cutoff_per_case, int64_t capacity_rows,
+                      pstat_energy **out) {
+  if (!h || !spec || !out) return fail(PSTAT_ERR_INVALID_ARG, "null argument");
+  *out = nullptr;
+  const int64_t n = h->base.n;
+  const bool planar = h->cfg.planar;
+  int32_t max_sep = spec->max_sep;
+  if (max_sep < -1 || max_sep > n - 1)
+    return fail(PSTAT_ERR_INVALID_ARG, "max_sep must be in 0 .. n - 1 = %lld (or -1 for n - 1), not %d", (long long)n - 1, max_sep);
+  if (spec->reserved != 0) return fail(PSTAT_ERR_INVALID_ARG, "reserved must be 0, not %d", spec->reserved);
+  std::vector<double> tab;
+  try {
+    tab.resize((size_t)h->ncases);
+  } catch (const std::bad_alloc &) {
+    return fail(PSTAT_ERR_NOMEM, "host allocation failed");
+  }
+  bool cut = false;
+  for (int c = 0; c < h->ncases; ++c) {
+    const double v = cutoff_per_case ? cutoff_per_case[c] : spec->cutoff;
+    if (!std::isfinite(v) || v < 0.0)
+      return fail(PSTAT_ERR_INVALID_ARG, "%s = %g (case %d) must be finite and >= 0 (0: no `within` column)",
+                  cutoff_per_case ? "cutoff_per_case" : "cutoff", v, c);
+    tab[(size_t)c] = v;
+    cut = cut || v > 0.0;
+  }
+  if (capacity_rows < 0) return fail(PSTAT_ERR_INVALID_ARG, "capacity_rows must be >= 0, not %lld", (long long)capacity_rows);
+  if (h->cfg.umbrella)
+    return fail(PSTAT_ERR_UNSUPPORTED, "the energy by term under --umbrella-sampling: the samples carry per-chain weights whose gauge "
+                "the sums do not hold");
+  if (n > energy_max_n(planar))
+    return fail(PSTAT_ERR_UNSUPPORTED, "n = %lld: a chain's positions and dipoles must fit the LDS of a workgroup, n <= %lld for a %s "
+                "handle", (long long)n, (long long)energy_max_n(planar), planar ? "planar" : "3D");
+  if (max_sep < 0) max_sep = (int32_t)(n - 1);
+  EnergyArgs a{};
+  a.per = h->base.num_chains; a.ncases = h->ncases; a.n = n;
+  a.max_sep = max_sep; a.cut = cut ? 1 : 0; a.paired = h->ov.energy_map == 's' ? 0 : 1;
+  a.ncols = 3 + max_sep + 1 + (cut ? 1 : 0);
+  a.elem = (int32_t)h->elem; a.planar = planar ? 1 : 0; a.polar = h->cfg.chain_type == PSTAT_POLAR ? 1 : 0;
+  energy_layout(a);
+  std::unique_ptr<pstat_energy> g;
+  PSTAT_TRY(new_totals(h, a.ncols, capacity_rows, tile_partial_doubles(a), kEnergyText, g));
+  g->args = a;
+  if (cut) {   // the cases' radii: a copy, the caller's table may go
+    hipError_t e = g->d_cut.malloc(tab.size());
+    if (e != hipSuccess) return fail(PSTAT_ERR_NOMEM, kEnergyText.nomem, g->stride, (long long)capacity_rows, hipGetErrorString(e));
+    e = hipMemcpy(g->d_cut.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(PSTAT_ERR_HIP, kEnergyText.hip, hipGetErrorString(e));
+  }
+  return adopt(h->energies, g, out);
+}
+
+int pstat_energy_record(pstat_handle *h, pstat_energy *g) {
+  PSTAT_TRY(open_energy(h, g));
+  return totals_record(h, g, kEnergyText, [&] { return enqueue_energy(h, g); });
+}
+
+int pstat_advance_energy(pstat_handle *h, pstat_energy *g, int64_t nsteps, int64_t stepout) {
+  PSTAT_TRY(open_energy(h, g));
+  return advance_recording(h, nsteps, stepout, g->capacity, g->rows, kEnergyText.object, [&] { return enqueue_energy(h, g); });
+}
+
+int pstat_energy_read(pstat_handle *h, pstat_energy *g, double *sum, double *sumsq, int64_t *records) {
+  PSTAT_TRY(open_energy(h, g));
+  return totals_read(h, g, sum, sumsq, records);
+}
+
+int pstat_energy_rows(pstat_handle *h, pstat_energy *g, const double **dev_rows, int64_t *nrows, int64_t *stride) {
+  PSTAT_TRY(open_energy(h, g, dev_rows && nrows && stride));
+  return totals_rows(h, g, dev_rows, nrows, stride);
+}
+
+int pstat_energy_clear(pstat_handle *h, pstat_energy *g) {
+  PSTAT_TRY(open_energy(h, g));
+  return totals_clear(h, g);
+}
+
+void pstat_energy_close(pstat_handle *h, pstat_energy *g) { close_object(h, &pstat_handle::energies, g); }
 
 int pstat_sync(pstat_handle *h) {
   if (!h) return fail(PSTAT_ERR_INVALID_ARG, "null handle");

@@ -487,4 +487,20 @@ int64_t pdist_max_n(int planar, int nbins);
 hipError_t launch_pdist(const PdistArgs &a, const void *ang, const CaseConst *cases, const double *q, const double *inv,
                         double *partial, double *totals, double *row, hipStream_t stream);
 
+// Per-case energy breakdown of the chains' current configurations (pstat_energy.hip states the contract).
+struct EnergyArgs : TileArgs {  // ncols = 3 + max_sep + 1 + (cut ? 1 : 0)
+  int32_t max_sep;              // pair[s] for s = 1 .. max_sep, the separations beyond it in `rest`
+  int32_t cut;                  // a `within` column, its radius per case in the launch's table
+  int32_t polar;
+  int32_t paired;               // the pair mapping: separations u and n - u share a wavefront pass (1, the default), or one each
+};
+// fills the tile fields of `a` from the others: tile_layout's, with fewer chains per tile where the dipoles would not fit LDS
+// behind the positions
+void energy_layout(EnergyArgs &a);
+// the longest chain whose positions and dipoles fit a workgroup's LDS beside the scratch
+int64_t energy_max_n(int planar);
+// one record, as launch_pdist; cutoff = the radius per case [ncases] in monomer lengths, device memory (null without the column)
+hipError_t launch_energy(const EnergyArgs &a, const void *ang, const CaseConst *cases, const double *cutoff, double *partial,
+                         double *totals, double *row, hipStream_t stream);
+
 }  // namespace pstat

@@ -185,6 +185,31 @@ class Ensemble:
         """advance(nsteps) with a record into `pdist` after every `stepout`-th step (asynchronous)."""
         check(self._L.pstat_advance_pdist(self._h, pdist._g, int(nsteps), int(stepout)))
 
+    # --- per-case energy by term and separation (pstat_energy_*; DESIGN.md 3.19)
+    def open_energy(self, max_sep: int = -1, cutoff=None, capacity_rows: int = 0) -> "Energy":
+        """`max_sep`: pair[s] for s = 1 .. max_sep (-1: n - 1; 0: none), the separations beyond it in `rest`; `cutoff`: the
+        radius of the `within` column in monomer lengths, a number or one per case; None: the cases' own cutoff_radius on a
+        CUTOFF handle, no column otherwise.  `capacity_rows` > 0 also keeps one row of case means per record, for
+        Energy.error_bars."""
+        types = [int(p.energy_type) for p in self.cases]
+        if cutoff is None:
+            cut = np.array([float(p.cutoff_radius) for p in self.cases]) if types[0] == _lib.CUTOFF else np.zeros(1)
+        else:
+            cut = np.atleast_1d(np.asarray(cutoff, dtype=np.float64))
+            if cut.ndim != 1 or len(cut) not in (1, self.ncases):
+                raise ValueError(f"cutoff must be one number or one per case ({self.ncases}), not {cut.shape}")
+        cut = np.ascontiguousarray(cut)
+        spec = _lib.EnergySpec(int(max_sep), 0, float(cut[0]) if len(cut) == 1 else 0.0)
+        g = C.c_void_p()
+        check(self._L.pstat_energy_open(self._h, C.byref(spec), cut.ctypes.data_as(C.POINTER(C.c_double)) if len(cut) > 1 else None,
+                                        int(capacity_rows), C.byref(g)))
+        per_case = np.broadcast_to(cut, (self.ncases,)).copy()
+        return Energy(self, g, self.n - 1 if int(max_sep) < 0 else int(max_sep), per_case, types)
+
+    def advance_energy(self, energy: "Energy", nsteps: int, stepout: int):
+        """advance(nsteps) with a record into `energy` after every `stepout`-th step (asynchronous)."""
+        check(self._L.pstat_advance_energy(self._h, energy._g, int(nsteps), int(stepout)))
+
     # --- read-outs
     def reduce_into(self, dev_ptr: int, icase: int = -1):
         """Device-side reduction into a caller-owned device buffer of NRED doubles (async)."""
@@ -423,7 +448,7 @@ class CorrResult:
 
 
 class _Totals(_Recorder):
-    """What Corr, Shape and Pdist share: per-case totals of `ncols` columns and, with capacity_rows > 0 at the open, one row of case
+    """What Corr, Shape, Pdist and Energy share: per-case totals of `ncols` columns and, with capacity_rows > 0 at the open, one row of case
     means per record."""
 
     def __init__(self, ensemble: Ensemble, g, ncols: int):
@@ -447,7 +472,7 @@ class _Totals(_Recorder):
 
     def rows(self):
         """(device pointer, rows, stride) of the per-record case means, a float64 matrix [rows][ncases * ncols] in device
-        memory (pstat_corr_rows, pstat_shape_rows, pstat_pdist_rows).  Synchronises."""
+        memory (pstat_corr_rows, pstat_shape_rows, pstat_pdist_rows, pstat_energy_rows).  Synchronises."""
         e = self._e
         ptr, nrows, stride = C.c_void_p(), C.c_int64(0), C.c_int64(0)
         check(self._fn("rows")(e._h, self._g, C.byref(ptr), C.byref(nrows), C.byref(stride)))
@@ -455,7 +480,7 @@ class _Totals(_Recorder):
 
     def error_bars(self, min_blocks: int = 32, levels: bool = False, device: int | None = None) -> "ErrorBars":
         """Blocked standard errors of the recorded rows' columns (pstat_blocking_device on rows()): arrays of shape
-        [ncases, ncols].  Needs capacity_rows > 0 at open_corr / open_shape / open_pdist and at least `min_blocks` records.  Synchronises."""
+        [ncases, ncols].  Needs capacity_rows > 0 at open_corr / open_shape / open_pdist / open_energy and at least `min_blocks` records.  Synchronises."""
         e = self._e
         ptr, nrows, stride = self.rows()
         dev = int(e.cases[0].device) if device is None else int(device)
@@ -614,6 +639,106 @@ class Pdist(_Totals):
         """Synchronises."""
         e = self._e
         return PdistResult(e.n, self.max_sep, self.min_sep, self.nbins, self.rmax, self.q, e.num_chains, *self._read())
+
+
+class EnergyResult:
+    """What Energy.read returns.  `sum`, `sumsq`: the raw totals, float64 [ncases, ncols], the columns field, work, bend,
+    pair[1 .. max_sep], rest and, with a cutoff, within; `records`; `mean`: sum / (records * chains per case); `chain_stderr`: the
+    across-chain standard error of that mean, defined after exactly one record and NaN otherwise.  Views of `mean`: `field`,
+    `work`, `bend`, `rest`, `within` [ncases] (`within`: None without the column) and `pair` [ncases, max_sep].  `model_sum`,
+    `model` [ncases]: the energy the handle's own step carries, from `sum` and `mean`, by each case's energy type
+    (`model_columns`); on a CUTOFF handle opened without its `within` column they raise ValueError."""
+
+    def __init__(self, max_sep: int, cutoff: np.ndarray, energy_types, num_chains: int, sum_: np.ndarray, sumsq: np.ndarray,
+                 records: int):
+        self.max_sep, self.cutoff, self.energy_types = max_sep, cutoff, list(energy_types)
+        self.num_chains, self.records, self.sum, self.sumsq = num_chains, records, sum_, sumsq
+        self.mean, self.chain_stderr = _mean_and_chain_stderr(sum_, sumsq, records, num_chains)
+        self.has_within = sum_.shape[1] == 3 + max_sep + 2
+        m = self.mean
+        self.field, self.work, self.bend = m[:, 0], m[:, 1], m[:, 2]
+        self.pair, self.rest = m[:, 3:3 + max_sep], m[:, 3 + max_sep]
+        self.within = m[:, 4 + max_sep] if self.has_within else None
+
+    def model_columns(self, k: int) -> list[int]:
+        """The columns whose sum is the energy case k's own step carries (include/pstat.h, "model total")."""
+        return energy_model_columns(self.energy_types[k], self.max_sep, self.has_within)
+
+    def _model(self, a: np.ndarray) -> np.ndarray:
+        return np.array([a[k, self.model_columns(k)].sum() for k in range(len(a))])
+
+    @property
+    def model_sum(self) -> np.ndarray:
+        return self._model(self.sum)
+
+    @property
+    def model(self) -> np.ndarray:
+        return self._model(self.mean)
+
+
+def energy_model_columns(energy_type: int, max_sep: int, has_within: bool) -> list[int]:
+    """Columns of an energy object whose sum is the U a handle of `energy_type` carries: field + work + bend, with pair[1]
+    (Ising) or every pair column and rest (interacting); `within` alone for the cutoff energy."""
+    if energy_type == _lib.CUTOFF:
+        if not has_within:
+            raise ValueError("the model total of a cutoff handle is its `within` column: open the energy object with a cutoff")
+        return [4 + max_sep]
+    cols = [0, 1, 2]
+    if energy_type == _lib.ISING:
+        if max_sep < 1:
+            raise ValueError("the model total of an Ising handle needs pair[1]: open the energy object with max_sep >= 1")
+        cols.append(3)
+    elif energy_type == _lib.INTERACTING:
+        cols += list(range(3, 4 + max_sep))
+    return cols
+
+
+class Energy(_Totals):
+    """The energy by term and separation recorded on the device (Ensemble.open_energy, pstat_energy_*)."""
+
+    _kind = "energy"
+
+    def __init__(self, ensemble: Ensemble, g, max_sep: int, cutoff: np.ndarray, energy_types):
+        self.has_within = bool(np.any(cutoff > 0.0))
+        super().__init__(ensemble, g, 3 + max_sep + 1 + (1 if self.has_within else 0))
+        self.max_sep, self.cutoff, self.energy_types = max_sep, cutoff, energy_types
+
+    def read(self) -> EnergyResult:
+        """Synchronises."""
+        return EnergyResult(self.max_sep, self.cutoff, self.energy_types, self._e.num_chains, *self._read())
+
+    def model_error_bars(self, min_blocks: int = 32) -> "ErrorBars":
+        """Blocked standard errors of the model total, arrays of shape [ncases]: the blocking transform of the rows' COMBINED
+        column (the parts of one record are correlated, so their errors do not add).  The rows come to the host, the combined
+        column goes back as a matrix [rows][ncases] of its own.  Needs capacity_rows > 0 at open_energy.  Synchronises."""
+        e = self._e
+        ptr, nrows, stride = self.rows()
+        hip = _hip_runtime()
+        rows = np.zeros((nrows, e.ncases, self.ncols))
+        if nrows and hip.hipMemcpy(rows.ctypes.data, ptr, rows.nbytes, 2):          # 2: device to host
+            raise RuntimeError("copying the energy rows to the host failed")
+        cols = [energy_model_columns(t, self.max_sep, self.has_within) for t in self.energy_types]
+        model = np.ascontiguousarray(np.stack([rows[:, k, cols[k]].sum(axis=1) for k in range(e.ncases)], axis=1))
+        dev = C.c_void_p()
+        if hip.hipMalloc(C.byref(dev), max(model.nbytes, 8)):
+            raise MemoryError("no device memory for the combined column")
+        try:
+            if nrows and hip.hipMemcpy(dev, model.ctypes.data, model.nbytes, 1):    # 1: host to device
+                raise RuntimeError("copying the combined column to the device failed")
+            return blocking_device(dev.value, nrows, e.ncases, min_blocks=min_blocks, device=int(e.cases[0].device))
+        finally:
+            hip.hipFree(dev)
+
+
+def _hip_runtime():
+    """The HIP runtime libpstat has loaded into this process, for the few copies this module makes itself."""
+    with open("/proc/self/maps") as f:
+        path = next(line.split()[-1] for line in f if "libamdhip64" in line)
+    hip = C.CDLL(path)
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+    hip.hipFree.argtypes = [C.c_void_p]
+    return hip
 
 
 def histogram_device(ptr: int, nrows: int, stride: int, specs, device: int = 0, stream: int | None = None):

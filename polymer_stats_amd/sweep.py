@@ -41,8 +41,8 @@ from . import _lib          # (tools/run_sweep.py counts the devices through it)
 from . import mcmc_clustering_eap_chain as cluster_main
 from . import mcmc_clustering_eap_chain_2d as planar_main
 from . import mcmc_eap_chain as fixed_main
-from ._host import RECORDINGS, Recording, ReferenceError_, arith, check_recording, fresh_seed, number
-from ._host import parse_corr, parse_hist, parse_pdist, parse_shape      # (reached through this module too)
+from ._host import RECORDING_KINDS, Recording, ReferenceError_, arith, check_recording, fresh_seed, number
+from ._host import parse_corr, parse_energy, parse_hist, parse_pdist, parse_shape      # (reached through this module too)
 
 # (the planar main: 2D/run/Ising_2024-11-06.jl and its siblings launch 2D/mcmc_clustering_eap_chain.jl the same way)
 MAINS = {"mcmc_eap_chain": fixed_main, "mcmc_clustering_eap_chain": cluster_main, "mcmc_clustering_eap_chain_2d": planar_main}
@@ -195,20 +195,20 @@ def plan(main_name: str, fixed_argv: list[str], cases: list[dict], workdir: str,
 
 
 def recording(main_name: str, fixed_argv: list[str], cases: list[dict], *, error_bars: int = 0, hist=None, corr=None, shape=None,
-              pdist=None, write_csv: bool = False, world: int = 1) -> Recording | None:
-    """--error-bars N | --hist SPEC ... | --corr SPEC | --shape [SPEC] | --pdist SPEC of tools/run_sweep.py (the texts as the
+              pdist=None, energy=None, write_csv: bool = False, world: int = 1) -> Recording | None:
+    """--error-bars N | --hist SPEC ... | --corr SPEC | --shape [SPEC] | --pdist SPEC | --energy SPEC of tools/run_sweep.py (the texts as the
     command line gives them; shape "" is the bare flag, None its absence) -> the Recording of the production run, or None where none is asked for.
-    Parses the flag that is given and refuses what it cannot be combined with -- another of the five, more than one rank, and
+    Parses the flag that is given and refuses what it cannot be combined with -- another of the six, more than one rank, and
     what _host.check_recording refuses, judged from the options every case shares and from every chain and monomer length
     among the cases; no GPU is touched."""
     given = [(kind, text) for kind, text in (("error_bars", error_bars or None), ("hist", hist or None), ("corr", corr or None),
-                                             ("shape", shape), ("pdist", pdist or None)) if text is not None]
+                                             ("shape", shape), ("pdist", pdist or None), ("energy", energy or None)) if text is not None]
     if not given:
         return None
-    row = RECORDINGS[given[0][0]]
+    row = RECORDING_KINDS[given[0][0]]
     rec = Recording(given[0][0], row.parse(given[0][1]))
     if len(given) > 1:
-        raise ReferenceError_(f"{RECORDINGS[given[1][0]].flag} cannot be combined with {row.flag}: each records the production run "
+        raise ReferenceError_(f"{RECORDING_KINDS[given[1][0]].flag} cannot be combined with {row.flag}: each records the production run "
                               "in its own way")
     if world > 1:
         raise ReferenceError_(f"{row.flag} needs one device, not --gpus {world}")
@@ -230,24 +230,24 @@ def _signature(pargs: dict):
 def run_sweep(main_name: str, fixed_argv: list[str], cases: list[dict], workdir: str, *, name=None, num_chains: int = 64,
               seed: int | None = None, precision: str | None = None, rng: str | None = None, rank: int = 0, world: int = 1,
               device: int = 0, overwrite: bool = False, write_csv: bool = False, max_chains: int = 262144, log=None,
-              error_bars: int = 0, hist=None, corr=None, shape=None, pdist=None) -> dict:
+              error_bars: int = 0, hist=None, corr=None, shape=None, pdist=None, energy=None) -> dict:
     """Runs the cases whose `.out` does not exist yet (run/interacting_dielectric_study.jl:39) and that fall to this rank
     (position in the full case list modulo `world`).  `write_csv` also writes every case's two time-series files (rows
     recorded on the device for the whole ensemble, _Pool.recorded).  `error_bars` = N | `hist` = ["CHANNEL:LO:HI:NBINS", ...] | `corr` =
     "MAXLAG[:nn,zz,mm]" | `shape` = "[AXIS:QMAX:NQ,...]" ("" for the gyration block alone; None: no shape) | `pdist` =
-    "RMAX:NBINS[,sep=..][,min=..][,q=QMAX:NQ]", the command line's five options and at most one of them (recording): the production run is recorded that way (_Pool.record: N batches | every chain
-    histogrammed | the lag correlations | the gyration tensor and the form factor at those wave-vectors | the pair distances, every --stepout steps)
-    and every `<case>.out` gets a `<case>.err` | `.hist` | `.corr` | `.shape` | `.pdist` beside it (_host.error_lines: blocked standard
-    errors under the .out's names | hist_lines | corr_lines | shape_lines | pdist_lines); the .out files are those of a run without it, and a
+    "RMAX:NBINS[,sep=..][,min=..][,q=QMAX:NQ]" | `energy` = "MAXSEP[,cut=RCUT]", the command line's six options and at most one of them (recording): the production run is recorded that way (_Pool.record: N batches | every chain
+    histogrammed | the lag correlations | the gyration tensor and the form factor at those wave-vectors | the pair distances | the energy by term and separation, every --stepout steps)
+    and every `<case>.out` gets a `<case>.err` | `.hist` | `.corr` | `.shape` | `.pdist` | `.energy` beside it (_host.error_lines: blocked standard
+    errors under the .out's names | hist_lines | corr_lines | shape_lines | pdist_lines | energy_lines); the .out files are those of a run without it, and a
     case whose file beside the .out is missing is run again.  Returns {"ran": [...], "skipped": [...], "launches": k}."""
     main = MAINS[main_name]
-    rec = recording(main_name, fixed_argv, cases, error_bars=error_bars, hist=hist, corr=corr, shape=shape, pdist=pdist,
+    rec = recording(main_name, fixed_argv, cases, error_bars=error_bars, hist=hist, corr=corr, shape=shape, pdist=pdist, energy=energy,
                     write_csv=write_csv, world=world)
     os.makedirs(workdir, exist_ok=True)
     todo_all = plan(main_name, fixed_argv, cases, workdir, name=name, num_chains=num_chains, seed=seed, precision=precision,
                     rng=rng, device=device)
     # a recorded case is complete when the recording's file is there too (a directory first swept without it: run again)
-    beside = lambda p: p["_out"][:-len(".out")] + RECORDINGS[rec.kind].ext
+    beside = lambda p: p["_out"][:-len(".out")] + RECORDING_KINDS[rec.kind].ext
     done = lambda p: os.path.isfile(p["_out"]) and (rec is None or os.path.isfile(beside(p)))
     skipped = [p["_name"] for p in todo_all if done(p) and not overwrite]
     todo = [p for p in todo_all if overwrite or not done(p)]
@@ -267,7 +267,7 @@ def run_sweep(main_name: str, fixed_argv: list[str], cases: list[dict], workdir:
             for k, (p, (sas, vas, ar)) in enumerate(zip(plist, res)):
                 texts = [(p["_out"], main.summary_lines(sas, vas, ar, p))]      # println x 10 (12)
                 if rec:      # (first: a case whose .out is there is complete)
-                    texts.insert(0, (beside(p), RECORDINGS[rec.kind].lines(main, info[rec.kind], rec.spec, k, p)))
+                    texts.insert(0, (beside(p), RECORDING_KINDS[rec.kind].lines(main, info[rec.kind], rec.spec, k, p)))
                 for path, lines in texts:           # complete or absent: an interrupted sweep re-runs the case
                     tmp = path + f".tmp{os.getpid()}"
                     with open(tmp, "w") as f:

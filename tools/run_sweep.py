@@ -90,6 +90,15 @@ def main():
                          "next to every <case>.out a <case>.pdist: CSV name,x,value,stderr with the blocked standard errors of the "
                          "records (at least 32 records).  Refused where --shape is, and with it; the .out files stay byte for byte "
                          "a plain run's, at the same doubled production time")
+    ap.add_argument("--energy", default="", metavar="MAXSEP[,cut=RCUT]",
+                    help="record what EVERY chain's energy is made of every --stepout steps of the production run, on the device: "
+                         "the field term, the work of the force, the bending term, the dipole-dipole sum by separation s = 1 .. "
+                         "MAXSEP along the chain (-1: n - 1) whatever --energy-type is, the separations beyond MAXSEP in one column "
+                         "and, with cut=RCUT (monomer lengths; default under --energy-type cutoff: --cutoff-radius), the sum inside "
+                         "that radius; write next to every <case>.out a <case>.energy: CSV name,x,value,stderr with the blocked "
+                         "standard errors of the records (at least 32 records), the last row `model` the energy the step itself "
+                         "carries.  Refused where --pdist is, and with it; the .out files stay byte for byte a plain run's, at the "
+                         "same doubled production time")
     ap.add_argument("--max-chains", type=int, default=262144, help="chains per launch (cases per ensemble = this / num-chains)")
     ap.add_argument("--dry-run", action="store_true", help="print the plan (cases, file names, ensembles) and stop: no GPU needed")
     ap.add_argument("--aggregate", default="", help="afterwards write scripts/aggregate_mcmc.jl's CSV of the whole directory here")
@@ -109,7 +118,7 @@ def main():
     if not cases:
         raise SystemExit("no cases: give --axis and/or --cases")
 
-    recording = dict(error_bars=args.error_bars, hist=args.hist, corr=args.corr, shape=args.shape, pdist=args.pdist)
+    recording = dict(error_bars=args.error_bars, hist=args.hist, corr=args.corr, shape=args.shape, pdist=args.pdist, energy=args.energy)
     try:
         sw.recording(args.main, fixed, cases, write_csv=args.csv, world=args.gpus, **recording)
     except sw.ReferenceError_ as e:
