@@ -34,6 +34,9 @@
 #ifndef PSTAT_GM_DEPTH
 #define PSTAT_GM_DEPTH 2   // prefetch depth (steps) of the f64 non-interacting sweep with its cells in memory: 2 or 3
 #endif
+#ifndef PSTAT_GM_LATE
+#define PSTAT_GM_LATE 1    // that sweep at depth 2: fetch the row of step s + 2 AFTER the stores of step s (one forwarded commit); 0: before
+#endif
 #ifndef PSTAT_GI_DEPTH
 #define PSTAT_GI_DEPTH 1   // prefetch depth (steps) of the f64 Ising sweep with its cells in memory
 #endif
@@ -308,6 +311,11 @@ __device__ __forceinline__ void run_segment(const SweepArgs &A, const DevState &
   // of bounds as well (gbase < 2^24), and as a forwarding tag it equals no cell.  The fill and the spill address `cells`
   // itself, not the resource: the bytes of row i stay at cells + i * row_bytes.
   constexpr bool AS = GM && !CC;
+  // LATE (the address-steered non-interacting step at depth 2, PSTAT_GM_LATE): step s still draws step s + 2 at its top but
+  // fetches that row directly AFTER its own stores.  A wave's ds_write -> ds_read and buffer_store -> buffer_load to one
+  // address are ordered by the hardware (LDS is in order; the vector-memory path is the one in-order vmcnt stream), so the
+  // fetched row already holds the commit of step s: only the commit of step s + 1 is left to forward.
+  constexpr bool LATE = AS && !GI && DEPTH == 2 && PSTAT_GM_LATE;
   constexpr uint32_t NOWHERE = 0xFFFFFFFFu;
   const uint32_t nL = GM ? (uint32_t)A.lds_rows : 0u;
   const uint32_t trash = nL * row_bytes + lane_bytes;        // LDS row nL: never read for its contents
@@ -326,7 +334,8 @@ __device__ __forceinline__ void run_segment(const SweepArgs &A, const DevState &
     }
     return r;
   };
-  // a fetched cell at its first use: its home, then the commits made after its load was issued (fw2 older, fw1 newer)
+  // a fetched cell at its first use: its home, then the commits made after its load was issued (fw2 older, fw1 newer;
+  // LATE: the load was issued behind the older one's stores, so fw1 alone)
   auto resolve = [&](const RowG &r, const uint32_t idx, const uint32_t cell, const Cell &f1, const uint32_t at1,
                      const Cell &f2, const uint32_t at2, const Cell &f3, const uint32_t at3) __attribute__((always_inline)) -> Cell {
     if constexpr (GM) {
@@ -339,7 +348,7 @@ __device__ __forceinline__ void run_segment(const SweepArgs &A, const DevState &
         const bool s3 = at3 == cell;
         a.x = s3 ? f3.x : a.x; a.y = s3 ? f3.y : a.y;
       }
-      if constexpr (DEPTH >= 2) {
+      if constexpr (DEPTH >= 2 && !LATE) {
         const bool s2 = at2 == cell;
         a.x = s2 ? f2.x : a.x; a.y = s2 ? f2.y : a.y;
       }
@@ -389,6 +398,9 @@ __device__ __forceinline__ void run_segment(const SweepArgs &A, const DevState &
   // every CU is issuing them (measured with a one-step pipeline: 27 % of the wave's cycles spent waiting).  A row is
   // therefore loaded BEFORE the stores of the two steps that precede its use; their committed cells are forwarded
   // into it at its first use (fw1 = previous step, fw2 = the one before; ~0 = no such cell).
+  // LATE: step s issues that load behind its own stores, so a row is loaded before the stores of ONE step that precedes its
+  // use, and fw1 is all there is to forward.  The two rows fetched here are loaded before any commit: step 0 forwards nothing
+  // (fw1_at = ~0) and step 1 forwards the commit of step 0, as every later step forwards its predecessor's.
   Draw dC = dA;
   Row aC = aA;
   Draw dD = dA;             // (a third step of depth, PSTAT_GM_DEPTH = 3: four sets, three forwarded commits)
@@ -485,11 +497,16 @@ __device__ __forceinline__ void run_segment(const SweepArgs &A, const DevState &
         aLo = resolve(a0_.lo, hasLo ? d.idx - 1 : d.idx, hasLo ? d.cell - row_bytes : d.cell, fw1_cell, fw1_at, fw2_cell, fw2_at, fw3_cell, fw3_at);
         aHi = resolve(a0_.hi, hasHi ? d.idx + 1 : d.idx, hasHi ? d.cell + row_bytes : d.cell, fw1_cell, fw1_at, fw2_cell, fw2_at, fw3_cell, fw3_at);
       } else if constexpr (GM) {
+        // LATE: the draws of step s + 2 up here, where the generator overlaps the old state's trigonometry; its row follows
+        // this step's commit, below
+        if constexpr (LATE) {
+          if (more) dn = draw_step<RARE>(g, (uint32_t)n, flips, row_bytes, lane_bytes);
+        }
         a0 = resolve(a0_, d.idx, d.cell, fw1_cell, fw1_at, fw2_cell, fw2_at, fw3_cell, fw3_at);
       } else {
         a0 = a0_;
       }
-      if (more) {
+      if (!LATE && more) {
         dn = draw_step<RARE>(g, (uint32_t)n, flips, row_bytes, lane_bytes);
         an = rdrow(dn);
         // keep the next row's read up here, a whole step ahead of its use: left alone, the scheduler sinks it
@@ -704,6 +721,15 @@ __device__ __forceinline__ void run_segment(const SweepArgs &A, const DevState &
       else { a1.x = ok ? th1 : th0; a1.y = ok ? ph1 : ph0; }
       if constexpr (GM) { Cell t1; t1.x = th1; t1.y = ph1; wr(d, t1, ok); }   // (steered away unless accepted)
       else wr(d, a1, ok);
+      if constexpr (LATE) {
+        if (more) {
+          // the row of step s + 2, behind the stores of step s: fenced on both sides, so that the scheduler neither lifts it
+          // over them (it would miss this commit) nor sinks it toward its use (see the barrier above)
+          __builtin_amdgcn_sched_barrier(0);
+          an = rdrow(dn);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
       const R m = ok ? (R)1 : (R)0;
       const P mm = {m, m};
       if constexpr (sizeof(R) == 8) {  // the oracle's update order: r += b*dn, p += dm, U += dU
@@ -724,8 +750,10 @@ __device__ __forceinline__ void run_segment(const SweepArgs &A, const DevState &
       if constexpr (EN == PSTAT_ISING) nnan_seg += not_finite(dU) ? 1 : 0;
       if constexpr (GM) {
         // (a rejected step changed nothing in memory: it forwards nothing, so the trial angles need no select here)
-        fw3_cell = fw2_cell; fw3_at = fw2_at;
-        fw2_cell = fw1_cell; fw2_at = fw1_at;
+        if constexpr (!LATE) {
+          fw3_cell = fw2_cell; fw3_at = fw2_at;
+          fw2_cell = fw1_cell; fw2_at = fw1_at;
+        }
         fw1_cell.x = th1; fw1_cell.y = ph1; fw1_at = ok ? d.cell : ~0u;
       } else if (more) {  // forward the accepted angles into the prefetched row if it is the same monomer
         const bool same = dn.cell == d.cell;
@@ -779,6 +807,13 @@ __device__ __forceinline__ void run_segment(const SweepArgs &A, const DevState &
       // exactly how many younger operations are in flight, or it ends up waiting for the previous step's STORE as well.
       // The main loop therefore prefetches unconditionally and the segment's last steps run in the tail.
       // (`more` of a step = a step two after it exists in this segment; the main loop covers only such steps)
+      // In flight at the first use of row(s), oldest first -- each step issues one ds + one buffer operation of either kind:
+      //   load -> store (PSTAT_GM_LATE = 0):  L(s) S(s-2) L(s+1) S(s-1)   => up to three younger: vmcnt(3) lgkmcnt(3), one or
+      //                                                                      two fewer where the scheduler has let the wait pass a store
+      //   store -> load (LATE):               L(s) S(s-1) L(s+1)          => two younger, always: vmcnt(2) lgkmcnt(2) -- the wait of
+      //                                                                      step s stands right behind the fenced S(s-1) L(s+1) pair
+      // (LATE: L(s) went out in step s - 2 behind S(s-2); L(s+2) follows S(s) further down.)  The compiler counts them itself as
+      // long as the 3-step body stays one basic block: its three s_waitcnt are these, one per step, nothing else waits.
       if constexpr (DEPTH == 3) {
         const int lim = chunk < left - 3 ? chunk : left - 3;
         for (; k + 4 <= lim; k += 4) {
