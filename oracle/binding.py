@@ -63,6 +63,12 @@ class EapStepOut(C.Structure):
                 ("U_cur", C.c_double), ("U_trial", C.c_double), ("usum_cur", C.c_double), ("usum_trial", C.c_double)]
 
 
+class EapReinitOut(C.Structure):
+    _fields_ = [("rng", C.c_uint32 * 4), ("adopt", C.c_int32), ("pad_", C.c_int32), ("eps", C.c_double), ("d", C.c_double),
+                ("lag_out", C.c_double), ("U_cur", C.c_double), ("U_fresh", C.c_double), ("usum_cur", C.c_double),
+                ("usum_fresh", C.c_double), ("mag", C.c_double)]
+
+
 def build(force: bool = False) -> str:
     src = os.path.join(HERE, "eap_oracle.c")
     if force or not os.path.exists(LIB_PATH) or \
@@ -110,6 +116,8 @@ def lib():
         L.eap_step_judge.restype = C.c_int
         L.eap_step_judge_cluster.argtypes = L.eap_step_judge.argtypes + [dp, C.c_int64]
         L.eap_step_judge_cluster.restype = C.c_int
+        L.eap_reinit_judge.argtypes = [C.POINTER(EapParams), dp, dp, up, C.c_double, C.c_int, dp, dp, C.POINTER(EapReinitOut), dp, dp]
+        L.eap_reinit_judge.restype = C.c_int
         L.eap_seed_state.argtypes = [C.POINTER(EapParams), C.c_uint64, up, dp, dp]
         L.eap_seed_state.restype = None
         L.eap_adapt.argtypes = [C.POINTER(EapParams), C.c_int64, dp, dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -338,6 +346,50 @@ def step_judge(params: EapParams, phi, theta, rng, phi_step: float, theta_step: 
                 log_alpha=out.log_alpha, U_cur=out.U_cur, U_trial=out.U_trial, usum_cur=out.usum_cur,
                 usum_trial=out.usum_trial, trial_phi=tphi, trial_theta=tth,
                 grow=grow[:out.ngrow])
+
+
+@dataclass
+class Reinit:
+    """One judged re-init (eap_reinit_out): see oracle/eap_oracle.h for the meaning of every field."""
+    rng: np.ndarray            # generator words after the draws
+    adopt: bool
+    forced: bool
+    eps: float
+    d: float
+    lag_in: float
+    lag_out: float
+    U_cur: float
+    U_fresh: float
+    usum_cur: float
+    usum_fresh: float
+    mag: float
+    fresh_phi: np.ndarray      # [n] the fresh configuration
+    fresh_theta: np.ndarray
+
+
+def reinit_judge(params: EapParams, phi, theta, rng, lag_in: float = 0.0, force: bool = False, fresh_to=None) -> Reinit:
+    """One re-init of the fixed-force main (mcmc_eap_chain.jl:352-361) from an explicit state, judged in f64.
+    fresh_to = (phi[n], theta[n]): angles that stand in for the fresh draw's (every word is still drawn)."""
+    n = params.n
+    phi = np.ascontiguousarray(phi, dtype=np.float64)
+    theta = np.ascontiguousarray(theta, dtype=np.float64)
+    assert phi.shape == (n,) and theta.shape == (n,)
+    words = (C.c_uint32 * 4)(*[int(w) for w in rng])
+    out = EapReinitOut()
+    fphi, fth = np.empty(n), np.empty(n)
+    dp = C.POINTER(C.c_double)
+    tp = tt = None
+    if fresh_to is not None:
+        keep = [np.ascontiguousarray(a, dtype=np.float64) for a in fresh_to]
+        assert keep[0].shape == (n,) and keep[1].shape == (n,)
+        tp, tt = keep[0].ctypes.data_as(dp), keep[1].ctypes.data_as(dp)
+    rc = lib().eap_reinit_judge(C.byref(params), phi.ctypes.data_as(dp), theta.ctypes.data_as(dp), words, float(lag_in),
+                                int(bool(force)), tp, tt, C.byref(out), fphi.ctypes.data_as(dp), fth.ctypes.data_as(dp))
+    if rc != 0:
+        raise RuntimeError(f"oracle returned {rc}")
+    return Reinit(rng=np.array(out.rng[:], dtype=np.uint32), adopt=bool(out.adopt), forced=bool(force), eps=out.eps, d=out.d,
+                  lag_in=float(lag_in), lag_out=out.lag_out, U_cur=out.U_cur, U_fresh=out.U_fresh, usum_cur=out.usum_cur,
+                  usum_fresh=out.usum_fresh, mag=out.mag, fresh_phi=fphi, fresh_theta=fth)
 
 
 def seed_state(params: EapParams, chain_id: int = 0):

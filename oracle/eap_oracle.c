@@ -26,7 +26,7 @@
  *   init    : phi_i = 2pi*u  for i = 1..n, then theta_i = pi*u for i = 1..n   (eap_chain.jl:6-7,61-62)
  *   step    : idx = mulhi32(w, n); dphi = phi_step*(2u-1); [flip bit = w>>31 if --do-flips];
  *             dtheta = theta_step*(2u-1); eps = u                              (mcmc_eap_chain.jl:277-287)
- *   re-init : 2n init draws, then eps = u unless --force-init                  (:353-358)
+ *   re-init : 2n init draws (always uniform: this main has no --x0), then eps = u unless --force-init   (:353-358)
  *   clustering main (eap_run_cluster), per step: idx, dphi, dtheta as above; then the cluster's draws --
  *             skip = u (no cluster if skip <= cluster_prob), then per round one draw for the link
  *             above the cluster while that end grows and one for the link below while that end grows
@@ -481,6 +481,35 @@ static void propose_single(const eap_params *P, uint32_t rng[5], const chain_t *
   pr->lower = pr->upper = pr->idx; pr->flipped = 0; pr->alpha = 1.0;
 }
 
+/* ------------------------------------------------------------------ re-initialisation
+ * mcmc_eap_chain.jl:352-361, stated once: the run loops below and the one-call judge (eap_reinit_judge) call these same
+ * functions.  The fixed-force main has no --x0: a fresh configuration is always the uniform draw of EAPChain(pargs). */
+
+static void fresh_random(const eap_params *P, uint32_t rng[5], chain_t *fresh) {
+  eap_params Q = *P;
+  Q.use_x0 = 0; Q.x0_vec = NULL; Q.x0_len = 0;
+  chain_random(&Q, rng, fresh);                                  /* :353 */
+}
+
+/* metropolis_acc, acceptance.jl:1-3, on the energies and the products of sin(theta) of both chains; eps is drawn unless the
+ * adoption is forced (:354-358) */
+static int reinit_adopt(const eap_params *P, uint32_t rng[5], int force, double U_cur, double U_fresh, double pa, double pb,
+                        double *eps_out) {
+  if (force) { if (eps_out) *eps_out = 0.0; return 1; }
+  const double eps = draw_u(rng);
+  if (eps_out) *eps_out = eps;
+  return eps <= (exp(-(U_fresh - U_cur) / P->kT) * pb / pa);
+}
+
+/* The reference's acceptor keeps the log pi it cached at the last acceptance: after an adoption its comparisons are offset
+ * by (cached log pi) - (log pi of the adopted chain) until the next accepted move. */
+static double reinit_lag(const eap_params *P, const weight_t *wf, double lag_in, double U_cur, double Om_cur, double usum_cur,
+                         double U_fresh, double Om_fresh, double usum_fresh) {
+  const double lp_old = -U_cur / P->kT + Om_cur + weight_eval(wf, usum_cur);
+  const double lp_new = -U_fresh / P->kT + Om_fresh + weight_eval(wf, usum_fresh);
+  return (lp_old + lag_in) - lp_new;
+}
+
 /* ------------------------------------------------------------------ faithful run */
 
 int eap_run_faithful(const eap_params *P, uint64_t chain_id, eap_result *out, eap_trace *tr) {
@@ -527,15 +556,11 @@ int eap_run_faithful(const eap_params *P, uint64_t chain_id, eap_result *out, ea
     /* re-initialisation, :352-361.  The reference also does it after the last init, where nothing
      * can observe it any more; skipped there so that `out` reports the last sampled microstate. */
     if (init == P->num_inits) break;
-    chain_random(P, rng, &fresh);
-    int adopt = P->force_init;
-    if (!adopt) {
-      double pa = 1.0, pb = 1.0;
-      for (int64_t i = 0; i < P->n; ++i) { pa *= cur.sth[i]; pb *= fresh.sth[i]; }
-      double eps = draw_u(rng);
-      adopt = eps <= (exp(-(fresh.U - cur.U) / P->kT) * pb / pa); /* acceptance.jl:1-3 */
-    }
-    if (adopt) { chain_t tmp = cur; cur = fresh; fresh = tmp; }  /* acceptor keeps its stale cache */
+    fresh_random(P, rng, &fresh);
+    double pa = 1.0, pb = 1.0;
+    for (int64_t i = 0; i < P->n; ++i) { pa *= cur.sth[i]; pb *= fresh.sth[i]; }
+    int adopt = reinit_adopt(P, rng, P->force_init, cur.U, fresh.U, pa, pb, NULL);
+    if (adopt) { chain_t tmp = cur; cur = fresh; fresh = tmp; }  /* acceptor keeps its stale cache (logpi_prev) */
   }
 
   memcpy(out->sum, A.sum, sizeof A.sum);
@@ -813,6 +838,43 @@ int eap_step_judge_cluster(const eap_params *P, const double *phi, const double 
   return step_judge(P, 1, phi, theta, rng, phi_step, theta_step, moved_to, out, trial_phi, trial_theta, grow, max_grow);
 }
 
+int eap_reinit_judge(const eap_params *P, const double *phi, const double *theta, const uint32_t rng_in[4], double lag_in,
+                     int force, const double *fresh_to_phi, const double *fresh_to_theta, eap_reinit_out *out,
+                     double *fresh_phi, double *fresh_theta) {
+  if (check_params(P) || !out) return -1;
+  if (P->energy_type == EAP_CUTOFF) return -1;   /* mcmc_eap_chain.jl has no UCutoff; the clustering main has no --num-inits */
+  uint32_t rng[5] = {rng_in[0], rng_in[1], rng_in[2], rng_in[3], (uint32_t)P->rng};
+  chain_t cur, fresh;
+  if (chain_alloc(&cur, P->n) || chain_alloc(&fresh, P->n)) return -2;
+  memcpy(cur.phi, phi, sizeof(double) * (size_t)P->n);
+  memcpy(cur.th, theta, sizeof(double) * (size_t)P->n);
+  chain_derive(P, &cur);
+  fresh_random(P, rng, &fresh);
+  if (fresh_to_phi && fresh_to_theta) {          /* a state on a lattice: every word is drawn, the angles are the caller's */
+    memcpy(fresh.phi, fresh_to_phi, sizeof(double) * (size_t)P->n);
+    memcpy(fresh.th, fresh_to_theta, sizeof(double) * (size_t)P->n);
+    chain_derive(P, &fresh);
+  }
+  double pa = 1.0, pb = 1.0, djac = 0.0;
+  for (int64_t i = 0; i < P->n; ++i) {
+    pa *= cur.sth[i]; pb *= fresh.sth[i];
+    djac += log(fresh.sth[i]) - log(cur.sth[i]);
+  }
+  out->adopt = reinit_adopt(P, rng, force, cur.U, fresh.U, pa, pb, &out->eps);
+  out->d = -(fresh.U - cur.U) / P->kT + djac;
+  const weight_t wf = weight_make(P, cur.Omega);
+  out->U_cur = cur.U; out->U_fresh = fresh.U;
+  out->usum_cur = sum_us(&cur); out->usum_fresh = sum_us(&fresh);
+  out->lag_out = out->adopt ? reinit_lag(P, &wf, lag_in, cur.U, log(pa), out->usum_cur, fresh.U, log(pb), out->usum_fresh)
+                            : lag_in;
+  out->mag = judge_mag(P, &cur, &fresh, 0, P->n - 1, 0.0, 0.0) + fabs(lag_in);
+  memcpy(out->rng, rng, sizeof out->rng);
+  if (fresh_phi) memcpy(fresh_phi, fresh.phi, sizeof(double) * (size_t)P->n);
+  if (fresh_theta) memcpy(fresh_theta, fresh.th, sizeof(double) * (size_t)P->n);
+  chain_free(&cur); chain_free(&fresh);
+  return 0;
+}
+
 void eap_seed_state(const eap_params *P, uint64_t chain_id, uint32_t rng[4], double *phi, double *theta) {
   uint32_t s[5];
   seed_chain(P, chain_id, s);
@@ -997,15 +1059,9 @@ int eap_run_fast(const eap_params *P, uint64_t chain_id, eap_result *out, eap_tr
     fast_random(P, rng, &fresh, &Om_new);
     for (int64_t i = 0; i < P->n; ++i) { pa *= c.sth[i]; pb *= fresh.sth[i]; }
     Om_old = log(pa);
-    int adopt = P->force_init;
-    if (!adopt) {
-      double eps = draw_u(rng);
-      adopt = eps <= (exp(-(fresh.U - c.U) / P->kT) * pb / pa);
-    }
+    int adopt = reinit_adopt(P, rng, P->force_init, c.U, fresh.U, pa, pb, NULL);
     if (adopt) {
-      double lp_old = -c.U / P->kT + Om_old + weight_eval(&wf, c.usum);
-      double lp_new = -fresh.U / P->kT + Om_new + weight_eval(&wf, fresh.usum);
-      lag = (lp_old + lag) - lp_new;
+      lag = reinit_lag(P, &wf, lag, c.U, Om_old, c.usum, fresh.U, Om_new, fresh.usum);
       fast_t tmp = c; c = fresh; fresh = tmp;
     }
   }

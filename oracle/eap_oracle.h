@@ -161,6 +161,30 @@ int eap_step_judge(const eap_params *P, const double *phi, const double *theta, 
 int eap_step_judge_cluster(const eap_params *P, const double *phi, const double *theta, const uint32_t rng[4],
                            double phi_step, double theta_step, const double *moved_to, eap_step_out *out, double *trial_phi,
                            double *trial_theta, double *grow, int64_t max_grow);
+/* --- the one-call re-init judge: mcmc_eap_chain.jl:352-361 from an explicit state, judged in f64 ---
+ * The run loops and this entry point share the functions that draw the fresh configuration, apply metropolis_acc
+ * (acceptance.jl:1-3) and form the acceptor's stale-cache offset.  Fixed-force main only: EAP_CUTOFF returns an error, and the
+ * clustering main has no --num-inits.  The fresh configuration is the uniform draw whatever P->use_x0 says (this main has no
+ * --x0). */
+typedef struct eap_reinit_out {
+  uint32_t rng[4];              /* generator words after the draws: 2n words, one more for eps unless forced */
+  int32_t adopt;                /* forced, or eps <= exp(-dU / kT) prod sin(theta') / prod sin(theta): the run loops' expression */
+  int32_t pad_;
+  double eps;                   /* (w >> 9) 2^-23; 0 when forced (no word drawn) */
+  double d;                     /* log pi(fresh) - log pi(current): -dU/kT + sum log sin(theta') - sum log sin(theta), both sides
+                                   fresh from the given angles; no umbrella weight (metropolis_acc has none) */
+  double lag_out;               /* (lp_cur + lag_in) - lp_fresh, lp = -U/kT + log prod sin(theta) [+ usum wscale under
+                                   P->umbrella]; lag_in when not adopted */
+  double U_cur, U_fresh;        /* energy.jl:7-23 of both chains */
+  double usum_cur, usum_fresh;  /* sum(us) of both chains */
+  double mag;                   /* 1 + sum |t| over EVERY term of both configurations (field, force, pair terms) over kT
+                                   + sum |log sin theta| of both + |lag_in| */
+} eap_reinit_out;
+/* fresh_to_phi / fresh_to_theta: NULL, or [n] angles that stand in for the fresh draw's (a state on a lattice: every word is
+ * still drawn).  fresh_phi / fresh_theta: [n] or NULL, the fresh configuration that was judged. */
+int eap_reinit_judge(const eap_params *P, const double *phi, const double *theta, const uint32_t rng[4], double lag_in,
+                     int force, const double *fresh_to_phi, const double *fresh_to_theta, eap_reinit_out *out,
+                     double *fresh_phi, double *fresh_theta);
 /* the seeded start of chain `chain_id`: EAPChain(pargs) and the generator words after its draws */
 void eap_seed_state(const eap_params *P, uint64_t chain_id, uint32_t rng[4], double *phi, double *theta);
 /* the step-size adaptation of mcmc_eap_chain.jl:301-322 as the run loops apply it after in-run step `step` (1-based) */

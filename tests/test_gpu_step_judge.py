@@ -63,54 +63,11 @@ def ps():
     return ps
 
 
-def _device_params(ps, p, chains, precision, cluster, **kw):
-    return ps.default_params(num_chains=chains, precision=precision,
-                             move_set=ps.MOVES_CLUSTER if cluster else ps.MOVES_SINGLE, **p, **kw)
+_device_params = sj.device_params            # (shared with tests/test_gpu_lifecycle_judge.py)
+_check_adaptation = sj.check_adaptation
 
 
-def _check_adaptation(oracle, op, pre, post, t1, adaptive):
-    """The adaptation rule at a window end (mcmc_eap_chain.jl:301-322), from nacc_window / natt_window; between window ends
-    the step sizes stay and the window counts the step."""
-    dn = post["nacc_total"] - pre["nacc_total"]
-    nacc, natt = pre["nacc_window"] + dn, pre["natt_window"] + 1
-    ps_, ts_ = pre["phi_step"], pre["theta_step"]
-    if adaptive and t1 % op.steps_per_adjust == 0:
-        ps_, ts_, nacc, natt = oracle.adapt(op, t1, ps_, ts_, nacc, natt)
-    got = (post["phi_step"], post["theta_step"], post["nacc_window"], post["natt_window"])
-    assert got == (ps_, ts_, nacc, natt), (t1, got, (ps_, ts_, nacc, natt))
-
-
-def _scale(p):
-    return sj.umbrella_scale(p) if p.get("umbrella") else None
-
-
-def _record_check(who, D, p, acc, block, launch, at, dev_sums, dev_norm, ncol, rise=False):
-    """(d) for one chain: the device's sums read after the steps `at` (0-based) against the twin's prefixes.  D: the stepped
-    handle's record of the chain (recs, usum0, start); acc, launch: record_bound's acc_since_launch and steps per launch.  Returns the worst error / bound of the
-    16 columns and of the extras."""
-    s = _scale(p)
-    at = np.asarray(at)
-    tw = sj.record_twin(D["recs"], s, D["usum0"])
-    B, margin = sj.record_bound(D["recs"], p["n"], acc, block, s, D["usum0"], D["start"], launch)
-    dev_sums, dev_norm = np.asarray(dev_sums)[:, :ncol], np.asarray(dev_norm)
-    if s is None:
-        assert np.array_equal(dev_norm, at + 1.0), f"{who}: normalizer {dev_norm[:4]} is not the number of steps recorded"
-        got = dev_sums
-    else:
-        assert np.all(np.isfinite(dev_norm) & (dev_norm > 0)) and np.all(np.isfinite(dev_sums)), f"{who}: sums or normalizer not finite"
-        got = dev_sums / dev_norm[:, None]
-        assert launch > 1 or margin[at].max() <= sj.GAUGE_MARGIN_MAX, (who, margin[at].max())      # (the stepped handle's margin)
-        over = np.log(dev_norm / tw.nstar[at]) - (sj.GAUGE_T + margin[at])
-        assert np.all(over <= 0), (f"{who}: step {at[np.argmax(over > 0)] + 1}: the heaviest record weighs e^"
-                                   f"{sj.GAUGE_T + margin[at][np.argmax(over > 0)] + over.max():.3f} of the gauge")
-        if rise:
-            assert tw.top.max() >= sj.RISE_MIN and tw.rises[-1] >= 1, (who, tw.top.max())
-    worst = []
-    for lo, hi in ((0, 16), (16, ncol)):
-        q, msg = sj.first_violation(got[:, lo:hi], tw.cols[at][:, lo:hi], B[at][:, lo:hi], at + 1, lo) if hi > lo else (0.0, None)
-        assert msg is None, f"{who}: {msg}"
-        worst.append(q)
-    return worst
+_record_check = sj.record_check          # (shared with tests/test_gpu_lifecycle_judge.py)
 
 
 def _launch_accepts(accepted, every):
@@ -134,6 +91,8 @@ def _judge_run(ps, oracle, cases, chains, precision, cluster, T, judged, kernel,
         assert kernel in name and (not not_kernel or not_kernel not in name), name
         if packed is not None:
             assert info.packed_cases == packed, name
+        if all_pairs and cases[0].get("use_x0"):       # the --x0 start itself (store_phi_rad / store_theta_rad), every chain
+            sj.check_start(oracle, e, cases, ops, chains, precision, cluster=cluster)
         pre = {c: e.chain_state(c) for c in judged}
         lag = {c: 0.0 for c in judged}
         ncol = 18 if cluster else 16
